@@ -12,16 +12,30 @@ RCCL all-reduce of the flat gradient + Adam step.  Graph, features and index are
 HBM before the timed region.  Weak scaling: every rank owns one graph (seed = rank), value =
 sum of edges over ranks / max-over-ranks time.
 
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step if
+--dump-outputs DIR is given, and prints the line.  Everything else it can measure runs only with
+--full: the per-op timing step (roofline `kernels`, `op_ms`, `optimizer_ms`), the other matmul
+modes (`alt_matmul`), the lean activation mode (`alt_activations`), other node / edge numberings
+(`alt_node_order`, `alt_edge_ids`) and the CPU baseline (`cpu_baseline`); the --no-* options
+switch single parts of it off.
+
+  --dump-outputs DIR   after the timed steps: DIR/scores.npy (the logits of the last timed step, in
+                       edge-id order), DIR/loss.npy, DIR/grads.npy and DIR/params.npy (every parameter's
+                       gradient of that step and its value after that step's Adam update, flattened and
+                       concatenated in named_parameters() order), all float32 and of rank 0; --inference:
+                       scores.npy only.  An array that would take the files past 64 MB is replaced by a
+                       fixed, seeded sample of its elements (same sample for the same arguments).
+
 Rank 0 prints ONE JSON line.  Extra objects:
   roofline      SURVEY.md section 8(d): the STEP against the HBM roofline -- achieved = algorithmic bytes
-                (32*H*L per edge) / measured step time, peak 8 TB/s, frac = achieved / peak.  Inside it:
+                (32*H*L per edge) / measured step time, peak 8 TB/s, frac = achieved / peak.  Inside it (--full):
                 `kernels` (every C-ABI op >= 2 % of the step: launches, average launch time from HIP events on
                 the launch stream, its own algorithmic GB/s and TFLOP/s against the HBM / matrix-core peaks,
                 PMC traffic where a committed rocprofv3 pass has it), `dominant_kernel` (the slowest of them),
                 `traffic` = PMC HBM bytes of one step's layer kernels and `traffic_source` = where they
                 were measured (the counters cannot be read from inside this process)
-  cpu_baseline  the CPU oracle (torch restatement of the reference path; "port") timed on this
-                box's host cores on a bounded, smaller sample of the same workload (ratio stated in `sample`)
+  cpu_baseline  (--full) the CPU oracle (torch restatement of the reference path; "port") timed on the
+                host's cores on a bounded, smaller sample of the same workload (ratio stated in `sample`)
 """
 from __future__ import annotations
 
@@ -67,7 +81,35 @@ def parse():
                     help="internal node numbering policy of the graph index (default: the package default, 'auto')")
     ap.add_argument("--permute-edge-ids", action="store_true", help="seeded random edge-id permutation (SURVEY 8d second variant)")
     ap.add_argument("--no-alt-orders", action="store_true", help="skip the alt_node_order / alt_edge_ids measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-op timing step, the other matmul modes, the "
+                         "lean activation mode, other node / edge numberings and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     return ap.parse_args()
+
+
+DUMP_LIMIT = 64_000_000     # bytes over all files of --dump-outputs, npy headers included
+
+
+def dump_outputs(path, arrays):
+    """Write {name: float32 array} as path/<name>.npy.  When they would exceed DUMP_LIMIT, every array of more than
+    4096 elements is cut to the same fraction of its elements: a sorted sample drawn by a generator seeded from the
+    array's name and size, so that two runs with the same arguments write the same elements."""
+    import zlib
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for k, v in arrays.items()}
+    big = {k for k, v in arrays.items() if v.size > 4096}
+    fixed = sum(v.nbytes for k, v in arrays.items() if k not in big) + 256 * len(arrays)      # + npy headers
+    total = sum(arrays[k].nbytes for k in big)
+    if fixed + total > DUMP_LIMIT:
+        frac = (DUMP_LIMIT - fixed) / total
+        for k in sorted(big):
+            v = arrays[k]
+            rng = np.random.default_rng(zlib.crc32(f"{k}:{v.size}".encode()))
+            arrays[k] = v[np.sort(rng.choice(v.size, size=int(v.size * frac), replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def op_model(op: str, N: int, E: int, H: int):
@@ -332,11 +374,15 @@ def main():
 
     opt_ev = None   # (start, end) events around optimizer.step() of the per-op timing step: SURVEY 8(d) "optimizer step reported separately"
     own = []        # world > 1: (event before the step, event before the gradient exchange) = this rank's OWN compute
+    last = {} if args.dump_outputs else None     # --dump-outputs: what the latest step handed back to its caller
 
     def step():
         if args.inference:
             with torch.no_grad():
-                return model(W["graph"], None, W["e"], W["pe"])
+                scores = model(W["graph"], None, W["e"], W["pe"])
+            if last is not None:
+                last["scores"] = scores
+            return scores
         if dist_on:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -353,6 +399,8 @@ def main():
         opt.step()
         if opt_ev is not None:
             opt_ev[1].record()
+        if last is not None:
+            last.update(scores=scores, loss=loss)
         return loss
 
     dbg(f"setup done E={E}")
@@ -400,25 +448,36 @@ def main():
     dbg(f"timed region done {dt:.3f}s")
     ms = dt / args.steps * 1e3
     value = total_edges * args.steps / dt
+    peak_saved = torch.cuda.max_memory_allocated()
+    if last is not None and rank == 0:
+        out = {"scores": last["scores"].detach().reshape(-1).cpu().numpy()}
+        if not args.inference:
+            out["loss"] = last["loss"].detach().reshape(1).cpu().numpy()
+            out["grads"] = torch.cat([p.grad.detach().reshape(-1) for _, p in model.named_parameters()]).cpu().numpy()
+            out["params"] = torch.cat([p.detach().reshape(-1) for _, p in model.named_parameters()]).cpu().numpy()
+        dump_outputs(args.dump_outputs, out)
+        dbg(f"outputs written to {args.dump_outputs}")
+    last = None                                     # the steps after the timed ones keep nothing
 
     # per-op timing of ONE extra (untimed) step: HIP events on the launch stream.  Every rank runs
     # the step (it contains the gradient all-reduce); only rank 0 records and reports.
-    if rank == 0:
-        engine.profile_ops(True)
-        opt_ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-    step()
-    ops = engine.profile_ops(False) if rank == 0 else None
-    optimizer_ms = None
-    if rank == 0 and not args.inference:
-        torch.cuda.synchronize()
-        optimizer_ms = opt_ev[0].elapsed_time(opt_ev[1])
-    opt_ev = None
-    dbg("profile step done")
+    ops = optimizer_ms = None
+    if args.full:
+        if rank == 0:
+            engine.profile_ops(True)
+            opt_ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        step()
+        ops = engine.profile_ops(False) if rank == 0 else None
+        if rank == 0 and not args.inference:
+            torch.cuda.synchronize()
+            optimizer_ms = opt_ev[0].elapsed_time(opt_ev[1])
+        opt_ev = None
+        dbg("profile step done")
     # the other matmul mode of the fused kernels (include/gnm.h), measured the same way right after the
     # default run; reported beside `value`, never as `value`
     alt = None
     mode = G._lib.get_matmul_mode()
-    if args.matmul is None and H == 128 and not args.no_alt_matmul and not args.inference:
+    if args.full and args.matmul is None and H == 128 and not args.no_alt_matmul and not args.inference:
         alt = []
         for other in [m for m in ("f16x2", "bf16x3", "f32") if m != mode]:
             G._lib.set_matmul_mode(other)
@@ -434,8 +493,9 @@ def main():
         dbg("alt matmul run done")
     # the "lean" activation mode (engine.set_activation_mode): one step, for its time and its peak memory
     alt_act = None
-    peak_saved = torch.cuda.max_memory_allocated()
-    if not args.inference and args.matmul is None and not args.no_alt_matmul and engine.ACTIVATIONS == "saved":
+    if args.full:
+        peak_saved = torch.cuda.max_memory_allocated()
+    if args.full and not args.inference and args.matmul is None and not args.no_alt_matmul and engine.ACTIVATIONS == "saved":
         engine.set_activation_mode("lean")
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats()
@@ -451,7 +511,7 @@ def main():
     # are never sorted by position: pipeline.py:46-61,160-169, graph_parser.py:297-304) -- with the index's internal
     # renumbering ('auto') and without it ('keep' = what every gather kernel sees when node ids are taken as they come).
     alt_orders = {}
-    if world == 1 and not args.inference and not args.no_alt_orders and not args.shuffle_nodes and args.matmul is None:
+    if args.full and world == 1 and not args.inference and not args.no_alt_orders and not args.shuffle_nodes and args.matmul is None:
         main_W = dict(W)
         nalt = max(2, args.steps // 2)
         for key, (shuf, perm_e, order) in {"shuffled_node_ids": (True, False, None),
@@ -469,8 +529,8 @@ def main():
         dbg("alt order runs done")
     res = None
     if rank == 0:
-        tot = sum(t for _, t in ops.values())
-        ranked = sorted(ops.items(), key=lambda kv: -kv[1][1])
+        tot = sum(t for _, t in (ops or {}).values())
+        ranked = sorted((ops or {}).items(), key=lambda kv: -kv[1][1])
         # fp32-equivalent FLOP/s of an op's matrix arithmetic: six bf16 MFMAs per product (bf16x3), three fp16 (f16x2), or the fp32 MFMA rate
         def mm_peak_of(op):
             if mode == "f32" or op.startswith(("gnm_predictor", "gnm_edge_encoder")):       # those run fp32 MFMAs in every mode
@@ -543,6 +603,11 @@ def main():
             "optimizer_ms": None if optimizer_ms is None else round(optimizer_ms, 3),
             "peak_mem_gib": round(peak_saved / 2 ** 30, 1),
         }
+        if ops is None:         # no per-op timing step without --full: nothing per kernel to report
+            for k in ("kernels", "dominant_kernel"):
+                del roof[k]
+            for k in ("op_ms", "op_total_ms", "optimizer_ms"):
+                del res[k]
         if alt:
             res["alt_matmul"] = alt
         if alt_act:
@@ -552,7 +617,7 @@ def main():
             res["alt_edge_ids"] = alt_orders.get("alt_edge_ids")
         if per_rank_main:
             res["per_rank"] = per_rank_main
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline_subprocess(args)
         print(json.dumps(res), flush=True)
     if dist_on:

@@ -1870,13 +1870,13 @@ def test_chr1_scale_inference_at_size():
 
 @pytest.mark.mode_independent
 def test_bench_line_contract(tmp_path):
-    """bench.py prints ONE JSON line with the driver's keys, the roofline and cpu_baseline objects."""
+    """bench.py --full prints ONE JSON line with the driver's keys, the roofline and cpu_baseline objects."""
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--reads", "30000", "--steps", "2", "--warmup", "1",
-                          "--cpu-reads", "2000"], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+                          "--cpu-reads", "2000", "--full"], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
