@@ -5,6 +5,7 @@
 // against 0.86 / 0.85 -- were removed in round 5).
 // Rows are in internal (destination-sorted) order; e_raw is read through `perm`.
 #include "gnm_common.h"
+#include "gnm_ln.h"     // row_sum: DPP adds over the 16 lanes of a row
 
 namespace gnm {
 
@@ -27,6 +28,9 @@ constexpr int ENP = EH * EQ + EH + 2 * EQ + EQ;   // gW2 | gb2 | gW1 | gb1 = 222
 //   TN step s, column block cb: A = tile[4 g + s][16 cb + i], B = a1[4 g + s][q = i] -- exactly the four rows the
 //   lane holds of the NN result (C layout of the 16 x 16 MFMA: row 4 g + r, column l & 15).
 // relu mask, gW1, gb1 in that C layout; gb2 from the coalesced load registers.  Partials as above.
+// DX (gnm_edge_encoder_bwd_dx): also the input gradient  ge_raw[perm[row]][f] = sum_q ga1[row][q] W1[q][f]  -- the lane holds
+// ga1 of rows 4 g + r for unit q = i, so a row's sum runs over the 16 lanes of one DPP row (row_sum<16>, gnm_ln.h); row r is
+// written to ge_raw[perm[r]]: a permutation, no atomics.  DX = false is the kernel without it, instruction for instruction.
 // ------------------------------------------------------------------------------------------
 typedef float floatx4m __attribute__((ext_vector_type(4)));
 constexpr int ET = 16;            // rows per wave tile
@@ -39,7 +43,9 @@ template <int EHT> struct EncDims {
   static constexpr int LDS = kWavesPerBlock * ET * EPL > kWavesPerBlock * ENP ? kWavesPerBlock * ET * EPL : kWavesPerBlock * ENP;
 };
 
-template <int EHT>
+// GX: empty, or float* ge_raw (DX) -- a trailing pack, so that the DX = false kernel keeps today's argument list (and with it
+// the offsets of the implicit kernel arguments)
+template <int EHT, typename... GX>
 __global__ __launch_bounds__(kBlock) void edge_encoder_bwd_mfma_k(int64_t E, const float* __restrict__ ge0,
                                                                   const float* __restrict__ e_raw,
                                                                   const int32_t* __restrict__ perm,
@@ -47,7 +53,10 @@ __global__ __launch_bounds__(kBlock) void edge_encoder_bwd_mfma_k(int64_t E, con
                                                                   const float* __restrict__ b1,
                                                                   const float* __restrict__ W2,
                                                                   double* __restrict__ partials,
-                                                                  int64_t tiles_per_block) {
+                                                                  int64_t tiles_per_block, GX... gx) {
+  constexpr bool DX = sizeof...(GX) == 1;
+  static_assert(sizeof...(GX) == 0 || (DX && (std::is_same_v<GX, float*> && ...)), "GX: empty or float* ge_raw");
+  float* const ge_raw = [&]() __attribute__((always_inline)) { if constexpr (DX) return (gx, ...); else return (float*)nullptr; }();
   using D = EncDims<EHT>;
   constexpr int NCB = D::NCB, NH = D::NH, EPL = D::EPL, ENPT = D::ENP;
   __shared__ __attribute__((aligned(16))) float lds[D::LDS];
@@ -82,6 +91,7 @@ __global__ __launch_bounds__(kBlock) void edge_encoder_bwd_mfma_k(int64_t E, con
   auto clampr = [&](int64_t r) __attribute__((always_inline)) { return r < Elast ? r : Elast; };
   float4 gn[NH][8];
   int kn[4];
+  int kx[4];                                        // DX: perm of the tile whose features sit in xn
   float2 xn[4];
   auto load_rows = [&](int64_t t) __attribute__((always_inline)) {
     const int64_t r0 = t * ET;
@@ -97,7 +107,10 @@ __global__ __launch_bounds__(kBlock) void edge_encoder_bwd_mfma_k(int64_t E, con
   };
   auto load_x = [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int s_ = 0; s_ < 4; ++s_) xn[s_] = *reinterpret_cast<const float2*>(e_raw + 2 * (int64_t)kn[s_]);
+    for (int s_ = 0; s_ < 4; ++s_) {
+      xn[s_] = *reinterpret_cast<const float2*>(e_raw + 2 * (int64_t)kn[s_]);
+      if constexpr (DX) kx[s_] = kn[s_];
+    }
   };
   load_perm(tile_of(0));
   load_rows(tile_of(0));
@@ -108,8 +121,12 @@ __global__ __launch_bounds__(kBlock) void edge_encoder_bwd_mfma_k(int64_t E, con
     const int64_t r0 = t * ET;
     const bool live_tile = t < t1;
     float2 x[4];
+    int kc[4];                                         // DX: perm of this tile's rows 4 g + s
 #pragma unroll
-    for (int s_ = 0; s_ < 4; ++s_) x[s_] = xn[s_];
+    for (int s_ = 0; s_ < 4; ++s_) {
+      x[s_] = xn[s_];
+      if constexpr (DX) kc[s_] = kx[s_];
+    }
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const bool live = live_tile && r0 + 2 * q + cr < E;
@@ -144,6 +161,11 @@ __global__ __launch_bounds__(kBlock) void edge_encoder_bwd_mfma_k(int64_t E, con
       gw1_0 = fmaf(ga, x[s_].x, gw1_0);
       gw1_1 = fmaf(ga, x[s_].y, gw1_1);
       gb1_ += ga;
+      if constexpr (DX) {
+        const float gx0 = row_sum<16>(ga * w1a), gx1 = row_sum<16>(ga * w1b);
+        if (i == 0 && live_tile && r0 + 4 * g + s_ < E)
+          *reinterpret_cast<float2*>(ge_raw + 2 * (int64_t)kc[s_]) = make_float2(gx0, gx1);
+      }
     }
     // ---- TN: gW2[16 cb + 4 g + r][q] += sum_rows ge0[row][16 cb + ..] a1[row][q] ----
 #pragma unroll
@@ -293,29 +315,38 @@ extern "C" int gnm_edge_encoder_fwd(int64_t E, int H, int F, int Q, const float*
 // partials must hold gnm_max_partial_blocks() * (H * 16 + H + 48) doubles; the size returned covers H = 256
 extern "C" size_t gnm_edge_encoder_bwd_workspace_bytes(void) { return (size_t)kMaxPartialBlocks * EncDims<2 * EH>::ENP * sizeof(double); }
 
-extern "C" int gnm_edge_encoder_bwd(int64_t E, int H, int F, int Q, const float* ge0, const float* e_raw,
-                                    const int32_t* perm, const float* W1, const float* b1, const float* W2,
-                                    float* gW1, float* gb1, float* gW2, float* gb2, void* ws, size_t ws_bytes,
-                                    void* stream) {
-  GNM_CHECK_ARG((H == EH || H == 2 * EH) && F == 2 && Q == EQ, "edge_encoder_bwd: built for H=128 or 256, edge_features=2, hidden=16 (got %d,%d,%d)", H, F, Q);
-  GNM_CHECK_ARG(E >= 0 && ge0 && e_raw && perm && W1 && b1 && W2 && gW1 && gb1 && gW2 && gb2, "edge_encoder_bwd: null/neg argument");
+// the backward kernel at width EHT: DX = true also writes ge_raw; returns the grid (the number of partial rows), or < 0
+template <int EHT, bool DX>
+static int edge_encoder_bwd_launch(const char* what, int64_t E, const float* ge0, const float* e_raw, const int32_t* perm,
+                                   const float* W1, const float* b1, const float* W2, float* ge_raw, void* ws, size_t ws_bytes,
+                                   hipStream_t st) {
+  const int64_t ntiles = (E + ET - 1) / ET;
+  const int grid = DX ? persistent_grid(ntiles, 16, occ_blocks<edge_encoder_bwd_mfma_k<EHT, float*>>())
+                      : persistent_grid(ntiles, 16, occ_blocks<edge_encoder_bwd_mfma_k<EHT>>());
+  GNM_CHECK_ARG(ws && ws_bytes >= (size_t)grid * EncDims<EHT>::ENP * sizeof(double), "%s: workspace too small", what);
+  if constexpr (DX)
+    hipLaunchKernelGGL((edge_encoder_bwd_mfma_k<EHT, float*>), dim3(grid), dim3(kBlock), 0, st, E, ge0, e_raw, perm, W1, b1, W2,
+                       (double*)ws, (ntiles + grid - 1) / grid, ge_raw);
+  else
+    hipLaunchKernelGGL(edge_encoder_bwd_mfma_k<EHT>, dim3(grid), dim3(kBlock), 0, st, E, ge0, e_raw, perm, W1, b1, W2,
+                       (double*)ws, (ntiles + grid - 1) / grid);
+  return grid;
+}
+
+// the two backward entry points: DX = true also writes ge_raw [E,F] (caller's edge-id order)
+template <bool DX>
+static int edge_encoder_bwd_impl(const char* what, int64_t E, int H, int F, int Q, const float* ge0, const float* e_raw,
+                                 const int32_t* perm, const float* W1, const float* b1, const float* W2, float* gW1, float* gb1,
+                                 float* gW2, float* gb2, float* ge_raw, void* ws, size_t ws_bytes, void* stream) {
+  GNM_CHECK_ARG((H == EH || H == 2 * EH) && F == 2 && Q == EQ, "%s: built for H=128 or 256, edge_features=2, hidden=16 (got %d,%d,%d)", what, H, F, Q);
+  GNM_CHECK_ARG(E >= 0 && ge0 && e_raw && perm && W1 && b1 && W2 && gW1 && gb1 && gW2 && gb2 && (!DX || ge_raw),
+                "%s: null/neg argument", what);
   hipStream_t st = (hipStream_t)stream;
-  int grid;
   const int enp = H * EQ + H + 2 * EQ + EQ;
-  if (H == 2 * EH) {
-    const int64_t ntiles = (E + ET - 1) / ET;
-    grid = persistent_grid(ntiles, 16, occ_blocks<edge_encoder_bwd_mfma_k<2 * EH>>());
-    GNM_CHECK_ARG(ws && ws_bytes >= (size_t)grid * enp * sizeof(double), "edge_encoder_bwd: workspace too small");
-    hipLaunchKernelGGL(edge_encoder_bwd_mfma_k<2 * EH>, dim3(grid), dim3(kBlock), 0, st, E, ge0, e_raw, perm, W1, b1, W2,
-                       (double*)ws, (ntiles + grid - 1) / grid);
-  } else {
-    const int64_t ntiles = (E + ET - 1) / ET;
-    grid = persistent_grid(ntiles, 16, occ_blocks<edge_encoder_bwd_mfma_k<EH>>());
-    GNM_CHECK_ARG(ws && ws_bytes >= (size_t)grid * ENP * sizeof(double), "edge_encoder_bwd: workspace too small");
-    hipLaunchKernelGGL(edge_encoder_bwd_mfma_k<EH>, dim3(grid), dim3(kBlock), 0, st, E, ge0, e_raw, perm, W1, b1, W2,
-                       (double*)ws, (ntiles + grid - 1) / grid);
-  }
-  GNM_LAUNCH_CHECK("edge_encoder_bwd");
+  const int grid = H == 2 * EH ? edge_encoder_bwd_launch<2 * EH, DX>(what, E, ge0, e_raw, perm, W1, b1, W2, ge_raw, ws, ws_bytes, st)
+                               : edge_encoder_bwd_launch<EH, DX>(what, E, ge0, e_raw, perm, W1, b1, W2, ge_raw, ws, ws_bytes, st);
+  if (grid < 0) return grid;
+  GNM_LAUNCH_CHECK(what);
   // gW2 | gb2 | gW1 | gb1 are contiguous in the partial rows; reduce each piece into its tensor
   const double* p = (const double*)ws;
   struct Piece { int off, n; float* out; } pieces[4] = {
@@ -325,4 +356,20 @@ extern "C" int gnm_edge_encoder_bwd(int64_t E, int H, int F, int Q, const float*
     if (reduce_partials_strided(p, grid, enp, pc.off, pc.n, pc.out, stream)) return -3;
   }
   return 0;
+}
+
+extern "C" int gnm_edge_encoder_bwd(int64_t E, int H, int F, int Q, const float* ge0, const float* e_raw,
+                                    const int32_t* perm, const float* W1, const float* b1, const float* W2,
+                                    float* gW1, float* gb1, float* gW2, float* gb2, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  return edge_encoder_bwd_impl<false>("edge_encoder_bwd", E, H, F, Q, ge0, e_raw, perm, W1, b1, W2, gW1, gb1, gW2, gb2, nullptr,
+                                      ws, ws_bytes, stream);
+}
+
+extern "C" int gnm_edge_encoder_bwd_dx(int64_t E, int H, int F, int Q, const float* ge0, const float* e_raw,
+                                       const int32_t* perm, const float* W1, const float* b1, const float* W2,
+                                       float* gW1, float* gb1, float* gW2, float* gb2, float* ge_raw, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  return edge_encoder_bwd_impl<true>("edge_encoder_bwd_dx", E, H, F, Q, ge0, e_raw, perm, W1, b1, W2, gW1, gb1, gW2, gb2, ge_raw,
+                                     ws, ws_bytes, stream);
 }

@@ -398,6 +398,18 @@ def node_rows_in(idx, x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def edge_rank(idx) -> torch.Tensor:
+    """The inverse of idx['perm']: internal position of each caller edge id (int32 [E], built once per index and kept in
+    it).  A gather through it takes [E,W] rows from the internal order back to the caller's edge-id order."""
+    er = idx.get("erank")
+    if er is None:
+        perm = idx["perm"]
+        er = torch.empty_like(perm)
+        er[perm.long()] = torch.arange(perm.numel(), dtype=perm.dtype, device=perm.device)
+        idx["erank"] = er
+    return er
+
+
 def node_rows_out(idx, x: torch.Tensor) -> torch.Tensor:
     """The inverse of node_rows_in: internal numbering -> the caller's."""
     nrank = idx.get("nrank")
@@ -1508,10 +1520,13 @@ def grad_targets(out: Dict[str, torch.Tensor], i: int) -> Optional[Dict[str, tor
 @on_device_of(lambda graph, P, num_layers, ms, gscores, *a, **k: gscores)
 @_scoped(3)
 def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: ModelSaved, gscores, batch_norm: bool = True,
-                   out: Optional[Dict[str, torch.Tensor]] = None, ln_width: Optional[int] = None):
+                   out: Optional[Dict[str, torch.Tensor]] = None, ln_width: Optional[int] = None, inputs: bool = False):
     """Gradients of every parameter (keys = state_dict keys) from d loss / d scores.  With `out` (state_dict key ->
     contiguous tensor of the parameter's shape, e.g. the .grad views of dp.FlatGradients) the kernels write the
-    gradients straight into those tensors and the same tensors are returned."""
+    gradients straight into those tensors and the same tensors are returned.  inputs=True: returns (G, g_e_raw, g_pe)
+    instead, the gradients of model_forward's inputs -- e_raw [E,edge_features] in the caller's edge-id order, pe
+    [N,nb_pos_enc+2] in the caller's node numbering (the encoders' input gradients; inputs=False launches exactly what
+    it launched before the option existed)."""
     dev = ms.pe.device
     _same_matmul_mode(ms)
     idx = graph.index(dev)
@@ -1567,6 +1582,9 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
     lib = _lib.load()
     G["linear_pe.weight"] = tgt("linear_pe.weight", P["linear_pe.weight"])
     G["linear_pe.bias"] = gemm_tn_colsum(gh, ms.pe, G["linear_pe.weight"], out["linear_pe.bias"] if out else None)
+    g_e_raw = g_pe = None
+    if inputs:          # d pe = gh W_pe (full_graph.py:23), internal node numbering -> the caller's
+        g_pe = node_rows_out(idx, gemm(NN, gh, P["linear_pe.weight"], torch.empty(N, ms.pe.shape[1], **f32)))
     G["linear2_edge.weight"] = tgt("linear2_edge.weight", P["linear2_edge.weight"])
     G["linear1_edge.weight"] = tgt("linear1_edge.weight", P["linear1_edge.weight"])
     if ms.a1 is None:      # fused encoder: every encoder gradient from one pass over ge
@@ -1574,10 +1592,17 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
         G["linear1_edge.bias"] = tgt("linear1_edge.bias", P["linear1_edge.bias"])
         need = lib.gnm_edge_encoder_bwd_workspace_bytes()
         ws = scratch(dev).ws(need)
-        _call("gnm_edge_encoder_bwd", E, H, ms.e_raw.shape[1], P["linear1_edge.weight"].shape[0], _ptr(ge),
-              _ptr(ms.e_raw), _ptr(idx["perm"]), _ptr(P["linear1_edge.weight"]), _ptr(P["linear1_edge.bias"]),
-              _ptr(P["linear2_edge.weight"]), _ptr(G["linear1_edge.weight"]), _ptr(G["linear1_edge.bias"]),
-              _ptr(G["linear2_edge.weight"]), _ptr(G["linear2_edge.bias"]), _ptr(ws), need, _stream())
+        if inputs:      # the same pass also writes d e_raw, straight into the caller's edge-id order
+            g_e_raw = torch.empty_like(ms.e_raw)
+            _call("gnm_edge_encoder_bwd_dx", E, H, ms.e_raw.shape[1], P["linear1_edge.weight"].shape[0], _ptr(ge),
+                  _ptr(ms.e_raw), _ptr(idx["perm"]), _ptr(P["linear1_edge.weight"]), _ptr(P["linear1_edge.bias"]),
+                  _ptr(P["linear2_edge.weight"]), _ptr(G["linear1_edge.weight"]), _ptr(G["linear1_edge.bias"]),
+                  _ptr(G["linear2_edge.weight"]), _ptr(G["linear2_edge.bias"]), _ptr(g_e_raw), _ptr(ws), need, _stream())
+        else:
+            _call("gnm_edge_encoder_bwd", E, H, ms.e_raw.shape[1], P["linear1_edge.weight"].shape[0], _ptr(ge),
+                  _ptr(ms.e_raw), _ptr(idx["perm"]), _ptr(P["linear1_edge.weight"]), _ptr(P["linear1_edge.bias"]),
+                  _ptr(P["linear2_edge.weight"]), _ptr(G["linear1_edge.weight"]), _ptr(G["linear1_edge.bias"]),
+                  _ptr(G["linear2_edge.weight"]), _ptr(G["linear2_edge.bias"]), _ptr(ws), need, _stream())
     else:
         gemm(TN, ge, ms.a1, G["linear2_edge.weight"])
         G["linear2_edge.bias"] = colsum(ge, out["linear2_edge.bias"] if out else None)
@@ -1586,7 +1611,11 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
         _call("gnm_relu_mask_f32", ga1.numel(), _ptr(ga1), _ptr(ms.a1), _stream())
         gemm(TN, ga1, ms.e_int, G["linear1_edge.weight"])
         G["linear1_edge.bias"] = colsum(ga1, out["linear1_edge.bias"] if out else None)
-    return G
+        if inputs:      # d e_raw = ga1 W1e in internal order, then gathered back to edge-id order
+            g_int = gemm(NN, ga1, P["linear1_edge.weight"], torch.empty_like(ms.e_int))
+            g_e_raw = torch.empty_like(g_int)
+            _call("gnm_gather_rows_f32", E, g_int.shape[1], _ptr(g_int), _ptr(edge_rank(idx)), _ptr(g_e_raw), _stream())
+    return (G, g_e_raw, g_pe) if inputs else G
 
 
 @on_device_of(lambda scores, *a, **k: scores)

@@ -66,7 +66,7 @@ class _ModelFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, graph, e, pe, num_layers, names, need, norm, *flat):
-        # `need` (grad mode on and some parameter requires grad) is decided by the caller: inside
+        # `need` (grad mode on and some parameter or input e / pe requires grad) is decided by the caller: inside
         # Function.forward grad mode is always off, and needs_input_grad stays set under no_grad.
         # norm = (batch_norm, real hidden width): LayerNorm statistics run over the model's real width when the kernels
         # run it zero-padded to the next width up (gated_gcn_full.py:58-59: nn.LayerNorm(out_channels))
@@ -85,16 +85,21 @@ class _ModelFn(torch.autograd.Function):
         # (the training loops call flat.zero_() before each backward) -> the kernels write the gradients straight
         # into those views and autograd is told "no gradient": accumulating x into zeros is x, and the ~140
         # accumulation kernels per step disappear.  Anything else takes the ordinary autograd route.
+        # Input gradients (e at position 1, pe at 2): the encoders' backward also writes them when asked for.
+        want_e, want_pe = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        inputs = want_e or want_pe
         fg = dp.fresh_flat_gradients(ctx.params)
         if fg is not None and all(ctx.needs_input_grad[7:]):
             out = {k: p.grad for k, p in zip(ctx.names, ctx.params)}
-            engine.model_backward(ctx.graph, ctx.P, ctx.L, ctx.saved, gscores, ctx.bn, out=out, ln_width=ctx.lnw)
+            r = engine.model_backward(ctx.graph, ctx.P, ctx.L, ctx.saved, gscores, ctx.bn, out=out, ln_width=ctx.lnw, inputs=inputs)
             fg.fresh = False
             ctx.saved = None
-            return (None,) * (7 + len(ctx.names))
-        G = engine.model_backward(ctx.graph, ctx.P, ctx.L, ctx.saved, gscores, ctx.bn, ln_width=ctx.lnw)
+            _, ge, gpe = r if inputs else (r, None, None)
+            return (None, ge if want_e else None, gpe if want_pe else None) + (None,) * (4 + len(ctx.names))
+        r = engine.model_backward(ctx.graph, ctx.P, ctx.L, ctx.saved, gscores, ctx.bn, ln_width=ctx.lnw, inputs=inputs)
         ctx.saved = None
-        return (None, None, None, None, None, None, None) + tuple(G[k] for k in ctx.names)
+        G, ge, gpe = r if inputs else (r, None, None)
+        return (None, ge if want_e else None, gpe if want_pe else None, None, None, None, None) + tuple(G[k] for k in ctx.names)
 
 
 def _pad_param(name: str, v: torch.Tensor, H: int, Hp: int) -> torch.Tensor:
@@ -145,17 +150,14 @@ class GraphGatedGCNModel(nn.Module):
             # are 0.5 and gate zeros) and autograd slices the gradients back out of the padded tensors
             names, flat = zip(*self.named_parameters())
             padded = tuple(_pad_param(k, v, H, Hp) for k, v in zip(names, flat))
-            need = torch.is_grad_enabled() and any(p.requires_grad for p in flat)
+            need = torch.is_grad_enabled() and (any(p.requires_grad for p in flat) or e.requires_grad or pe.requires_grad)
             return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H), *padded)
         if pe.is_cuda and not _is_flat(self):
             flatten_parameters(self)          # once per device placement: stacked-parameter views instead of torch.cat
         names, flat = zip(*self.named_parameters())
-        need = torch.is_grad_enabled() and any(p.requires_grad for p in flat)
-        if torch.is_grad_enabled() and (e.requires_grad or pe.requires_grad):
-            # the reference never differentiates its inputs (train.py:245-258); the whole-model backward
-            # stops at the encoders, so refuse instead of returning a silent None for these gradients
-            raise NotImplementedError("GraphGatedGCNModel: gradients w.r.t. the inputs e / pe are not computed; "
-                                      "detach them (the stand-alone layers do return input gradients)")
+        # e / pe requiring grad (input attribution, a frozen model, a learnable transform in front of the encoders) also
+        # needs the activations: the backward returns their gradients; x stays dead (full_graph.py:23), its .grad None
+        need = torch.is_grad_enabled() and (any(p.requires_grad for p in flat) or e.requires_grad or pe.requires_grad)
         return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H), *flat)
 
 

@@ -439,6 +439,12 @@ int gnm_edge_encoder_bwd(int64_t E, int H, int F, int Q, const float* ge0, const
                          const int32_t* perm, const float* W1, const float* b1, const float* W2,
                          float* gW1, float* gb1, float* gW2, float* gb2, void* ws, size_t ws_bytes,
                          void* stream);
+/* the same pass, and also d loss / d e_raw: ge_raw [E,F] in the caller's edge-id order (row j of the internal order
+ * written to ge_raw[perm j], every row exactly once: a permutation, no accumulation).  Same ws as gnm_edge_encoder_bwd. */
+int gnm_edge_encoder_bwd_dx(int64_t E, int H, int F, int Q, const float* ge0, const float* e_raw,
+                            const int32_t* perm, const float* W1, const float* b1, const float* W2,
+                            float* gW1, float* gb1, float* gW2, float* gb2, float* ge_raw, void* ws,
+                            size_t ws_bytes, void* stream);
 
 /* ---- ScorePredictor (score_predictor.py:12-25), split-W1 form ---------------------------
  * hid[j] += Ps[isrc j] + Pd[idst j] (hid holds e*W1e^T+b1 on entry; Pn=[Ps|Pd] is [N,2*HS]);
