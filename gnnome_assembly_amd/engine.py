@@ -644,6 +644,25 @@ def _same_matmul_mode(s) -> None:
                             "gnm_set_matmul_mode is process-wide, change it between steps, not inside one")
 
 
+def _wide_rebuild(idx, N, E, H, prm, s: LayerSaved) -> None:
+    """The lean backward of a wide layer: each chunk's P and t exactly as _wide_layer_forward made them -- both dense products at
+    full width, then per chunk the contiguous copy and gnm_edge_t_stats_fwd (its BatchNorm partial sums are not used: the chunk's
+    saved stat_e is the forward's).  The full-width P and t are dropped as soon as the chunk copies exist."""
+    dev = s.h_in.device
+    sc = scratch(dev)
+    P = torch.empty(N, 5 * H, dtype=torch.float32, device=dev)
+    t = torch.empty(E, H, dtype=torch.float32, device=dev)
+    gemm(NT, s.h_in, prm.W5, P, bias=prm.b5)
+    gemm(NT, s.e_in, prm.W3, t, bias=prm.b3)
+    w = WIDE_CHUNK
+    for ci, c0 in enumerate(range(0, H, w)):
+        sc_ = s.chunks[ci]
+        sc_.P, sc_.t = _cols(P, c0, w, 5), _cols(t, c0, w)
+        _call("gnm_edge_t_stats_fwd", E, w, _ptr(sc_.t), _ptr(sc_.P), _ptr(idx["isrc"]), _ptr(idx["idst"]), _ptr(sc.partials),
+              C.byref(C.c_int(0)), _stream())
+    del P, t
+
+
 def _wide_layer_backward(idx, N, E, H, prm, s: LayerSaved, gh_out, ge, out, residual, plan):
     dev = gh_out.device
     f32 = dict(dtype=torch.float32, device=dev)
@@ -651,6 +670,8 @@ def _wide_layer_backward(idx, N, E, H, prm, s: LayerSaved, gh_out, ge, out, resi
     w = WIDE_CHUNK
     new = lambda key, *shape: out[key] if key in out else torch.empty(*shape, **f32)  # noqa: E731
     g: Dict[str, torch.Tensor] = {k: new(k, H) for k in ("gamma_e", "beta_e", "gamma_h", "beta_h")}
+    if any(c.P is None or c.t is None for c in s.chunks):      # "lean" activations: rebuild every chunk's P and t with the
+        _wide_rebuild(idx, N, E, H, prm, s)                     # kernels that made them, before the first chunk reads them
     gP = torch.empty(N, 5 * H, **f32)
     gt = torch.empty(E, H, **f32)
     ge_tot = ge if residual else None           # the residual path adds the incoming edge gradient: updated in place, chunk by chunk

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from gnnome_assembly_amd import synth
+from oracle import gatedgcn_oracle as orc
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -134,6 +135,163 @@ def branch_exact_rows(src, dst, n, e_raw, pe, y, pw, sd, L, dev):
     return rows, gmax
 
 
+
+
+# -----------------------------------------------------------------------------------------
+# the gradient clauses of the parameter gradients (test_gpu_parity.py) and of the input gradients (test_gpu_input_grads.py),
+# shared with test_gpu_schedule_matrix.py
+# -----------------------------------------------------------------------------------------
+GRAD_L2 = 2e-4          # norm-relative bar for one parameter-gradient tensor (fp32 vs fp64 oracle)
+GRAD_ABS_FLOOR = 2e-7   # gradients that are analytically zero (biases in front of a BatchNorm)
+# Gradients that pass through BatchNorm_e backward (B_1/B_2/B_3, bn_e) are differences of large sums and flip with single
+# relu-boundary elements: the reference's OWN fp32 arithmetic (the oracle run in fp32) differs from fp64 by up to ~1e-3
+# norm-relative on them.  Rounds 1-4 let such a tensor pass when it was no further from the fp64 oracle than NOISE_X times the
+# fp32 oracle is -- a bar that moves with the fixture and bounded nothing.  Since round 5 a BatchNorm model has NO
+# noise clause: a tensor outside GRAD_L2 must be EXACT (rel-L2 <= BRANCH_L2 = 5e-5) against the fp64 backward evaluated on the
+# relu branches the device took -- the network is piecewise linear in those branches, so that comparison has no kink
+# ambiguity and no fixture-dependent slack.  The noise clause survives only where there is no branch-exact oracle (LayerNorm
+# models: none of their tensors has ever needed it).
+NOISE_X = 3.0
+BRANCH_L2 = 5e-5
+
+
+def _grad_ok(r_ours, max_abs, floor, r_ref32=None):
+    """Which clause decides this tensor is tallied per test (helpers.GRAD_CLAUSES -> gpurun_out/grad_clauses.json, committed
+    under profiles/).  BatchNorm models (r_ref32 is None): rel-L2 <= GRAD_L2 or "miss" -- the caller takes the misses to the
+    branch-exact comparison (_branch_exact_or_fail), where the absolute floor is the last resort.  LayerNorm models (no
+    branch-exact oracle): rel-L2, then within NOISE_X of the fp32 oracle's own distance from the fp64 one, then the floor.
+    tests/test_zz_grad_clause_budget.py fails the suite when a test takes more "noise" / "floor" escapes than the committed
+    baseline."""
+    if r_ref32 is None:
+        clause = "l2" if r_ours <= GRAD_L2 else "miss"
+    else:
+        clause = ("l2" if r_ours <= GRAD_L2 else "noise" if r_ours <= NOISE_X * r_ref32 + 1e-6 else
+                  "floor" if max_abs <= floor else "miss")
+    tally_clause(clause)
+    return clause != "miss"
+
+
+def _branch_exact_or_fail(bad, exact, bgmax, what, floor=None):
+    """bad: rows (name, ...) that missed the plain bar; exact: name -> (name, rel_l2, max_abs, ref_norm) against the fp64
+    backward on the device's branches.  Each must be exact (rel-L2 <= BRANCH_L2: tallied "branch_exact") or, failing that, under
+    the absolute floor (max_abs <= max(GRAD_ABS_FLOOR, 1e-6 x the largest gradient norm): "floor" -- the gradients that are
+    analytically zero, e.g. of a bias in front of a BatchNorm)."""
+    floor = max(GRAD_ABS_FLOOR, 1e-6 * bgmax) if floor is None else floor
+    ex = [b for b in bad if exact[b[0]][1] <= BRANCH_L2]
+    fl = [b for b in bad if exact[b[0]][1] > BRANCH_L2 and exact[b[0]][2] <= floor]
+    still = [b for b in bad if exact[b[0]][1] > BRANCH_L2 and exact[b[0]][2] > floor]
+    tally_clause("branch_exact", len(ex), forgiven=True)
+    tally_clause("floor", len(fl), forgiven=True)
+    assert not still, (f"{what}: gradient tensors outside rel-L2 {GRAD_L2:g} of the fp64 oracle AND not exact ({BRANCH_L2:g}) for the "
+                       f"relu branches the device took: {[(b, exact[b[0]]) for b in still]}")
+
+
+def _oracle_grads(z, sd, dtype, batch_norm=True):
+    from oracle import gatedgcn_oracle as orc
+    p = sd_to_torch(sd, dtype, requires_grad=True)
+    s = orc.model_forward(p, torch.from_numpy(z["src"]), torch.from_numpy(z["dst"]), int(z["n"]),
+                          torch.from_numpy(z["e_raw"]).to(dtype), torch.from_numpy(z["pe"]).to(dtype), batch_norm)
+    orc.bce_loss(s, torch.from_numpy(z["y"]).to(dtype), float(z["pos_weight"])).backward()
+    return {k: v.grad.double().numpy() for k, v in p.items()}
+
+
+def _oracle(sd, src, dst, n, e_np, pe_np, y_np, pw, bn):
+    """fp64 autograd of oracle.model_forward: (d loss / d e_raw, d loss / d pe)."""
+    p = sd_to_torch(sd, torch.float64)
+    e = torch.from_numpy(e_np).double().requires_grad_(True)
+    pe = torch.from_numpy(pe_np).double().requires_grad_(True)
+    s = orc.model_forward(p, torch.as_tensor(src).long(), torch.as_tensor(dst).long(), n, e, pe, bn)
+    orc.bce_loss(s, torch.from_numpy(y_np).double(), pw).backward()
+    return e.grad.numpy(), pe.grad.numpy()
+
+
+def _branch_exact(g, sd, H, L, e_np, pe_np, y_np, pw, dev):
+    """The device's input gradients and the fp64 ones evaluated on the relu branches the device took (BatchNorm models;
+    helpers.branch_exact_rows for the input gradients): the network is piecewise linear in those branches, so where a
+    pre-activation within round-off of a kink flips between fp32 and fp64 -- which moves the gradient of the rows behind
+    it by far more than round-off -- this comparison is exact all the same.  Runs the engine on the model's graph `g`
+    (same index, same launches as GraphGatedGCNModel.forward / backward)."""
+    from gnnome_assembly_amd import engine, layers, models
+    P = {k: v.to(dev) for k, v in sd_to_torch(sd).items()}
+    Hp = layers.padded_width(H)
+    if Hp != H:
+        P = {k: models._pad_param(k, v, H, Hp).contiguous() for k, v in P.items()}
+    scores, ms = engine.model_forward(g, torch.from_numpy(e_np).to(dev), torch.from_numpy(pe_np).to(dev), P, L, True)
+    masks = device_masks(ms, sd, e_np, g.index(dev))
+    if e_np.shape[1] != 2:          # the generic encoder: relu of one fp32 GEMM output (device_masks models the fused kernel's fmaf)
+        masks["a1"] = (ms.a1.cpu()[engine.edge_rank(g.index(dev)).long().cpu()] > 0)
+    _, gs = engine.bce_with_logits(scores, torch.from_numpy(y_np).to(dev), pw)
+    _, dev_e, dev_pe = engine.model_backward(g, P, L, ms, gs, inputs=True)
+    torch.cuda.synchronize()
+    if Hp != H:
+        masks["u"] = [m[:, :H] for m in masks["u"]]
+        masks["w"] = [m[:, :H] for m in masks["w"]]
+    s64 = sd_to_torch(sd, torch.float64)
+    src, dst = (t.cpu() for t in g.edges())
+    with torch.no_grad():
+        _, _, _, dbg = orc.manual_forward_backward(s64, src, dst, g.num_nodes(), torch.from_numpy(e_np).double(),
+                                                   torch.from_numpy(pe_np).double(), torch.from_numpy(y_np).double(), pw,
+                                                   keep=True, masks=masks)
+    want_pe = dbg[0]["gh_in"] @ s64["linear_pe.weight"]
+    want_e = ((dbg[0]["ge_in"] @ s64["linear2_edge.weight"]) * masks["a1"]) @ s64["linear1_edge.weight"]
+    return dev_e.cpu(), dev_pe.cpu(), want_e.numpy(), want_pe.numpy()
+
+
+def _check(got_e, got_pe, want_e, want_pe, what, exact=None):
+    """Each input gradient within GRAD_L2 of the fp64 reference or -- BatchNorm models, `exact` given -- exact (BRANCH_L2)
+    against the fp64 backward on the branches the device took (the parameter gradients' two clauses; no other escape)."""
+    ex = None
+    for k, (name, got, want) in enumerate((("d e_raw", got_e, want_e), ("d pe", got_pe, want_pe))):
+        got = np.asarray(got, dtype=np.float64)
+        assert got.shape == want.shape, f"{what} {name}: shape {got.shape} vs {want.shape}"
+        assert np.all(np.isfinite(got)), f"{what} {name}: non-finite values"
+        r = rel_l2(got, want)
+        if r <= GRAD_L2:
+            tally_clause("l2")
+            continue
+        assert exact is not None, f"{what} {name}: rel_l2 {r:.3e} (max abs {np.abs(got - want).max():.3e}), no branch-exact oracle"
+        ex = ex or exact()
+        dev_g, want_x = ex[k], ex[2 + k]
+        assert torch.equal(dev_g, torch.from_numpy(np.asarray(got, dtype=np.float32))), f"{what} {name}: engine route differs"
+        rx = rel_l2(dev_g.numpy(), want_x)
+        print(f"{what} {name}: rel_l2 {r:.3e} against fp64, {rx:.3e} on the device's branches")
+        assert rx <= BRANCH_L2, f"{what} {name}: rel_l2 {r:.3e} against fp64 and {rx:.3e} on the device's own branches"
+        tally_clause("branch_exact")
+
+
+# -----------------------------------------------------------------------------------------
+# the schedule-switch matrix (test_schedule_matrix_cpu.py checks the table, test_gpu_schedule_matrix.py runs it)
+# -----------------------------------------------------------------------------------------
+# Two levels per factor, (default, other): the engine.Options switches except the two side-stream caps (those are exercised by
+# test_gpu_parity.test_side_stream_schedule_and_per_call_caps_change_nothing_but_rounding), and two choices of the caller --
+# "inputs": e / pe require grad (the encoder backward that also writes their gradients), "flat": models.flatten_parameters +
+# dp.FlatGradients(direct_write=True) (the kernels write the parameter gradients straight into the flat buffer).
+SCHEDULE_FACTORS = {
+    "FUSED": (True, False), "ACTIVATIONS": ("saved", "lean"), "CHAIN": (True, False), "TWO_SIDED": (True, False),
+    "TWO_SIDED_FWD": (True, False), "WIDE_FUSED": (True, False), "NODE_FUSED": (True, False), "LN_SWEEP": (True, False),
+    "TN_SIDE": (True, False), "TN_AT": ("auto", "now"), "TN_SPLIT": (True, False), "inputs": (False, True), "flat": (False, True),
+}
+SCHEDULE_CALLER = ("inputs", "flat")            # the factors that are not engine.Options switches
+SCHEDULE_FORWARD = ("FUSED", "TWO_SIDED_FWD", "WIDE_FUSED")     # the switches a forward pass reads (ACTIVATIONS: only what it keeps)
+# The factors each row sets to their non-default level.  Every factor gets its own 3-subset of rows 1..7 that contains row 1, so
+# every pair of levels of every two factors appears in some row (row 0: both defaults; row 1: both others; the rows of one
+# subset that are not in the other: one of each).  TN_AT = "auto" resolves to "next" at the matrix's graph size.
+_SCHEDULE_OFF = {
+    "r0": (),
+    "r1": tuple(SCHEDULE_FACTORS),
+    "r2": ("FUSED", "ACTIVATIONS", "CHAIN", "TWO_SIDED", "flat"),
+    "r3": ("TWO_SIDED_FWD", "WIDE_FUSED", "NODE_FUSED", "LN_SWEEP", "flat"),
+    "r4": ("FUSED", "TWO_SIDED_FWD", "TN_SIDE", "TN_AT"),
+    "r5": ("ACTIVATIONS", "WIDE_FUSED", "TN_SPLIT", "inputs"),
+    "r6": ("CHAIN", "NODE_FUSED", "TN_SIDE", "TN_SPLIT"),
+    "r7": ("TWO_SIDED", "LN_SWEEP", "TN_AT", "inputs"),
+}
+SCHEDULE_ROWS = {r: {f: lv[f in off] for f, lv in SCHEDULE_FACTORS.items()} for r, off in _SCHEDULE_OFF.items()}
+
+
+def schedule_switches(row: dict) -> dict:
+    """The engine.options(...) keywords of a SCHEDULE_ROWS row (every switch given, whatever the process defaults are)."""
+    return {k: v for k, v in row.items() if k not in SCHEDULE_CALLER}
 
 
 # -----------------------------------------------------------------------------------------

@@ -9,15 +9,12 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN, sd_to_torch, rel_l2, device_masks, tally_clause
-from oracle import gatedgcn_oracle as orc
+from helpers import GOLDEN, _branch_exact, _check, _oracle
 
 pytestmark = pytest.mark.gpu
 
 INPUT_GRADS = os.path.join(GOLDEN, "input_grads")
 CASES = sorted(f for f in os.listdir(INPUT_GRADS) if f.endswith(".npz"))
-GRAD_L2 = 2e-4          # the parameter gradients' bar (test_gpu_parity.GRAD_L2)
-BRANCH_L2 = 5e-5        # ... and their exact comparison on the device's relu branches (test_gpu_parity.BRANCH_L2)
 
 
 @pytest.fixture(autouse=True, params=["f16x2", "bf16x3", "f32"])
@@ -51,70 +48,6 @@ def _run(model, g, e_np, pe_np, y_np, pw, dev, inputs=True):
     torch.cuda.synchronize()
     grads = {k: p.grad.cpu() for k, p in model.named_parameters() if p.grad is not None}
     return s.detach().cpu(), grads, (e.grad.cpu() if inputs else None), (pe.grad.cpu() if inputs else None)
-
-
-def _oracle(sd, src, dst, n, e_np, pe_np, y_np, pw, bn):
-    """fp64 autograd of oracle.model_forward: (d loss / d e_raw, d loss / d pe)."""
-    p = sd_to_torch(sd, torch.float64)
-    e = torch.from_numpy(e_np).double().requires_grad_(True)
-    pe = torch.from_numpy(pe_np).double().requires_grad_(True)
-    s = orc.model_forward(p, torch.as_tensor(src).long(), torch.as_tensor(dst).long(), n, e, pe, bn)
-    orc.bce_loss(s, torch.from_numpy(y_np).double(), pw).backward()
-    return e.grad.numpy(), pe.grad.numpy()
-
-
-def _branch_exact(g, sd, H, L, e_np, pe_np, y_np, pw, dev):
-    """The device's input gradients and the fp64 ones evaluated on the relu branches the device took (BatchNorm models;
-    helpers.branch_exact_rows for the input gradients): the network is piecewise linear in those branches, so where a
-    pre-activation within round-off of a kink flips between fp32 and fp64 -- which moves the gradient of the rows behind
-    it by far more than round-off -- this comparison is exact all the same.  Runs the engine on the model's graph `g`
-    (same index, same launches as GraphGatedGCNModel.forward / backward)."""
-    from gnnome_assembly_amd import engine, layers, models
-    P = {k: v.to(dev) for k, v in sd_to_torch(sd).items()}
-    Hp = layers.padded_width(H)
-    if Hp != H:
-        P = {k: models._pad_param(k, v, H, Hp).contiguous() for k, v in P.items()}
-    scores, ms = engine.model_forward(g, torch.from_numpy(e_np).to(dev), torch.from_numpy(pe_np).to(dev), P, L, True)
-    masks = device_masks(ms, sd, e_np, g.index(dev))
-    if e_np.shape[1] != 2:          # the generic encoder: relu of one fp32 GEMM output (device_masks models the fused kernel's fmaf)
-        masks["a1"] = (ms.a1.cpu()[engine.edge_rank(g.index(dev)).long().cpu()] > 0)
-    _, gs = engine.bce_with_logits(scores, torch.from_numpy(y_np).to(dev), pw)
-    _, dev_e, dev_pe = engine.model_backward(g, P, L, ms, gs, inputs=True)
-    torch.cuda.synchronize()
-    if Hp != H:
-        masks["u"] = [m[:, :H] for m in masks["u"]]
-        masks["w"] = [m[:, :H] for m in masks["w"]]
-    s64 = sd_to_torch(sd, torch.float64)
-    src, dst = (t.cpu() for t in g.edges())
-    with torch.no_grad():
-        _, _, _, dbg = orc.manual_forward_backward(s64, src, dst, g.num_nodes(), torch.from_numpy(e_np).double(),
-                                                   torch.from_numpy(pe_np).double(), torch.from_numpy(y_np).double(), pw,
-                                                   keep=True, masks=masks)
-    want_pe = dbg[0]["gh_in"] @ s64["linear_pe.weight"]
-    want_e = ((dbg[0]["ge_in"] @ s64["linear2_edge.weight"]) * masks["a1"]) @ s64["linear1_edge.weight"]
-    return dev_e.cpu(), dev_pe.cpu(), want_e.numpy(), want_pe.numpy()
-
-
-def _check(got_e, got_pe, want_e, want_pe, what, exact=None):
-    """Each input gradient within GRAD_L2 of the fp64 reference or -- BatchNorm models, `exact` given -- exact (BRANCH_L2)
-    against the fp64 backward on the branches the device took (the parameter gradients' two clauses; no other escape)."""
-    ex = None
-    for k, (name, got, want) in enumerate((("d e_raw", got_e, want_e), ("d pe", got_pe, want_pe))):
-        got = np.asarray(got, dtype=np.float64)
-        assert got.shape == want.shape, f"{what} {name}: shape {got.shape} vs {want.shape}"
-        assert np.all(np.isfinite(got)), f"{what} {name}: non-finite values"
-        r = rel_l2(got, want)
-        if r <= GRAD_L2:
-            tally_clause("l2")
-            continue
-        assert exact is not None, f"{what} {name}: rel_l2 {r:.3e} (max abs {np.abs(got - want).max():.3e}), no branch-exact oracle"
-        ex = ex or exact()
-        dev_g, want_x = ex[k], ex[2 + k]
-        assert torch.equal(dev_g, torch.from_numpy(np.asarray(got, dtype=np.float32))), f"{what} {name}: engine route differs"
-        rx = rel_l2(dev_g.numpy(), want_x)
-        print(f"{what} {name}: rel_l2 {r:.3e} against fp64, {rx:.3e} on the device's branches")
-        assert rx <= BRANCH_L2, f"{what} {name}: rel_l2 {r:.3e} against fp64 and {rx:.3e} on the device's own branches"
-        tally_clause("branch_exact")
 
 
 @pytest.mark.parametrize("fname", CASES)

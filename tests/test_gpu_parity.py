@@ -14,6 +14,7 @@ import torch
 
 from conftest import golden_files
 from helpers import GOLDEN, load_case, grad_stride_of, sd_to_torch, rel_l2, assert_parity, tally_clause, RTOL, ATOL
+from helpers import GRAD_L2, GRAD_ABS_FLOOR, NOISE_X, BRANCH_L2, _grad_ok, _branch_exact_or_fail, _oracle_grads  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -32,58 +33,6 @@ def matmul_mode(request):
     _lib.set_matmul_mode(request.param)
     yield request.param
     _lib.set_matmul_mode(_lib.DEFAULT_MATMUL_MODE)
-
-GRAD_L2 = 2e-4          # norm-relative bar for one parameter-gradient tensor (fp32 vs fp64 oracle)
-GRAD_ABS_FLOOR = 2e-7   # gradients that are analytically zero (biases in front of a BatchNorm)
-# Gradients that pass through BatchNorm_e backward (B_1/B_2/B_3, bn_e) are differences of large sums and flip with single
-# relu-boundary elements: the reference's OWN fp32 arithmetic (the oracle run in fp32) differs from fp64 by up to ~1e-3
-# norm-relative on them.  Rounds 1-4 let such a tensor pass when it was no further from the fp64 oracle than NOISE_X times the
-# fp32 oracle is -- a bar that moves with the fixture and bounded nothing.  Since round 5 a BatchNorm model has NO
-# noise clause: a tensor outside GRAD_L2 must be EXACT (rel-L2 <= BRANCH_L2 = 5e-5) against the fp64 backward evaluated on the
-# relu branches the device took -- the network is piecewise linear in those branches, so that comparison has no kink
-# ambiguity and no fixture-dependent slack.  The noise clause survives only where there is no branch-exact oracle (LayerNorm
-# models: none of their tensors has ever needed it).
-NOISE_X = 3.0
-
-
-def _grad_ok(r_ours, max_abs, floor, r_ref32=None):
-    """Which clause decides this tensor is tallied per test (helpers.GRAD_CLAUSES -> gpurun_out/grad_clauses.json, committed
-    under profiles/).  BatchNorm models (r_ref32 is None): rel-L2 <= GRAD_L2 or "miss" -- the caller takes the misses to the
-    branch-exact comparison (_branch_exact_or_fail), where the absolute floor is the last resort.  LayerNorm models (no
-    branch-exact oracle): rel-L2, then within NOISE_X of the fp32 oracle's own distance from the fp64 one, then the floor.
-    tests/test_zz_grad_clause_budget.py fails the suite when a test takes more "noise" / "floor" escapes than the committed
-    baseline."""
-    if r_ref32 is None:
-        clause = "l2" if r_ours <= GRAD_L2 else "miss"
-    else:
-        clause = ("l2" if r_ours <= GRAD_L2 else "noise" if r_ours <= NOISE_X * r_ref32 + 1e-6 else
-                  "floor" if max_abs <= floor else "miss")
-    tally_clause(clause)
-    return clause != "miss"
-
-
-def _branch_exact_or_fail(bad, exact, bgmax, what, floor=None):
-    """bad: rows (name, ...) that missed the plain bar; exact: name -> (name, rel_l2, max_abs, ref_norm) against the fp64
-    backward on the device's branches.  Each must be exact (rel-L2 <= BRANCH_L2: tallied "branch_exact") or, failing that, under
-    the absolute floor (max_abs <= max(GRAD_ABS_FLOOR, 1e-6 x the largest gradient norm): "floor" -- the gradients that are
-    analytically zero, e.g. of a bias in front of a BatchNorm)."""
-    floor = max(GRAD_ABS_FLOOR, 1e-6 * bgmax) if floor is None else floor
-    ex = [b for b in bad if exact[b[0]][1] <= BRANCH_L2]
-    fl = [b for b in bad if exact[b[0]][1] > BRANCH_L2 and exact[b[0]][2] <= floor]
-    still = [b for b in bad if exact[b[0]][1] > BRANCH_L2 and exact[b[0]][2] > floor]
-    tally_clause("branch_exact", len(ex), forgiven=True)
-    tally_clause("floor", len(fl), forgiven=True)
-    assert not still, (f"{what}: gradient tensors outside rel-L2 {GRAD_L2:g} of the fp64 oracle AND not exact ({BRANCH_L2:g}) for the "
-                       f"relu branches the device took: {[(b, exact[b[0]]) for b in still]}")
-
-
-def _oracle_grads(z, sd, dtype, batch_norm=True):
-    from oracle import gatedgcn_oracle as orc
-    p = sd_to_torch(sd, dtype, requires_grad=True)
-    s = orc.model_forward(p, torch.from_numpy(z["src"]), torch.from_numpy(z["dst"]), int(z["n"]),
-                          torch.from_numpy(z["e_raw"]).to(dtype), torch.from_numpy(z["pe"]).to(dtype), batch_norm)
-    orc.bce_loss(s, torch.from_numpy(z["y"]).to(dtype), float(z["pos_weight"])).backward()
-    return {k: v.grad.double().numpy() for k, v in p.items()}
 
 
 def _dev():
@@ -328,7 +277,7 @@ def test_model_matches_golden(fname):
     if bad and bn:
         # A tensor outside the plain bar passes ONLY if the whole deviation is a relu decision that fell the other way in
         # fp32 (every fp32 evaluation, the reference's own included, flips some): against the fp64 backward evaluated on the
-        # branches the device took it must agree to fp32 round-off.  No noise clause (see GRAD_L2 above).
+        # branches the device took it must agree to fp32 round-off.  No noise clause (see helpers.GRAD_L2).
         brows, bgmax = _branch_exact_rows(z["src"], z["dst"], int(z["n"]), z["e_raw"], z["pe"], z["y"],
                                           float(z["pos_weight"]), sd, L, dev)
         _branch_exact_or_fail(bad, {r[0]: r for r in brows}, bgmax, fname)
@@ -984,9 +933,6 @@ def test_other_widths_and_norms_vs_oracle(H, L, bn):
 
 
 from helpers import branch_exact_rows as _branch_exact_rows  # noqa: E402  (shared with __graft_entry__.smoke)
-
-
-BRANCH_L2 = 5e-5
 
 
 @pytest.mark.parametrize("case", ["small_h128l8_s0.npz", "small_h128l8_s1.npz", "small_h64l1_s1.npz", "tiny_h64l1_s0.npz",
