@@ -260,42 +260,67 @@ def _side_stream(device):
     return _side_streams[device]
 
 
-_side_held: Dict[torch.device, list] = {}       # what the side stream of a device is reading (kept alive until the main stream has waited)
+class SideLane:
+    """The side stream of ONE backward pass (model_backward makes it and drains it): weight gradients with no consumer before
+    the optimizer step run there, beside HBM-bound passes of the main stream (see TN_SIDE).  The schedules decide WHEN to
+    launch; the lane knows HOW.  It keeps what the side stream reads alive until the main stream has waited for it (no
+    record_stream: blocks parked on a side-stream event made the allocator fall back to hipMalloc / hipFree in the lean mode:
+    3x the step time), and its scratch is allocated and grown only with the side stream current, so a block it gives up goes
+    back to the side stream's pool.  Main-stream launches never use that scratch."""
 
+    def __init__(self, device):
+        self.device = device
+        self.side = _side_stream(device)
+        self.main = torch.cuda.current_stream(device)
+        self.held: List[torch.Tensor] = []
+        self.sc: Optional[_Scratch] = None      # made at the first launch
 
-def side_begin(device):
-    """The side stream of `device`, ready for one more launch: the main stream first waits for what ran there before (a layer ago:
-    free) -- which also makes the held tensors safe to drop -- and the side stream for the main stream's work so far."""
-    device = torch.device(device)
-    side = _side_stream(device)
-    main = torch.cuda.current_stream(device)
-    main.wait_stream(side)
-    _side_held.setdefault(device, []).clear()
-    side.wait_stream(main)
-    return side
+    def begin(self) -> None:
+        """Ready for one more launch: the main stream first waits for what ran there before (a layer ago: free) -- which also
+        makes the held tensors safe to drop -- and the side stream for the main stream's work so far."""
+        self.main.wait_stream(self.side)
+        self.held.clear()
+        self.side.wait_stream(self.main)
 
+    def wait_for_main(self) -> None:
+        """A further launch since begin(): the side stream only waits for the main stream's work so far."""
+        self.side.wait_stream(self.main)
 
-def tn_on_side(device, A, B, C_, out, first: bool) -> None:
-    """gemm_tn_colsum(A, B, C_, out) on the side stream of `device` (a weight gradient: no consumer before the optimizer step), its
-    operands held until the main stream has waited for it.  first: the first deferred launch since the main stream last waited
-    (side_begin); a further one only makes the side stream wait for the main stream's work so far."""
-    device = torch.device(device)
-    if first:
-        side = side_begin(device)
-    else:
-        side = _side_stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-    with torch.cuda.stream(side):
-        gemm_tn_colsum(A, B, C_, out, sc_key="tn")
-    _side_held[device].extend((A, B, C_, out))
+    def drain(self) -> None:
+        """The main stream waits for everything launched here; the held tensors are released."""
+        self.main.wait_stream(self.side)
+        self.held.clear()
 
+    def _ws(self, need: int) -> torch.Tensor:
+        with torch.cuda.stream(self.side):
+            self.sc = self.sc or scratch(self.device, "side")
+            return self.sc.ws(need)
 
-def side_drain(device) -> None:
-    """The main stream waits for the side stream's work (layer_backward(..., defer_tn=True)); the held tensors are released."""
-    device = torch.device(device)
-    if device in _side_streams:
-        torch.cuda.current_stream(device).wait_stream(_side_streams[device])
-    _side_held.get(device, []).clear()
+    def node_proj_bwd_tn(self, N: int, H: int, gP, h, W, b) -> None:
+        lib = _lib.load()
+        need = lib.gnm_node_proj_bwd_workspace_bytes(5 * H)
+        ws = self._ws(need)
+        _lib.check(lib.gnm_node_proj_bwd_tn(N, H, 5 * H, _ptr(gP), _ptr(h), _ptr(W), _ptr(b), _ptr(self.sc.partials), _ptr(ws), need,
+                                            current().TN_SIDE_CAP, C.c_void_p(self.side.cuda_stream)), "gnm_node_proj_bwd_tn")
+        self.held += (gP, h, W, b)
+
+    def tn128(self, N: int, A, lda: int, ncg: int, h, W, b) -> None:
+        lib = _lib.load()
+        need = lib.gnm_tn128_workspace_bytes()
+        ws = self._ws(need)
+        _lib.check(lib.gnm_tn128(N, _ptr(A), lda, ncg, _ptr(h), _ptr(W), _ptr(b), _ptr(self.sc.partials), _ptr(ws), need,
+                                 C.c_void_p(self.side.cuda_stream)), "gnm_tn128")
+        self.held += (A, h, W, b)
+
+    def gemm_tn_colsum(self, A, B, C_, out) -> None:
+        """gemm_tn_colsum(A, B, C_, out) here (the shapes are the layer's own)."""
+        lib = _lib.load()
+        (K, M), N = A.shape, B.shape[1]
+        need = lib.gnm_gemm_tn_colsum_workspace_bytes(M, N, K)
+        ws = self._ws(need) if need else None
+        _lib.check(lib.gnm_gemm_tn_colsum(M, N, K, _ptr(A), A.stride(0), _ptr(B), B.stride(0), _ptr(C_), C_.stride(0), _ptr(out),
+                                          _ptr(ws), need, C.c_void_p(self.side.cuda_stream)), "gnm_gemm_tn_colsum")
+        self.held += (A, B, C_, out)
 
 
 # ---------------------------------------------------------------------------------------
@@ -333,11 +358,9 @@ def gemm(mode: int, A: torch.Tensor, B: torch.Tensor, C_: torch.Tensor, bias=Non
 
 
 @on_device_of(lambda A, *a, **k: A)
-def gemm_tn_colsum(A: torch.Tensor, B: torch.Tensor, C_: torch.Tensor, out: Optional[torch.Tensor] = None,
-                   sc_key: str = "main") -> torch.Tensor:
+def gemm_tn_colsum(A: torch.Tensor, B: torch.Tensor, C_: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """C = A^T B and the column sums of A (weight and bias gradient of a Linear: A = grad of its output [rows, out],
-    B = its input [rows, in]); returns the column sums.  sc_key: which scratch workspace the call uses (a launch on the side
-    stream must not share the main stream's)."""
+    B = its input [rows, in]); returns the column sums."""
     lib = _lib.load()
     _chk_dev(A, B, C_, out)
     for t in (A, B, C_):
@@ -350,7 +373,7 @@ def gemm_tn_colsum(A: torch.Tensor, B: torch.Tensor, C_: torch.Tensor, out: Opti
     if out is None:
         out = torch.empty(M, dtype=torch.float32, device=A.device)
     need = lib.gnm_gemm_tn_colsum_workspace_bytes(M, N, K)
-    ws = scratch(A.device, sc_key).ws(need) if need else None
+    ws = scratch(A.device).ws(need) if need else None
     _call("gnm_gemm_tn_colsum", M, N, K, _ptr(A), A.stride(0), _ptr(B), B.stride(0), _ptr(C_), C_.stride(0), _ptr(out),
           _ptr(ws), need, _stream(), tag=f"gemm_TN+colsum[{M}x{N}x{K}]" if _prof is not None else None)
     return out
@@ -761,21 +784,20 @@ def _bn_backward_mid(idx, N, E, H, prm, s, gh_out, ge, out, plan):
 @_scoped(5)
 def layer_backward(idx, N: int, E: int, H: int, prm: LayerParams, s: LayerSaved, gh_out, ge, batch_norm: bool = True,
                    out: Optional[Dict[str, torch.Tensor]] = None, residual: bool = True, plan: Optional[dict] = None,
-                   ln_width: Optional[int] = None, defer_tn: bool = False):
+                   ln_width: Optional[int] = None, lane: Optional[SideLane] = None):
     """Backward of layer_forward.  `ge` ([E,H], internal order) holds d loss / d e_out on entry
     and is OVERWRITTEN with d loss / d e_in (residual layers; without the residual the returned ge is a fresh [E,Hin]
     tensor).  Returns (gh_in, ge, grads dict).  `out` (optional) names the tensors
     the parameter gradients are written INTO (keys W5 b5 W3 b3 gamma_e beta_e gamma_h beta_h; contiguous blocks,
     e.g. views of a flat gradient buffer) instead of fresh allocations.
-    defer_tn (H = 128 fused route): the node-projection weight gradient may run on the side stream; the CALLER then calls
-    side_drain(device) before anything reads W5 / b5 gradients (model_backward does, after the last layer)."""
+    lane (H = 128 fused route, H = 256): the weight gradients may run on its side stream; the CALLER then drains it before
+    anything reads them (model_backward does, after the last layer).  None: everything on the current stream."""
     out = out or {}
     Hin = s.h_in.shape[1]
     lnw = H if ln_width is None else int(ln_width)
     fused = H == 128 and current().FUSED and residual          # the fused backward kernels have the residual adds built in
-    # the two weight-gradient GEMMs of a 256-wide layer on the side stream (model_backward drains): see tn_on_side
-    defer_side = (defer_tn and H == 256 and batch_norm and current().TN_SIDE and _prof is None and current().ACTIVATIONS != "lean"
-                  and _lib.split_mode())
+    # the two weight-gradient GEMMs of a 256-wide layer on the side stream
+    defer_side = lane is not None and H == 256 and batch_norm and _lib.split_mode()
     deferred_first = True
     new = lambda key, *shape: out[key] if key in out else torch.empty(*shape, dtype=torch.float32, device=gh_out.device)  # noqa: E731
     lib = _lib.load()
@@ -854,7 +876,8 @@ def layer_backward(idx, N: int, E: int, H: int, prm: LayerParams, s: LayerSaved,
             ge = ge_in
             if defer_side:          # round 6: beside the next layer's HBM-bound sweep instead of in front of it
                 g["b3"] = new("b3", H)
-                tn_on_side(dev, gt, s.e_in, g["W3"], g["b3"], first=True)
+                lane.begin()
+                lane.gemm_tn_colsum(gt, s.e_in, g["W3"], g["b3"])
                 deferred_first = False
             else:
                 g["b3"] = gemm_tn_colsum(gt, s.e_in, g["W3"], out.get("b3"))
@@ -877,15 +900,11 @@ def layer_backward(idx, N: int, E: int, H: int, prm: LayerParams, s: LayerSaved,
         need = lib.gnm_node_proj_bwd_workspace_bytes(5 * H)
         ws = sc.ws(need)
         _call("gnm_node_proj_bwd_nn", N, H, 5 * H, _ptr(gP), _ptr(prm.W5), _ptr(gh_out), _ptr(gh_in), _ptr(ws), need, st)
-        if defer_tn and current().TN_SIDE and _prof is None and current().ACTIVATIONS != "lean":
+        if lane is not None:
             # the weight gradient has no consumer before the optimizer step: on the side stream, beside the next layer's HBM-bound
-            # node / by-destination passes (what the chained schedule does with its deferred kernel); the caller drains (side_drain)
-            side = side_begin(dev)
-            sc3 = scratch(dev, "tn")
-            ws3 = sc3.ws(need)
-            _lib.check(lib.gnm_node_proj_bwd_tn(N, H, 5 * H, _ptr(gP), _ptr(s.h_in), _ptr(g["W5"]), _ptr(g["b5"]), _ptr(sc3.partials),
-                                                _ptr(ws3), need, current().TN_SIDE_CAP, C.c_void_p(side.cuda_stream)), "gnm_node_proj_bwd_tn")
-            _side_held[torch.device(dev)].extend((gP, s.h_in, g["W5"], g["b5"]))
+            # node / by-destination passes (what the chained schedule does with its deferred kernel)
+            lane.begin()
+            lane.node_proj_bwd_tn(N, H, gP, s.h_in, g["W5"], g["b5"])
         else:
             _call("gnm_node_proj_bwd_tn", N, H, 5 * H, _ptr(gP), _ptr(s.h_in), _ptr(g["W5"]), _ptr(g["b5"]),
                   _ptr(sc.partials), _ptr(ws), need, 0, st)
@@ -893,7 +912,8 @@ def layer_backward(idx, N: int, E: int, H: int, prm: LayerParams, s: LayerSaved,
         gemm(NN, gP, prm.W5, gh_in, resid=gh_out if residual else None)
         if defer_side:
             g["b5"] = new("b5", 5 * H)
-            tn_on_side(dev, gP, s.h_in, g["W5"], g["b5"], first=deferred_first)
+            lane.begin() if deferred_first else lane.wait_for_main()
+            lane.gemm_tn_colsum(gP, s.h_in, g["W5"], g["b5"])
         else:
             g["b5"] = gemm_tn_colsum(gP, s.h_in, g["W5"], out.get("b5"))
     return gh_in, ge, g
@@ -961,14 +981,9 @@ _D_NODE_FUSED = os.environ.get("GNM_NODE_FUSED", "1") != "0"
 _D_LN_SWEEP = os.environ.get("GNM_LN_SWEEP", "1") != "0"
 
 
-def tn128(N: int, A: torch.Tensor, lda: int, ncg: int, h: torch.Tensor, W, b, partials, ws, need, stream=None, tag: str = None):
-    """gW[cg] = A[:, cg]^T h, gb[cg] = sum A[:, cg] (gnm_tn128).  `stream`: a torch side stream (the call is then not profiled);
-    None = the current stream."""
-    if stream is None:
-        _call("gnm_tn128", N, _ptr(A), lda, ncg, _ptr(h), _ptr(W), _ptr(b), _ptr(partials), _ptr(ws), need, _stream(), tag=tag)
-    else:
-        _lib.check(_lib.load().gnm_tn128(N, _ptr(A), lda, ncg, _ptr(h), _ptr(W), _ptr(b), _ptr(partials), _ptr(ws), need,
-                                         C.c_void_p(stream.cuda_stream)), "gnm_tn128")
+def tn128(N: int, A: torch.Tensor, lda: int, ncg: int, h: torch.Tensor, W, b, partials, ws, need, tag: str = None):
+    """gW[cg] = A[:, cg]^T h, gb[cg] = sum A[:, cg] (gnm_tn128) on the current stream (SideLane.tn128: on the side stream)."""
+    _call("gnm_tn128", N, _ptr(A), lda, ncg, _ptr(h), _ptr(W), _ptr(b), _ptr(partials), _ptr(ws), need, _stream(), tag=tag)
 
 
 # workgroups per CU of the two-sided forward sweep (the partition its plan is built for); 1 only together with
@@ -987,7 +1002,8 @@ def chain_eligible(H: int, batch_norm: bool) -> bool:
 
 
 def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tensor], L: int, saved: List[LayerSaved],
-                            gh, ge, outs: List[Optional[Dict[str, torch.Tensor]]], plan: Optional[dict] = None):
+                            gh, ge, outs: List[Optional[Dict[str, torch.Tensor]]], plan: Optional[dict] = None,
+                            lane: Optional[SideLane] = None):
     """Backward of the L-layer stack (layers L-1 .. 0), same arithmetic as L x layer_backward, other schedule:
         node(L-1), dst(L-1);   then for i = L-1 .. 0:   finalize_e(i), src(i), proj(i),
                                                          i > 0:  node(i-1), CHAIN[fused(i) + dst(i-1)]
@@ -995,10 +1011,11 @@ def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tens
     `ge` is updated in place through all layers.  Returns (gh_in of layer 0, ge_in of layer 0, [grads dict per layer]);
     saved[i] is released as soon as layer i is done.  outs[i]: write-into targets as in layer_backward (or None).
     With `plan` (graph.sweep_plan) the chained kernel is the two-sided sweep: src(i) for i < L-1 becomes
-    fix(i) [right after CHAIN(i+1, i)] + bgrad(i) [after finalize_e(i)]."""
+    fix(i) [right after CHAIN(i+1, i)] + bgrad(i) [after finalize_e(i)].  With `lane` the node-projection weight gradients run on
+    its side stream (TN_AT, TN_SPLIT say when); the caller drains it."""
     lib = _lib.load()
     dev = gh.device
-    sc, sc2 = scratch(dev), scratch(dev, "side")
+    sc, sc2 = scratch(dev), scratch(dev, "chain")     # sc2: the chained kernel's second partials buffer
     st = _stream()
     f32 = dict(dtype=torch.float32, device=dev)
     grads: List[Dict[str, torch.Tensor]] = [dict() for _ in range(L)]
@@ -1059,19 +1076,10 @@ def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tens
     if current().ACTIVATIONS == "lean":
         s.P = None              # as below: only the by-destination pass reads the rebuilt P
     # not in the lean mode: the deferred kernel keeps its gP (one [E,H]-sized tensor) alive one layer longer
-    side = _side_stream(dev) if (current().TN_SIDE and _prof is None and current().ACTIVATIONS != "lean") else None
-    main = torch.cuda.current_stream()
     fusedn = current().NODE_FUSED and plan is not None      # the node side without node_bgrad / node_bwd_stats launches (see NODE_FUSED)
     at_now = tn_at(N) == "now"          # when the deferred weight-gradient kernel is launched (TN_AT; "auto": by graph size)
     pending = None              # (gP, h_in, gW5, gb5) of the layer above: its weight-gradient kernel, not yet launched
     pending2 = None             # the same, when only its first launch (TN_SPLIT) has been issued
-    held: List[torch.Tensor] = []   # what the side stream is reading; dropped only after the main stream has waited for it
-
-    def side_begin():
-        main.wait_stream(side)      # the previous deferred kernel ended a layer ago: free, and makes `held` safe to drop
-        held.clear()                # (no record_stream: blocks parked on a side-stream event made the allocator
-        side.wait_stream(main)      #  fall back to hipMalloc / hipFree in the lean mode: 3x the step time)
-
     while True:
         prm, s = prms[i], saved[i]
         o = outs[i] or {}
@@ -1085,12 +1093,9 @@ def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tens
             # ---- round 5: tn34(i) [forms gB1h | gB2h from the raw sums, writes them to gP, their weight gradient] ->
             #      nn(i) [+ the BatchNorm_h backward sums of layer i-1 in its epilogue];  the weight gradient of the other three
             #      column groups on the side stream beside the HBM-bound BatchNorm_h backward of layer i-1
-            sc3 = scratch(dev, "tn")
-            if side is not None and pending is not None:        # tn012 of the layer above, deferred (TN_AT = "next")
-                pgP, ph, pW, pb = pending
-                side_begin()
-                tn128(N, pgP, 5 * H, 3, ph, pW, pb, sc3.partials, sc3.ws(need_t), need_t, stream=side)
-                held.extend((pgP, ph))
+            if pending is not None:         # tn012 of the layer above, deferred (TN_AT = "next")
+                lane.begin()
+                lane.tn128(N, pending[0], 5 * H, 3, *pending[1:])
                 pending = None
             _call("gnm_tn128_bgrad", N, H, _ptr(UT), _ptr(Ud), _ptr(Td), Ud.stride(0), _ptr(s.stat_e), _ptr(bstat_e),
                   _ptr(prm.gamma_e), _ptr(idx["in_ptr"]), _ptr(idx["out_ptr"]), _ptr(gP),
@@ -1105,32 +1110,26 @@ def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tens
                       _ptr(s_j.stat_h), _ptr(sc.partials), C.byref(nblk_h), _ptr(ws), need_p, st)
             else:
                 _call("gnm_node_proj_bwd_nn", N, H, 5 * H, _ptr(gP), _ptr(prm.W5), _ptr(gh), _ptr(gh_in), _ptr(ws), need_p, st)
-            if side is not None and at_now:             # tn012(i) right away, beside node(i-1)'s [N,H] passes
-                side_begin()
-                tn128(N, gP, 5 * H, 3, s.h_in, g["W5"], g["b5"], sc3.partials, sc3.ws(need_t), need_t, stream=side)
-                held.extend((gP, s.h_in))
-            elif side is not None and i > 0:
+            if lane is not None and at_now:             # tn012(i) right away, beside node(i-1)'s [N,H] passes
+                lane.begin()
+                lane.tn128(N, gP, 5 * H, 3, s.h_in, g["W5"], g["b5"])
+            elif lane is not None and i > 0:
                 pending = (gP, s.h_in, g["W5"], g["b5"])
             else:       # no side stream (lean activations, per-op timing) or the last iteration: the same launch on this stream
-                tn128(N, gP, 5 * H, 3, s.h_in, g["W5"], g["b5"], sc.partials if nblk_h is None else sc3.partials,
-                      sc.ws(max(need_p, need_f, need_t)) if nblk_h is None else sc3.ws(need_t), need_t, tag="gnm_tn128[3]")
+                sw = sc if nblk_h is None else scratch(dev, "wgrad")    # (sc.partials holds layer i-1's BatchNorm_h sums)
+                tn128(N, gP, 5 * H, 3, s.h_in, g["W5"], g["b5"], sw.partials, sw.ws(need_t), need_t, tag="gnm_tn128[3]")
         else:
             src_cap = 0
             if pending is not None:
                 # the matrix-bound weight gradient of the layer above on the side stream, beside this layer's HBM-bound
                 # by-source pass (see TN_SIDE)
                 pgP, ph, pW, pb = pending
-                side_begin()
-                sc3 = scratch(dev, "tn")
+                lane.begin()
                 if current().TN_SPLIT and UT is not None:
-                    tn128(N, pgP[:, 3 * H:], 5 * H, 2, ph, pW[3 * H:], pb[3 * H:], sc3.partials, sc3.ws(need_t), need_t, stream=side)
+                    lane.tn128(N, pgP[:, 3 * H:], 5 * H, 2, ph, pW[3 * H:], pb[3 * H:])
                     pending2 = pending
                 else:
-                    ws3 = sc3.ws(need_p)
-                    _lib.check(lib.gnm_node_proj_bwd_tn(N, H, 5 * H, _ptr(pgP), _ptr(ph), _ptr(pW), _ptr(pb), _ptr(sc3.partials),
-                                                        _ptr(ws3), need_p, current().TN_SIDE_CAP, C.c_void_p(side.cuda_stream)),
-                               "gnm_node_proj_bwd_tn")
-                held.extend((pgP, ph))
+                    lane.node_proj_bwd_tn(N, H, *pending)
                 pending = None
                 src_cap = current().SRC_SIDE_CAP
             if UT is None:
@@ -1143,26 +1142,19 @@ def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tens
             split2 = UT is not None
             del Ud, Td, Q
             UT = None
-            if not (side is not None and at_now):
+            if not (lane is not None and at_now):
                 _call("gnm_node_proj_bwd_nn", N, H, 5 * H, _ptr(gP), _ptr(prm.W5), _ptr(gh), _ptr(gh_in), _ptr(ws), need_p, st)
             if pending2 is not None:        # the other three column groups of the layer above, behind this layer's nn
-                pgP, ph, pW, pb = pending2
-                side.wait_stream(main)
-                sc3 = scratch(dev, "tn")
-                tn128(N, pgP, 5 * H, 3, ph, pW, pb, sc3.partials, sc3.ws(need_t), need_t, stream=side)
+                lane.wait_for_main()
+                lane.tn128(N, pending2[0], 5 * H, 3, *pending2[1:])
                 pending2 = None
-            if side is not None and at_now:
-                side_begin()
-                sc3 = scratch(dev, "tn")
-                ws3 = sc3.ws(need_p)
-                _lib.check(lib.gnm_node_proj_bwd_tn(N, H, 5 * H, _ptr(gP), _ptr(s.h_in), _ptr(g["W5"]), _ptr(g["b5"]), _ptr(sc3.partials),
-                                                    _ptr(ws3), need_p, current().TN_SIDE_CAP, C.c_void_p(side.cuda_stream)),
-                           "gnm_node_proj_bwd_tn")
-                held.extend((gP, s.h_in))
+            if lane is not None and at_now:
+                lane.begin()
+                lane.node_proj_bwd_tn(N, H, gP, s.h_in, g["W5"], g["b5"])
                 _call("gnm_node_proj_bwd_nn", N, H, 5 * H, _ptr(gP), _ptr(prm.W5), _ptr(gh), _ptr(gh_in), _ptr(ws), need_p, st)
-            elif side is not None and i > 0:
+            elif lane is not None and i > 0:
                 pending = (gP, s.h_in, g["W5"], g["b5"])
-            elif side is None and i > 0 and current().TN_SPLIT and split2:
+            elif lane is None and i > 0 and current().TN_SPLIT and split2:
                 # no side stream (lean activations, per-op timing): the same two launches the deferred path issues, back to back --
                 # the row partition of a launch depends on its column-group count, and the two modes must stay bit-identical
                 ws_t = sc.ws(max(need_p, need_f, need_t))
@@ -1179,9 +1171,6 @@ def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tens
             _call("gnm_edge_bwd_fused", E, H, _ptr(ge), _ptr(ge), _ptr(s.t), _ptr(s.e_in), _ptr(s.stat_e), _ptr(bstat_e),
                   _ptr(prm.gamma_e), _ptr(prm.W3), _ptr(g["W3"]), _ptr(g["b3"]), _ptr(sc.partials), _ptr(ws), need_f, st)
             saved[0] = None
-            if side is not None:
-                main.wait_stream(side)
-                held.clear()
             break
         j = i - 1
         prm_j, s_j = ensure(j)
@@ -1220,17 +1209,18 @@ def ln_chain_eligible(H: int, batch_norm: bool) -> bool:
 
 
 def layers_backward_chained_ln(idx, N: int, E: int, H: int, P: Dict[str, torch.Tensor], L: int, saved: List[LayerSaved], gh, ge,
-                               outs: List[Optional[Dict[str, torch.Tensor]]], plan: dict, lnw: int):
+                               outs: List[Optional[Dict[str, torch.Tensor]]], plan: dict, lnw: int, lane: Optional[SideLane] = None):
     """Backward of an L-layer LayerNorm stack (batch_norm=False), chained like layers_backward_chained.  LayerNorm has no global
     statistics, so the schedule is shorter than BatchNorm's -- no finalisation between a layer's passes, no conversion of raw sums:
         node(L-1), sweep(L-1) [+ fix];   then for i = L-1 .. 0:   nn(i), tn(i) [side stream],
                                               i > 0:  node(i-1), CHAIN[fused(i) with gt(i) given + sweep(i-1)] [+ fix(i-1)]
                                               i = 0:  fused(0) with gt(0) given
     The sweep of layer i writes gt(i) once; the chained kernel of the next iteration reads it back as layer i's given gt (6 [E,H]
-    streams per layer where the layer-by-layer schedule moves 9).  Returns (gh_in of layer 0, ge_in of layer 0, [grads dict per layer])."""
+    streams per layer where the layer-by-layer schedule moves 9).  Returns (gh_in of layer 0, ge_in of layer 0, [grads dict per layer]).
+    With `lane` tn(i) runs on its side stream; the caller drains it."""
     lib = _lib.load()
     dev = gh.device
-    sc, sc2 = scratch(dev), scratch(dev, "side")
+    sc, sc2 = scratch(dev), scratch(dev, "chain")
     st = _stream()
     f32 = dict(dtype=torch.float32, device=dev)
     grads: List[Dict[str, torch.Tensor]] = [dict() for _ in range(L)]
@@ -1279,7 +1269,6 @@ def layers_backward_chained_ln(idx, N: int, E: int, H: int, P: Dict[str, torch.T
           _ptr(sc.partials), _ptr(plan["sinfo"]), plan["nodes_per_block"], C.byref(nblk), _ptr(ws), need_f, st)
     fix_and_finalize(i, s, gt, Q, gP, nblk)
     del Q
-    use_side = current().TN_SIDE and _prof is None and current().ACTIVATIONS != "lean"
     while True:
         prm, s = prms[i], saved[i]
         g = grads[i]
@@ -1287,13 +1276,9 @@ def layers_backward_chained_ln(idx, N: int, E: int, H: int, P: Dict[str, torch.T
         gh_in = torch.empty(N, H, **f32)
         ws = sc.ws(max(need_f, need_p))
         _call("gnm_node_proj_bwd_nn", N, H, 5 * H, _ptr(gP), _ptr(prm.W5), _ptr(gh), _ptr(gh_in), _ptr(ws), need_p, st)
-        if use_side:
-            side = side_begin(dev)
-            sc3 = scratch(dev, "tn")
-            ws3 = sc3.ws(need_p)
-            _lib.check(lib.gnm_node_proj_bwd_tn(N, H, 5 * H, _ptr(gP), _ptr(s.h_in), _ptr(g["W5"]), _ptr(g["b5"]), _ptr(sc3.partials),
-                                                _ptr(ws3), need_p, current().TN_SIDE_CAP, C.c_void_p(side.cuda_stream)), "gnm_node_proj_bwd_tn")
-            _side_held[torch.device(dev)].extend((gP, s.h_in, g["W5"], g["b5"]))
+        if lane is not None:
+            lane.begin()
+            lane.node_proj_bwd_tn(N, H, gP, s.h_in, g["W5"], g["b5"])
         else:
             _call("gnm_node_proj_bwd_tn", N, H, 5 * H, _ptr(gP), _ptr(s.h_in), _ptr(g["W5"]), _ptr(g["b5"]), _ptr(sc.partials), _ptr(ws),
                   need_p, 0, st)
@@ -1304,7 +1289,6 @@ def layers_backward_chained_ln(idx, N: int, E: int, H: int, P: Dict[str, torch.T
             _call("gnm_edge_bwd_fused_gt", E, H, _ptr(ge), _ptr(ge), _ptr(gt), _ptr(s.e_in), _ptr(prm.W3), _ptr(g["W3"]), _ptr(g["b3"]),
                   _ptr(sc.partials), _ptr(ws), need_f, st)
             saved[0] = None
-            side_drain(dev)
             break
         j = i - 1
         prm_j, s_j = ensure(j)
@@ -1547,7 +1531,8 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
     gradients straight into those tensors and the same tensors are returned.  inputs=True: returns (G, g_e_raw, g_pe)
     instead, the gradients of model_forward's inputs -- e_raw [E,edge_features] in the caller's edge-id order, pe
     [N,nb_pos_enc+2] in the caller's node numbering (the encoders' input gradients; inputs=False launches exactly what
-    it launched before the option existed)."""
+    it launched before the option existed).  One backward at a time per device: the main stream's scratch (`scratch`) is
+    shared, so concurrent backward passes on one device are not supported."""
     dev = ms.pe.device
     _same_matmul_mode(ms)
     idx = graph.index(dev)
@@ -1564,30 +1549,35 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
     G["predictor.W2.weight"], G["predictor.W2.bias"] = gp["W2"], gp["b2"]
     ms.pred = None
     louts = [grad_targets(out, i) if out else None for i in range(num_layers)]
-    chained = None
     # layer-by-layer backward on the two-sided sweep (the chained schedule's top-layer kernel for every layer): H = 256, and H = 128
     # where the chained schedule does not apply (fp32-MFMA matmul mode, GNM_CHAIN=0)
     plan_w = graph.sweep_plan(dev) if (sweep_width(H, batch_norm) and current().TWO_SIDED and not chain_eligible(H, batch_norm)
                                        and hasattr(graph, "sweep_plan")) else None
-    if chain_eligible(H, batch_norm):
-        plan = graph.sweep_plan(dev) if current().TWO_SIDED and hasattr(graph, "sweep_plan") else None
-        gh, ge, chained = layers_backward_chained(idx, N, E, H, P, num_layers, ms.layers, gh, ge, louts, plan)
-    elif ln_chain_eligible(H, batch_norm) and plan_w is not None:
-        gh, ge, chained = layers_backward_chained_ln(idx, N, E, H, P, num_layers, ms.layers, gh, ge, louts, plan_w,
-                                                     H if ln_width is None else int(ln_width))
+    # the side stream for the weight gradients (TN_SIDE; not under per-op timing, not with lean activations)
+    lane = SideLane(dev) if (current().TN_SIDE and _prof is None and current().ACTIVATIONS != "lean") else None
+    try:
+        if chain_eligible(H, batch_norm):
+            plan = graph.sweep_plan(dev) if current().TWO_SIDED and hasattr(graph, "sweep_plan") else None
+            gh, ge, grads = layers_backward_chained(idx, N, E, H, P, num_layers, ms.layers, gh, ge, louts, plan, lane)
+        elif ln_chain_eligible(H, batch_norm) and plan_w is not None:
+            gh, ge, grads = layers_backward_chained_ln(idx, N, E, H, P, num_layers, ms.layers, gh, ge, louts, plan_w,
+                                                       H if ln_width is None else int(ln_width), lane)
+        else:
+            grads = [None] * num_layers
+            for i in reversed(range(num_layers)):
+                gh, ge, grads[i] = layer_backward(idx, N, E, H, layer_params(P, i), ms.layers[i], gh, ge, batch_norm, louts[i],
+                                                  plan=plan_w, ln_width=ln_width, lane=lane)
+                ms.layers[i] = None     # release this layer's activations
+    finally:
+        if lane is not None:
+            lane.drain()        # before anything reads a weight gradient, and on the way out of an error
     for i in reversed(range(num_layers)):
         p = f"gnn.convs.{i}."
-        lout = louts[i]
-        if chained is not None:
-            gl = chained[i]
-        else:
-            gh, ge, gl = layer_backward(idx, N, E, H, layer_params(P, i), ms.layers[i], gh, ge, batch_norm, lout, plan=plan_w,
-                                        ln_width=ln_width, defer_tn=True)
-            ms.layers[i] = None     # release this layer's activations
+        gl = grads[i]
         for j, k in enumerate(LIN5):
             G[p + k + ".weight"] = gl["W5"][j * H:(j + 1) * H]
             G[p + k + ".bias"] = gl["b5"][j * H:(j + 1) * H]
-        if out and lout is None:          # the caller's targets are not stacked: copy the two stacked results over
+        if out and louts[i] is None:      # the caller's targets are not stacked: copy the two stacked results over
             for j, k in enumerate(LIN5):
                 G[p + k + ".weight"] = out[p + k + ".weight"].copy_(G[p + k + ".weight"])
                 G[p + k + ".bias"] = out[p + k + ".bias"].copy_(G[p + k + ".bias"])
@@ -1597,8 +1587,6 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
         G[p + "B_3.weight"], G[p + "B_3.bias"] = gl["W3"], gl["b3"]
         G[p + "bn_e.weight"], G[p + "bn_e.bias"] = gl["gamma_e"], gl["beta_e"]
         G[p + "bn_h.weight"], G[p + "bn_h.bias"] = gl["gamma_h"], gl["beta_h"]
-    if chained is None:
-        side_drain(dev)             # the deferred weight-gradient launches of layer_backward(defer_tn=True)
     # encoders backward
     lib = _lib.load()
     G["linear_pe.weight"] = tgt("linear_pe.weight", P["linear_pe.weight"])

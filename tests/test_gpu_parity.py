@@ -1884,6 +1884,112 @@ def test_side_stream_schedule_and_per_call_caps_change_nothing_but_rounding():
             assert d <= 1e-5 * float(base[k].abs().max()) + 1e-9, (setting, k, d)
 
 
+@pytest.mark.parametrize("H,batch_norm", [(128, True), (256, True), (128, False)], ids=["chained_bn128", "layers_bn256", "chained_ln128"])
+def test_backward_that_raises_drains_the_side_lane_and_releases_its_tensors(H, batch_norm, monkeypatch):
+    """A backward pass that raises while side-stream weight-gradient launches are outstanding (engine.SideLane) leaves
+    nothing behind: once its references are gone, device memory is back where it was after a clean step, and the next
+    step's gradients are bit-identical to a clean step's.  The error is a host-side exception injected into engine._call
+    at the first main-stream launch after a side launch (the f32 matmul mode runs H = 256 without a side stream: there it is
+    injected at the layer's main-stream weight gradient)."""
+    import gc
+    import gnnome_assembly_amd as G
+    from gnnome_assembly_amd import _lib, engine, synth
+    dev = _dev()
+    L = 3
+    src, dst, n = synth.make_graph(2000, 3)
+    inp = synth.make_inputs(src, dst, n, 3)
+    model = G.GraphGatedGCNModel(1, 2, H, 16, L, 64, batch_norm, 16)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in synth.synth_state_dict(H, L, 3).items()})
+    model.to(dev)
+    g = G.AssemblyGraph(src, dst, n).to(dev)
+    e, pe, y = (torch.from_numpy(inp[k]).to(dev) for k in ("e", "pe", "y"))
+    crit = G.BCEWithLogitsLoss(float(inp["pos_weight"]))
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        crit(model(g, None, e, pe).squeeze(-1), y).backward()
+        grads = {k: p.grad.clone() for k, p in model.named_parameters()}
+        model.zero_grad(set_to_none=True)
+        torch.cuda.synchronize()
+        return grads
+
+    class Injected(RuntimeError):
+        pass
+
+    side_route = H == 128 or _lib.split_mode()
+    launched, raised = [], []
+    real_call = engine._call
+
+    def call(name, *a, **k):
+        if not raised and (launched or (not side_route and name == "gnm_gemm_tn_colsum")):
+            raised.append(name)
+            raise Injected(name)
+        return real_call(name, *a, **k)
+
+    def counted(name):
+        f = getattr(engine.SideLane, name)
+
+        def w(self, *a):
+            f(self, *a)
+            launched.append(name)
+        return w
+
+    with engine.options(TN_SIDE=True, ACTIVATIONS="saved"):
+        before = step()
+        mem = torch.cuda.memory_allocated()
+        with monkeypatch.context() as mp:
+            mp.setattr(engine, "_call", call)
+            for name in ("node_proj_bwd_tn", "tn128", "gemm_tn_colsum"):
+                mp.setattr(engine.SideLane, name, counted(name))
+            scores = model(g, None, e, pe)
+            try:
+                crit(scores.squeeze(-1), y).backward()
+            except Injected:
+                pass
+        assert raised, "the injected error was never raised"
+        assert bool(launched) == side_route, (launched, side_route)
+        del scores
+        gc.collect()
+        torch.cuda.synchronize()
+        assert model.gnn.convs[0].A_1.weight.grad is None
+        assert torch.cuda.memory_allocated() == mem, (torch.cuda.memory_allocated() - mem, launched, raised)
+        after = step()
+    for k in before:
+        assert torch.equal(before[k], after[k]), k
+
+
+def test_model_backward_into_separate_targets_matches_the_stacked_result():
+    """H = 256 with the side stream on: model_backward with an `out` dict of separate tensors (not back to back, so the
+    stacked W5 / b5 results are copied over) returns exactly what the call without `out` returns.  The copies read weight
+    gradients written on the side stream, so they must come after the lane is drained; a race would not show up reliably,
+    so this guards the ordering rather than proving it."""
+    import gnnome_assembly_amd as G
+    from gnnome_assembly_amd import engine, synth
+    dev = _dev()
+    H, L = 256, 2
+    src, dst, n = synth.make_graph(2000, 5)
+    inp = synth.make_inputs(src, dst, n, 5)
+    P = {k: v.to(dev) for k, v in sd_to_torch(synth.synth_state_dict(H, L, 5)).items()}
+    g = G.AssemblyGraph(src, dst, n).to(dev)
+    e, pe, y = (torch.from_numpy(inp[k]).to(dev) for k in ("e", "pe", "y"))
+
+    def backward(out):
+        scores, ms = engine.model_forward(g, e, pe, P, L, True)
+        _, gs = engine.bce_with_logits(scores, y, float(inp["pos_weight"]))
+        return engine.model_backward(g, P, L, ms, gs, out=out)
+
+    with engine.options(TN_SIDE=True, ACTIVATIONS="saved"):
+        want = backward(None)
+        out = {k: torch.full_like(v, float("nan")) for k, v in P.items()}        # one allocation each: never back to back
+        assert engine.grad_targets(out, 0) is None
+        got = backward(out)
+    torch.cuda.synchronize()
+    assert set(got) == set(want)
+    for k in want:
+        assert got[k].data_ptr() == out[k].data_ptr(), k
+        assert torch.equal(got[k], want[k]), k
+
+
 @pytest.mark.mode_independent
 @pytest.mark.parametrize("prog", ["host_layer", "host_step"])
 def test_cxx_host_through_the_c_abi(tmp_path, prog):
