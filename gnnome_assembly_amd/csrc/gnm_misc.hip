@@ -175,8 +175,11 @@ __global__ __launch_bounds__(kBlock) void bce_fwd_bwd_k(int64_t E, const float* 
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < E; i += (int64_t)gridDim.x * kBlock) {
     const float xi = x[i], yi = y[i];
     const float p = sigmoid_ieee_(xi);
+    // 1 - p: for x > 0 as e^-x / (1 + e^-x), where 1.f - p cancels (it is 0 from x ~ 17 on, where 1 - p is ~4e-8)
+    const float em = expf(-fabsf(xi));
+    const float q = xi > 0.f ? em / (1.f + em) : 1.f - p;
     acc += (double)(pw * yi * softplusf_(-xi) + (1.f - yi) * softplusf_(xi));
-    gscore[i] = (-pw * yi * (1.f - p) + (1.f - yi) * p) * inv_e;
+    gscore[i] = (-pw * yi * q + (1.f - yi) * p) * inv_e;
   }
   red[threadIdx.x] = acc;
   __syncthreads();

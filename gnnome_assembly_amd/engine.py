@@ -1320,12 +1320,50 @@ class PredSaved:
     hid: torch.Tensor = None     # pre-activation [E,HS]; overwritten by its gradient in backward
     W1sd: torch.Tensor = None
     opts: "Options" = None
+    pieces: list = None          # hidden_edge_scores run as padded pieces: [((c0, w, wp), PredSaved of the piece)] (pred_pieces)
+
+
+PRED_WIDTHS = (32, 64, 128, 256)      # the hidden_edge_scores the predictor's row kernels are built for (GNM_DISPATCH_W)
+
+
+def pred_pieces(HS: int):
+    """[(c0, w, wp)]: the column pieces predictor_forward runs hidden_edge_scores = HS as.  A built width runs as itself; any
+    other HS as pieces of at most 256 columns, each zero-padded to the next built width (zero rows of W1 and b1, zero columns
+    of W2: relu(0) * 0 adds nothing to the score, and the padded rows' gradients are dropped).  nn.Linear takes any size
+    (score_predictor.py:8-9), and so does this."""
+    if HS in PRED_WIDTHS:
+        return [(0, HS, HS)]
+    out = []
+    for c0 in range(0, HS, PRED_WIDTHS[-1]):
+        w = min(PRED_WIDTHS[-1], HS - c0)
+        out.append((c0, w, next(k for k in PRED_WIDTHS if k >= w)))
+    return out
+
+
+def _pred_piece(t, c0, w, wp, cols: bool = False):
+    """Rows c0 .. c0+w of W1 [HS,3H] / b1 [HS], or (cols) columns of W2 [1,HS], zero-padded to wp."""
+    if cols:
+        return torch.nn.functional.pad(t[:, c0:c0 + w], (0, wp - w))
+    return torch.nn.functional.pad(t[c0:c0 + w], (0, 0, 0, wp - w) if t.dim() == 2 else (0, wp - w))
 
 
 @on_device_of(lambda idx, N, E, H, W1, b1, W2, b2, x, *a, **k: x)
 @_scoped()
 def predictor_forward(idx, N, E, H, W1, b1, W2, b2, x, e, save: bool):
-    """scores (caller edge-id order, [E,1]) from internal-order x [N,H], e [E,H]."""
+    """scores (caller edge-id order, [E,1]) from internal-order x [N,H], e [E,H].  Any hidden_edge_scores: see pred_pieces."""
+    pieces = pred_pieces(W1.shape[0])
+    if len(pieces) == 1 and pieces[0][1] == pieces[0][2]:
+        return _predictor_forward(idx, N, E, H, W1, b1, W2, b2, x, e, save)
+    scores, saved = None, []
+    for j, (c0, w, wp) in enumerate(pieces):
+        s_j, ps = _predictor_forward(idx, N, E, H, _pred_piece(W1, c0, w, wp), _pred_piece(b1, c0, w, wp),
+                                     _pred_piece(W2, c0, w, wp, cols=True), b2 if j == 0 else torch.zeros_like(b2), x, e, save)
+        scores = s_j if scores is None else scores.add_(s_j)
+        saved.append(ps)
+    return scores, (PredSaved(x=x, e=e, opts=current(), pieces=list(zip(pieces, saved))) if save else None)
+
+
+def _predictor_forward(idx, N, E, H, W1, b1, W2, b2, x, e, save: bool):
     lib = _lib.load()
     dev = x.device
     HS = W1.shape[0]
@@ -1356,6 +1394,32 @@ def predictor_forward(idx, N, E, H, W1, b1, W2, b2, x, e, save: bool):
 @_scoped(6)
 def predictor_backward(idx, N, E, H, W1, W2, s: PredSaved, gscores, out: Optional[Dict[str, torch.Tensor]] = None):
     """Returns (gx [N,H], ge [E,H] fresh buffer, grads dict W1,b1,W2,b2); `out` as in layer_backward."""
+    if s.pieces is None:
+        return _predictor_backward(idx, N, E, H, W1, W2, s, gscores, out)
+    # the pieces of predictor_forward: each backward needs only gscores; the padded rows' gradients are dropped
+    out = out or {}
+    HS = W1.shape[0]
+    f32 = dict(dtype=torch.float32, device=gscores.device)
+    g = {"W1": out["W1"] if "W1" in out else torch.empty(HS, 3 * H, **f32),
+         "b1": out["b1"] if "b1" in out else torch.empty(HS, **f32),
+         "W2": out["W2"] if "W2" in out else torch.empty(1, HS, **f32)}
+    gx = ge = None
+    for (c0, w, wp), ps in s.pieces:
+        gx_j, ge_j, g_j = _predictor_backward(idx, N, E, H, _pred_piece(W1, c0, w, wp), _pred_piece(W2, c0, w, wp, cols=True), ps,
+                                              gscores)
+        g["W1"][c0:c0 + w] = g_j["W1"][:w]
+        g["b1"][c0:c0 + w] = g_j["b1"][:w]
+        g["W2"][:, c0:c0 + w] = g_j["W2"][:, :w]
+        if gx is None:
+            gx, ge = gx_j, ge_j
+            g["b2"] = out["b2"].copy_(g_j["b2"]) if "b2" in out else g_j["b2"]
+        else:
+            gx.add_(gx_j)
+            ge.add_(ge_j)
+    return gx, ge, g
+
+
+def _predictor_backward(idx, N, E, H, W1, W2, s: PredSaved, gscores, out: Optional[Dict[str, torch.Tensor]] = None):
     out = out or {}
     lib = _lib.load()
     dev = s.x.device

@@ -88,8 +88,12 @@ def device_masks(ms, sd, e_raw_np, idx):
         um, wm = branches(s)
         u.append(um[inv])                             # internal order -> edge-id order
         w.append(wm if nrank is None else wm[nrank])
-    hid = (ms.pred.hid > 0).cpu()[inv]
-    # encoder: ap = fmaf(w1a, x0, fmaf(w1b, x1, b))  (gnm_encoder.hip) -- inner fma rounded to fp32
+    pred = ms.pred          # hidden_edge_scores run as zero-padded pieces (engine.pred_pieces): the real columns of each
+    hid = torch.cat([ps.hid[:, :cols] for (_, cols, _), ps in pred.pieces], 1) if pred.pieces else pred.hid
+    hid = (hid > 0).cpu()[inv]
+    if ms.a1 is not None:   # the generic encoder keeps relu(a1) (one fp32 GEMM output): its sign is the branch taken
+        return {"u": u, "w": w, "hid": hid, "a1": (ms.a1 > 0).cpu()[inv]}
+    # fused encoder: ap = fmaf(w1a, x0, fmaf(w1b, x1, b))  (gnm_encoder.hip) -- inner fma rounded to fp32
     W1, b1 = sd["linear1_edge.weight"].astype(np.float64), sd["linear1_edge.bias"].astype(np.float64)
     x = e_raw_np.astype(np.float64)
     inner = (x[:, 1:2] * W1[None, :, 1] + b1[None, :]).astype(np.float32).astype(np.float64)

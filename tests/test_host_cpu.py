@@ -383,3 +383,34 @@ def test_a_backward_in_another_matmul_mode_than_its_forward_is_refused():
         engine._same_matmul_mode(s)
     engine._same_matmul_mode(engine.LayerSaved(matmul=_lib.get_matmul_mode()))
     engine._same_matmul_mode(engine.LayerSaved())          # no record (a state built by hand): unchecked
+
+
+def test_any_hidden_edge_scores_runs_as_zero_padded_pieces():
+    """score_predictor.py:8-9: nn.Linear(3H, hidden_edge_scores) takes any size.  A size the predictor's row kernels are not
+    built for (GNM_DISPATCH_W: 32, 64, 128, 256) runs as pieces of at most 256 columns, each zero-padded to the next built
+    width (engine.pred_pieces; parity on the GPU tier: test_gpu_heads.py).  The pieces tile [0, HS) and, with b2 added by the
+    first piece only, their scores add up to the unpadded predictor's in exact arithmetic."""
+    import gnnome_assembly_amd as G
+    from gnnome_assembly_amd import engine
+    assert engine.pred_pieces(64) == [(0, 64, 64)] and engine.pred_pieces(256) == [(0, 256, 256)]
+    assert engine.pred_pieces(48) == [(0, 48, 64)] and engine.pred_pieces(1) == [(0, 1, 32)]
+    assert engine.pred_pieces(300) == [(0, 256, 256), (256, 44, 64)]
+    for HS in (1, 31, 33, 48, 65, 100, 200, 255, 257, 300, 512, 513, 777):
+        pieces = engine.pred_pieces(HS)
+        assert [c0 for c0, _, _ in pieces] == list(range(0, HS, 256)) and sum(w for _, w, _ in pieces) == HS
+        assert all(w <= wp and wp in engine.PRED_WIDTHS for _, w, wp in pieces)
+        g = torch.Generator().manual_seed(HS)
+        H, E = 8, 50
+        data = torch.randn(E, 3 * H, generator=g, dtype=torch.float64)
+        W1, b1 = torch.randn(HS, 3 * H, generator=g, dtype=torch.float64), torch.randn(HS, generator=g, dtype=torch.float64)
+        W2, b2 = torch.randn(1, HS, generator=g, dtype=torch.float64), torch.randn(1, generator=g, dtype=torch.float64)
+        want = torch.relu(data @ W1.t() + b1) @ W2.t() + b2
+        got = 0
+        for j, (c0, w, wp) in enumerate(pieces):
+            W1p, b1p, W2p = engine._pred_piece(W1, c0, w, wp), engine._pred_piece(b1, c0, w, wp), engine._pred_piece(W2, c0, w, wp, cols=True)
+            assert W1p.shape == (wp, 3 * H) and b1p.shape == (wp,) and W2p.shape == (1, wp)
+            assert not W1p[w:].any() and not b1p[w:].any() and not W2p[:, w:].any()
+            got = got + torch.relu(data @ W1p.t() + b1p) @ W2p.t() + (b2 if j == 0 else 0)
+        assert torch.allclose(got, want, rtol=1e-12, atol=1e-12)
+    m = G.GraphGatedGCNModel(1, 2, 32, 16, 1, 300, False, 16)
+    assert m.predictor.W1.weight.shape == (300, 96) and m.predictor.W2.weight.shape == (1, 300)
