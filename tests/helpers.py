@@ -333,3 +333,93 @@ def layer_variant_case(name):
         sd[k + ".bias"] = f32(rng.uniform(-0.3, 0.3, size=cout))
     case["sd"] = sd
     return case
+
+
+# -----------------------------------------------------------------------------------------
+# replicated graphs (test_replica_cpu.py checks the identity, test_gpu_scale_replicas.py runs it past the 32-bit limits):
+# G_K = K disjoint copies of a small graph G0, every copy with G0's features and labels.  Exactly, in real arithmetic: the
+# BatchNorm statistics (mean, biased variance) over edges and nodes are G0's, so every copy's logits are G0's, the loss (a mean)
+# and every parameter gradient are G0's, and d loss / d e, d pe of each copy are G0's divided by K.  One fp64 oracle run on G0
+# then checks every row of a graph far too large for the oracle itself.
+# -----------------------------------------------------------------------------------------
+def replica_base_graph(reads=4000, seed=11, hub_in=300):
+    """G0: a synth.make_graph assembly graph plus the edge cases a replica run should carry -- one destination with `hub_in`
+    in-edges (its run spans many 16-row sweep tiles), one self loop, one duplicated edge, one isolated node (the last id, so
+    N0 is odd) and an edge dropped if need be so that E0 is odd; edge ids shuffled.  Returns (src, dst, n) int32 / int."""
+    src, dst, n = synth.make_graph(reads, seed=seed)
+    rng = np.random.default_rng(seed + 101)
+    hub = n // 3
+    hs = rng.choice(np.setdiff1d(np.arange(n), [hub]), size=hub_in, replace=False)
+    src, dst = np.concatenate([src, hs]), np.concatenate([dst, np.full(hub_in, hub)])
+    if src.size % 2 == 0:                       # two more follow: make E0 odd
+        src, dst = src[1:], dst[1:]
+    src = np.concatenate([src, [7, src[0]]])    # a self loop, a duplicated edge
+    dst = np.concatenate([dst, [7, dst[0]]])
+    p = rng.permutation(src.size)
+    n += 1                                                                              # the isolated node
+    assert src.size % 2 == 1 and n % 2 == 1
+    return src[p].astype(np.int32), dst[p].astype(np.int32), n
+
+
+def replicate(src, dst, n, K, shuffle_seed=None):
+    """G_K: K disjoint copies of (src, dst, n), copy-major (copy c holds edges c*E0 .. and nodes c*N0 ..), or -- with
+    `shuffle_seed` -- under one random permutation of ALL node ids and one of ALL edge ids.  Returns dict(src, dst [K*E0] int32,
+    n = K*N0, K, E0, N0, ecopy / epos [K*E0]: the (copy, position in G0) of each edge, ncopy / npos [K*N0]: same for each node).
+    Tile a G0 edge array with a[epos], a node array with a[npos]."""
+    src, dst = np.asarray(src, np.int64), np.asarray(dst, np.int64)
+    E0, N0 = src.size, int(n)
+    assert K * N0 < 2 ** 31 and K * E0 < 2 ** 31
+    base = (np.arange(K, dtype=np.int64) * N0)[:, None]
+    s, d = (src[None, :] + base).reshape(-1), (dst[None, :] + base).reshape(-1)
+    ecopy, epos = np.repeat(np.arange(K, dtype=np.int32), E0), np.tile(np.arange(E0, dtype=np.int32), K)
+    ncopy, npos = np.repeat(np.arange(K, dtype=np.int32), N0), np.tile(np.arange(N0, dtype=np.int32), K)
+    if shuffle_seed is not None:
+        rng = np.random.default_rng(shuffle_seed)
+        pn = rng.permutation(K * N0)                  # old node id -> new
+        pe = rng.permutation(K * E0)                  # new edge id -> old
+        s, d = pn[s[pe]], pn[d[pe]]
+        ecopy, epos = ecopy[pe], epos[pe]
+        nc, npp = np.empty_like(ncopy), np.empty_like(npos)
+        nc[pn], npp[pn] = ncopy, npos
+        ncopy, npos = nc, npp
+    return dict(src=s.astype(np.int32), dst=d.astype(np.int32), n=K * N0, K=K, E0=E0, N0=N0,
+                ecopy=ecopy, epos=epos, ncopy=ncopy, npos=npos)
+
+
+def per_copy(a, copy, pos, K, size0):
+    """Rows of a G_K array (edge or node order of the replicated graph) as [K, size0, ...] fp64: out[copy[i], pos[i]] = a[i]."""
+    a = np.asarray(a)
+    out = np.empty((K, size0) + a.shape[1:], dtype=np.float64)
+    out[copy, pos] = a
+    return out
+
+
+def copy_rel_l2(got, want):
+    """Per-copy rel-L2 of got [K, size0, ...] against one copy's reference want [size0, ...]: [K] fp64."""
+    g = np.asarray(got, np.float64).reshape(got.shape[0], -1)
+    w = np.asarray(want, np.float64).reshape(1, -1)
+    return np.linalg.norm(g - w, axis=1) / max(float(np.linalg.norm(w)), 1e-30)
+
+
+def assert_copies_parity(got, want, what, rtol=RTOL, atol=ATOL, l2=1e-4):
+    """assert_parity of EVERY copy of got [K, size0, ...] against want [size0, ...] (a whole-tensor norm would dilute a
+    corrupted tail).  Returns (worst rel-L2, its copy)."""
+    got = np.asarray(got, np.float64)
+    want = np.asarray(want, np.float64)
+    assert got.shape[1:] == want.shape, f"{what}: shape {got.shape} vs {want.shape}"
+    assert np.all(np.isfinite(got)), f"{what}: non-finite values in copies {np.unique(np.nonzero(~np.isfinite(got))[0])[:8]}"
+    r = copy_rel_l2(got, want)
+    g, w = got.reshape(got.shape[0], -1), want.reshape(1, -1)
+    bad = (np.abs(g - w) > atol + rtol * np.abs(w)).sum(1)
+    fail = np.nonzero((r > l2) | (bad > 0))[0]
+    worst = int(np.argmax(r))
+    assert fail.size == 0, (f"{what}: {fail.size} of {got.shape[0]} copies differ from the reference, first {fail[:8].tolist()} "
+                            f"(rel_l2 {r[fail[:8]].tolist()}, violations {bad[fail[:8]].tolist()}); worst copy {worst} rel_l2 "
+                            f"{r[worst]:.3e}")
+    return float(r[worst]), worst
+
+
+def zscore(a):
+    """utils.preprocess_graph's z-score (torch .std(): unbiased) in fp64."""
+    a = np.asarray(a, np.float64)
+    return (a - a.mean()) / a.std(ddof=1)
