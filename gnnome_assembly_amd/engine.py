@@ -13,6 +13,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import functools
+import operator
 import os
 import threading
 from dataclasses import dataclass, field
@@ -35,6 +36,8 @@ LIN5 = ("A_1", "A_2", "A_3", "B_1", "B_2")
 #            (node projections, then the fused edge-t kernel) from h_in / e_in, which ARE kept (e_in is the previous
 #            layer's e_out).  Bit-identical results (same kernels, same inputs), about 7 GiB less per layer at the
 #            size above, for two extra kernels per layer (+3.3 ms of 25).
+# Independent of the mode: model_forward(checkpoint=k) keeps of the layer stack only the inputs of every k-th layer and model_backward
+# recomputes one k-layer segment at a time (checkpoint_segments; a property of the call kept in ModelSaved, not an Options switch).
 _D_ACTIVATIONS = os.environ.get("GNM_ACTIVATIONS", "saved").strip().lower()
 
 
@@ -1003,7 +1006,7 @@ def chain_eligible(H: int, batch_norm: bool) -> bool:
 
 def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tensor], L: int, saved: List[LayerSaved],
                             gh, ge, outs: List[Optional[Dict[str, torch.Tensor]]], plan: Optional[dict] = None,
-                            lane: Optional[SideLane] = None):
+                            lane: Optional[SideLane] = None, first: int = 0):
     """Backward of the L-layer stack (layers L-1 .. 0), same arithmetic as L x layer_backward, other schedule:
         node(L-1), dst(L-1);   then for i = L-1 .. 0:   finalize_e(i), src(i), proj(i),
                                                          i > 0:  node(i-1), CHAIN[fused(i) + dst(i-1)]
@@ -1012,7 +1015,9 @@ def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tens
     saved[i] is released as soon as layer i is done.  outs[i]: write-into targets as in layer_backward (or None).
     With `plan` (graph.sweep_plan) the chained kernel is the two-sided sweep: src(i) for i < L-1 becomes
     fix(i) [right after CHAIN(i+1, i)] + bgrad(i) [after finalize_e(i)].  With `lane` the node-projection weight gradients run on
-    its side stream (TN_AT, TN_SPLIT say when); the caller drains it."""
+    its side stream (TN_AT, TN_SPLIT say when); the caller drains it.
+    first: the stack is the model's layers first .. first+L-1 (a checkpoint segment: `saved` and `outs` hold those L layers, the
+    parameters are read at the offset); its top layer is treated like a model's top layer, its bottom layer like layer 0."""
     lib = _lib.load()
     dev = gh.device
     sc, sc2 = scratch(dev), scratch(dev, "chain")     # sc2: the chained kernel's second partials buffer
@@ -1027,7 +1032,7 @@ def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tens
 
     def ensure(i):
         if prms[i] is None:
-            prms[i] = layer_params(P, i)
+            prms[i] = layer_params(P, first + i)
         s = saved[i]
         if s.P is None or s.t is None:      # "lean" activations
             s.P, s.t = _proj_and_t(idx, N, E, H, prms[i], s.h_in, s.e_in, C.c_int(0))
@@ -1209,7 +1214,8 @@ def ln_chain_eligible(H: int, batch_norm: bool) -> bool:
 
 
 def layers_backward_chained_ln(idx, N: int, E: int, H: int, P: Dict[str, torch.Tensor], L: int, saved: List[LayerSaved], gh, ge,
-                               outs: List[Optional[Dict[str, torch.Tensor]]], plan: dict, lnw: int, lane: Optional[SideLane] = None):
+                               outs: List[Optional[Dict[str, torch.Tensor]]], plan: dict, lnw: int, lane: Optional[SideLane] = None,
+                               first: int = 0):
     """Backward of an L-layer LayerNorm stack (batch_norm=False), chained like layers_backward_chained.  LayerNorm has no global
     statistics, so the schedule is shorter than BatchNorm's -- no finalisation between a layer's passes, no conversion of raw sums:
         node(L-1), sweep(L-1) [+ fix];   then for i = L-1 .. 0:   nn(i), tn(i) [side stream],
@@ -1217,7 +1223,7 @@ def layers_backward_chained_ln(idx, N: int, E: int, H: int, P: Dict[str, torch.T
                                               i = 0:  fused(0) with gt(0) given
     The sweep of layer i writes gt(i) once; the chained kernel of the next iteration reads it back as layer i's given gt (6 [E,H]
     streams per layer where the layer-by-layer schedule moves 9).  Returns (gh_in of layer 0, ge_in of layer 0, [grads dict per layer]).
-    With `lane` tn(i) runs on its side stream; the caller drains it."""
+    With `lane` tn(i) runs on its side stream; the caller drains it.  first: as in layers_backward_chained."""
     lib = _lib.load()
     dev = gh.device
     sc, sc2 = scratch(dev), scratch(dev, "chain")
@@ -1234,7 +1240,7 @@ def layers_backward_chained_ln(idx, N: int, E: int, H: int, P: Dict[str, torch.T
 
     def ensure(i):
         if prms[i] is None:
-            prms[i] = layer_params(P, i)
+            prms[i] = layer_params(P, first + i)
         s = saved[i]
         _same_matmul_mode(s)
         if s.P is None or s.t is None:      # "lean" activations
@@ -1500,6 +1506,27 @@ class ModelSaved:
     pred: PredSaved = None
     opts: "Options" = None
     matmul: str = None
+    checkpoint: int = 0          # k > 0: `layers` stays empty, the backward recomputes the stack in segments of k layers ...
+    boundaries: list = field(default_factory=list)      # ... from the (h_in, e_in) of every segment's first layer, kept here
+
+
+def _checkpoint_arg(k) -> int:
+    """model_forward's `checkpoint` argument as an int >= 0, or GnmError."""
+    try:
+        k = operator.index(k)       # int, numpy integer, ...; not 1.5, not "4"
+    except TypeError:
+        k = -1
+    if k < 0:
+        raise _lib.GnmError("checkpoint: expected an integer >= 0 (0: keep every layer's activations; k: keep the inputs of "
+                            "every k-th layer and recompute the rest in the backward)")
+    return k
+
+
+def checkpoint_segments(num_layers: int, k) -> List[tuple]:
+    """The layer segments [(first, last_exclusive), ...] of activation checkpointing with segments of k layers: the last one may
+    be shorter, k >= num_layers is one segment, k = 0 (no checkpointing) is no segment."""
+    k = _checkpoint_arg(k)
+    return [(a, min(a + k, num_layers)) for a in range(0, num_layers, k)] if k else []
 
 
 def stacked(ts):
@@ -1530,9 +1557,13 @@ def layer_params(P: Dict[str, torch.Tensor], i: int) -> LayerParams:
 @on_device_of(lambda graph, e_raw, pe, *a, **k: pe)
 @_scoped()
 def model_forward(graph, e_raw, pe, P: Dict[str, torch.Tensor], num_layers: int, save: bool, batch_norm: bool = True,
-                  ln_width: Optional[int] = None):
+                  ln_width: Optional[int] = None, checkpoint: int = 0):
     """GraphGatedGCNModel.forward.  e_raw [E,edge_features] in edge-id order, pe [N,nb_pos_enc+2].
-    Returns (scores [E,1] in edge-id order, ModelSaved or None).  ln_width: see layer_forward."""
+    Returns (scores [E,1] in edge-id order, ModelSaved or None).  ln_width: see layer_forward.
+    checkpoint = k > 0 (with save): layer-segment activation checkpointing -- of the layer stack only the (h_in, e_in) entering
+    every k-th layer is kept; model_backward re-runs one segment's forward (same kernels, same inputs: the same bits) right
+    before that segment's backward.  The scores are those of checkpoint = 0; without `save` it has no effect."""
+    checkpoint = _checkpoint_arg(checkpoint)
     lib = _lib.load()
     dev = pe.device
     _chk_dev(e_raw, pe)
@@ -1561,10 +1592,18 @@ def model_forward(graph, e_raw, pe, P: Dict[str, torch.Tensor], num_layers: int,
         gemm(NT, a1, P["linear2_edge.weight"], e, bias=P["linear2_edge.bias"])
     ms = ModelSaved(pe=pe, e_int=e_int, a1=a1, e_raw=e_raw, opts=current(), matmul=_lib.get_matmul_mode()) if save else None
     plan2 = graph.sweep_plan(dev, GATE2_WG) if (current().TWO_SIDED_FWD and sweep_width(H, batch_norm) and hasattr(graph, "sweep_plan")) else None
-    for i in range(num_layers):
-        h, e, ls = layer_forward(idx, N, E, H, layer_params(P, i), h, e, save, batch_norm, plan=plan2, ln_width=ln_width)
-        if save:
-            ms.layers.append(ls)
+    if save and checkpoint:
+        ms.checkpoint = checkpoint
+        firsts = {a for a, _ in checkpoint_segments(num_layers, checkpoint)}
+        for i in range(num_layers):
+            if i in firsts:
+                ms.boundaries.append((h, e))
+            h, e, _ = layer_forward(idx, N, E, H, layer_params(P, i), h, e, False, batch_norm, plan=plan2, ln_width=ln_width)
+    else:
+        for i in range(num_layers):
+            h, e, ls = layer_forward(idx, N, E, H, layer_params(P, i), h, e, save, batch_norm, plan=plan2, ln_width=ln_width)
+            if save:
+                ms.layers.append(ls)
     scores, ps = predictor_forward(idx, N, E, H, P["predictor.W1.weight"], P["predictor.W1.bias"],
                                    P["predictor.W2.weight"], P["predictor.W2.bias"], h, e, save)
     if save:
@@ -1595,7 +1634,9 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
     gradients straight into those tensors and the same tensors are returned.  inputs=True: returns (G, g_e_raw, g_pe)
     instead, the gradients of model_forward's inputs -- e_raw [E,edge_features] in the caller's edge-id order, pe
     [N,nb_pos_enc+2] in the caller's node numbering (the encoders' input gradients; inputs=False launches exactly what
-    it launched before the option existed).  One backward at a time per device: the main stream's scratch (`scratch`) is
+    it launched before the option existed).  A checkpointed forward (ms.checkpoint = k > 0): per segment of k layers, from the top, the
+    segment's forward again from its kept boundary, then its backward (ms.checkpoint = 0 launches exactly what it launched before).
+    One backward at a time per device: the main stream's scratch (`scratch`) is
     shared, so concurrent backward passes on one device are not supported."""
     dev = ms.pe.device
     _same_matmul_mode(ms)
@@ -1619,19 +1660,41 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
                                        and hasattr(graph, "sweep_plan")) else None
     # the side stream for the weight gradients (TN_SIDE; not under per-op timing, not with lean activations)
     lane = SideLane(dev) if (current().TN_SIDE and _prof is None and current().ACTIVATIONS != "lean") else None
+    # checkpointed forward: one segment at a time from the top -- its forward again from the kept boundary (under the forward's
+    # options and matmul mode, which this pass runs in), then its backward on the schedule a whole model of that shape would get
+    segs = checkpoint_segments(num_layers, ms.checkpoint) if ms.checkpoint else [(0, num_layers)]
+    plan2 = (graph.sweep_plan(dev, GATE2_WG) if (ms.checkpoint and current().TWO_SIDED_FWD and sweep_width(H, batch_norm)
+                                                 and hasattr(graph, "sweep_plan")) else None)
+    grads = [None] * num_layers
     try:
-        if chain_eligible(H, batch_norm):
-            plan = graph.sweep_plan(dev) if current().TWO_SIDED and hasattr(graph, "sweep_plan") else None
-            gh, ge, grads = layers_backward_chained(idx, N, E, H, P, num_layers, ms.layers, gh, ge, louts, plan, lane)
-        elif ln_chain_eligible(H, batch_norm) and plan_w is not None:
-            gh, ge, grads = layers_backward_chained_ln(idx, N, E, H, P, num_layers, ms.layers, gh, ge, louts, plan_w,
-                                                       H if ln_width is None else int(ln_width), lane)
-        else:
-            grads = [None] * num_layers
-            for i in reversed(range(num_layers)):
-                gh, ge, grads[i] = layer_backward(idx, N, E, H, layer_params(P, i), ms.layers[i], gh, ge, batch_norm, louts[i],
-                                                  plan=plan_w, ln_width=ln_width, lane=lane)
-                ms.layers[i] = None     # release this layer's activations
+        for si in reversed(range(len(segs))):
+            a, b = segs[si]
+            if ms.checkpoint:
+                h, e = ms.boundaries[si]
+                ms.boundaries[si] = None        # the recomputed first layer keeps them until its own backward is done
+                layers = []
+                for i in range(a, b):
+                    h, e, ls = layer_forward(idx, N, E, H, layer_params(P, i), h, e, True, batch_norm, plan=plan2, ln_width=ln_width)
+                    layers.append(ls)
+                del h, e, ls
+            else:
+                layers = ms.layers
+            if chain_eligible(H, batch_norm):
+                plan = graph.sweep_plan(dev) if current().TWO_SIDED and hasattr(graph, "sweep_plan") else None
+                gh, ge, grads[a:b] = layers_backward_chained(idx, N, E, H, P, b - a, layers, gh, ge, louts[a:b], plan, lane, first=a)
+            elif ln_chain_eligible(H, batch_norm) and plan_w is not None:
+                gh, ge, grads[a:b] = layers_backward_chained_ln(idx, N, E, H, P, b - a, layers, gh, ge, louts[a:b], plan_w,
+                                                                H if ln_width is None else int(ln_width), lane, first=a)
+            else:
+                for i in reversed(range(a, b)):
+                    gh, ge, grads[i] = layer_backward(idx, N, E, H, layer_params(P, i), layers[i - a], gh, ge, batch_norm, louts[i],
+                                                      plan=plan_w, ln_width=ln_width, lane=lane)
+                    layers[i - a] = None    # release this layer's activations
+            del layers
+            if lane is not None and si > 0:
+                # a deferred weight-gradient kernel of the segment's bottom layer still reads its activations: the lane holds them
+                # until the main stream has waited for it -- here, so that they are gone before the next segment is recomputed
+                lane.drain()
     finally:
         if lane is not None:
             lane.drain()        # before anything reads a weight gradient, and on the way out of an error

@@ -1,6 +1,8 @@
 """Host-side mirror of the reference's `models` package (models/full_graph.py)."""
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 
@@ -69,10 +71,12 @@ class _ModelFn(torch.autograd.Function):
         # `need` (grad mode on and some parameter or input e / pe requires grad) is decided by the caller: inside
         # Function.forward grad mode is always off, and needs_input_grad stays set under no_grad.
         # norm = (batch_norm, real hidden width): LayerNorm statistics run over the model's real width when the kernels
-        # run it zero-padded to the next width up (gated_gcn_full.py:58-59: nn.LayerNorm(out_channels))
-        batch_norm, ln_width = norm
+        # run it zero-padded to the next width up (gated_gcn_full.py:58-59: nn.LayerNorm(out_channels)); its third entry is the
+        # model's activation_checkpoint (it rides here so that the positional layout backward() counts on stays as it is)
+        batch_norm, ln_width, checkpoint = norm
         P = {k: v.detach() for k, v in zip(names, flat)}
-        scores, saved = engine.model_forward(graph, e.detach(), pe.detach(), P, num_layers, need, batch_norm, ln_width=ln_width)
+        scores, saved = engine.model_forward(graph, e.detach(), pe.detach(), P, num_layers, need, batch_norm, ln_width=ln_width,
+                                             checkpoint=checkpoint)
         ctx.graph, ctx.saved, ctx.P, ctx.names, ctx.L, ctx.bn, ctx.lnw = graph, saved, P, names, num_layers, batch_norm, ln_width
         ctx.params = flat if need else None
         return scores
@@ -117,11 +121,26 @@ def _pad_param(name: str, v: torch.Tensor, H: int, Hp: int) -> torch.Tensor:
     return F.pad(v, (0, d, 0, d)) if v.dim() == 2 else F.pad(v, (0, d))     # [H, H] layer weights, [H] biases
 
 
+def _default_checkpoint():
+    """GraphGatedGCNModel.activation_checkpoint of a new model: GNM_CHECKPOINT, unset = 0.  A value that is no integer is kept as it
+    is and refused where it is used (engine.model_forward)."""
+    v = os.environ.get("GNM_CHECKPOINT", "").strip()
+    try:
+        return int(v) if v else 0
+    except ValueError:
+        return v
+
+
 class GraphGatedGCNModel(nn.Module):
     """models/full_graph.py:11-29.  forward(graph, x, e, pe) -> scores [E,1] (edge-id order).
 
     `graph` is an AssemblyGraph (or anything AssemblyGraph-compatible on a HIP device); `x` is
-    ignored exactly as in the reference (full_graph.py:23 overwrites it)."""
+    ignored exactly as in the reference (full_graph.py:23 overwrites it).
+
+    `activation_checkpoint` (a plain int attribute, default 0 or the environment's GNM_CHECKPOINT; set it after construction):
+    k > 0 keeps, of the layer stack, only the inputs of every k-th layer for the backward, which recomputes one k-layer segment at
+    a time (engine.model_forward, `checkpoint`).  Same logits; less memory for one more forward of the stack per step.  No effect
+    under torch.no_grad().  A negative or non-integer value raises GnmError at the next forward."""
 
     def __init__(self, node_features, edge_features, hidden_features, hidden_edge_features, num_layers,
                  hidden_edge_scores, batch_norm, nb_pos_enc):
@@ -133,6 +152,7 @@ class GraphGatedGCNModel(nn.Module):
         self.predictor = layers.ScorePredictor(hidden_features, hidden_edge_scores)
         self.num_layers = num_layers
         self.batch_norm = bool(batch_norm)
+        self.activation_checkpoint = _default_checkpoint()
 
     def flatten_parameters(self) -> torch.Tensor:
         """See models.flatten_parameters.  Call it after .to(device) and BEFORE building dp.FlatGradients so that the
@@ -151,14 +171,14 @@ class GraphGatedGCNModel(nn.Module):
             names, flat = zip(*self.named_parameters())
             padded = tuple(_pad_param(k, v, H, Hp) for k, v in zip(names, flat))
             need = torch.is_grad_enabled() and (any(p.requires_grad for p in flat) or e.requires_grad or pe.requires_grad)
-            return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H), *padded)
+            return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint), *padded)
         if pe.is_cuda and not _is_flat(self):
             flatten_parameters(self)          # once per device placement: stacked-parameter views instead of torch.cat
         names, flat = zip(*self.named_parameters())
         # e / pe requiring grad (input attribution, a frozen model, a learnable transform in front of the encoders) also
         # needs the activations: the backward returns their gradients; x stays dead (full_graph.py:23), its .grad None
         need = torch.is_grad_enabled() and (any(p.requires_grad for p in flat) or e.requires_grad or pe.requires_grad)
-        return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H), *flat)
+        return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint), *flat)
 
 
 class _BCEFn(torch.autograd.Function):

@@ -120,7 +120,9 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     `hooks` (observers for tests and logging, never needed for training): "after_exchange"(epoch, it, flat) right
     after the gradient exchange of a full-graph step, "after_epoch"(epoch, model) at the end of every epoch;
     "model_factory"(hp) -> nn.Module and "criterion_factory"(pos_weight) -> loss module replace the HIP model / loss (the
-    CPU tier drives THIS loop under eight gloo ranks with a CPU stand-in model: tests/test_dp_gloo.py)."""
+    CPU tier drives THIS loop under eight gloo ranks with a CPU stand-in model: tests/test_dp_gloo.py).
+    Activation checkpointing is a property of the model (GraphGatedGCNModel.activation_checkpoint): the model built here takes
+    the environment's GNM_CHECKPOINT, a "model_factory" sets its own; the loop is the same either way."""
     hooks = hooks or {}
     hp = dict(get_hyperparameters())
     hp.update(hyperparameters or {})
