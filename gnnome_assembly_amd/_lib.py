@@ -99,6 +99,10 @@ SIGNATURES = {
     "gnm_stack_backward": (_i32, [_p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gnm_decode_build_adjacency": (_i32, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p]),
     "gnm_decode_iteration": (_i64, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _p, _i64, _p]),
+    "gnm_decode_iteration_mt": (_i64, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _p, _i64, _p, _i32]),
+    "gnm_decode_sample_workspace_bytes": (_sz, [_i64]),
+    "gnm_decode_candidate_sums": (_i32, [_i64, _i64, _p, _p, _p, _p, _p, _sz, _p, _p, _p]),
+    "gnm_decode_pick": (_i32, [_i64, _i64, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p]),
     "gnm_reduce_partials": (_i32, [_p, _i32, _i32, _i32, _p, _p]),
     "gnm_seg_sum_rows": (_i32, [_i64, _i32, _p, _p, _p, _p, _i64, _p]),
     "gnm_pagerank_pe_workspace_bytes": (_sz, [_i64]),

@@ -3,6 +3,8 @@
 #include <cstdio>
 #include <algorithm>
 #include <cstring>
+#include <atomic>
+#include <thread>
 #include <vector>
 
 #include "gnm_common.h"
@@ -499,6 +501,150 @@ extern "C" int64_t gnm_decode_iteration(int64_t N, const float* scores, const in
     for (int32_t v : best_seen) visited[(size_t)v] = 1;
     // nodes the walk jumped over: succs[a] & preds[b] for consecutive (a, b), and their complements (:231-239)
     for (int64_t j = 0; j + 1 < len; ++j) {
+      const int32_t a = best_walk[(size_t)j], b = best_walk[(size_t)j + 1];
+      for (int32_t p = succ_ptr[a]; p < succ_ptr[a + 1]; ++p) {
+        const int32_t t = succ_nbr[p];
+        bool is_pred = false;
+        for (int32_t q = pred_ptr[b]; q < pred_ptr[b + 1] && !is_pred; ++q) is_pred = pred_nbr[q] == t;
+        if (is_pred) {
+          visited[(size_t)t] = 1;
+          if ((t ^ 1) < N) visited[(size_t)(t ^ 1)] = 1;
+        }
+      }
+    }
+  }
+  return len;
+}
+
+// ------------------------------------------------------------------------------------------
+// The same iteration with the nb candidate walks dealt out to `threads` workers.  A candidate's two walks depend on
+// visited[] (read-only until the end) and on nothing another candidate does, so the workers share no state: each has its own
+// seen_f / seen_b arrays, records every candidate's length in bases (or its error code) and keeps the walk of its own best
+// candidate -- it takes candidates in ascending order, so "strictly longer" keeps the first of equally long walks, as the serial
+// loop does.  After the join the calling thread takes the longest walk (the lowest candidate index among equals), reports the
+// error of the lowest failing index -- what the serial loop would have stopped at -- and updates visited[].
+// ------------------------------------------------------------------------------------------
+namespace {
+
+struct DecodeCtx {
+  int64_t N;
+  const float* scores;
+  const int64_t *prefix_length, *read_length;
+  const int32_t *succ_ptr, *succ_nbr, *succ_eid, *pred_ptr, *pred_nbr, *pred_eid;
+  const uint8_t* visited;
+  const int32_t *start_src, *start_dst;
+};
+
+struct DecodeWorker {
+  std::vector<uint8_t> seen_f, seen_b;
+  std::vector<int32_t> wf, wb, tf, tb, best_walk, best_seen;
+  int64_t best_len = -1;
+  int best_idx = -1;
+};
+
+// candidate i: 0 and *bases_out, or the error code of gnm_decode_iteration (-2, -3, -4)
+int decode_candidate(const DecodeCtx& c, int i, DecodeWorker& w, int64_t* bases_out) {
+  const int64_t N = c.N, cap = 2 * N + 2;
+  if (c.start_src[i] < 0 || c.start_src[i] >= N || c.start_dst[i] < 0 || c.start_dst[i] >= N) return -2;
+  w.wf.clear(); w.wb.clear(); w.tf.clear(); w.tb.clear();
+  const bool ok = greedy_walk(c.start_dst[i], c.scores, c.succ_ptr, c.succ_nbr, c.succ_eid, N, c.visited, nullptr,
+                              w.seen_f.data(), w.wf, w.tf, cap) &&
+                  greedy_walk(c.start_src[i], c.scores, c.pred_ptr, c.pred_nbr, c.pred_eid, N, c.visited, w.seen_f.data(),
+                              w.seen_b.data(), w.wb, w.tb, cap);
+  int rc = 0;
+  int64_t bases = 0;
+  if (!ok) {
+    rc = -3;
+  } else {
+    bool bad = false;
+    auto add = [&](int32_t a, int32_t b) {
+      int32_t k = -1;
+      for (int32_t p = c.succ_ptr[a]; p < c.succ_ptr[a + 1] && k < 0; ++p)
+        if (c.succ_nbr[p] == b) k = c.succ_eid[p];
+      if (k < 0) bad = true; else bases += c.prefix_length[k];
+    };
+    for (size_t j = w.wb.size(); j-- > 1;) add(w.wb[j], w.wb[j - 1]);
+    if (!w.wb.empty() && !w.wf.empty()) add(w.wb[0], w.wf[0]);
+    for (size_t j = 0; j + 1 < w.wf.size(); ++j) add(w.wf[j], w.wf[j + 1]);
+    if (bad) {
+      rc = -4;
+    } else {
+      bases += c.read_length[w.wf.back()];
+      if (bases > w.best_len) {
+        w.best_len = bases;
+        w.best_idx = i;
+        w.best_walk.assign(w.wb.rbegin(), w.wb.rend());
+        w.best_walk.insert(w.best_walk.end(), w.wf.begin(), w.wf.end());
+        w.best_seen = w.tf;
+        w.best_seen.insert(w.best_seen.end(), w.tb.begin(), w.tb.end());
+      }
+    }
+  }
+  for (int32_t v : w.tf) w.seen_f[(size_t)v] = 0;
+  for (int32_t v : w.tb) w.seen_b[(size_t)v] = 0;
+  *bases_out = bases;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" int64_t gnm_decode_iteration_mt(int64_t N, const float* scores, const int64_t* prefix_length,
+                                           const int64_t* read_length, const int32_t* succ_ptr, const int32_t* succ_nbr,
+                                           const int32_t* succ_eid, const int32_t* pred_ptr, const int32_t* pred_nbr,
+                                           const int32_t* pred_eid, uint8_t* visited, int nb, const int32_t* start_src,
+                                           const int32_t* start_dst, int len_threshold, int32_t* walk_out,
+                                           int64_t walk_cap, int64_t* best_length_out, int threads) {
+  if (threads <= 1)
+    return gnm_decode_iteration(N, scores, prefix_length, read_length, succ_ptr, succ_nbr, succ_eid, pred_ptr, pred_nbr,
+                                pred_eid, visited, nb, start_src, start_dst, len_threshold, walk_out, walk_cap,
+                                best_length_out);
+  if (!(N > 0 && scores && prefix_length && read_length && succ_ptr && succ_nbr && succ_eid && pred_ptr && pred_nbr &&
+        pred_eid && visited && nb > 0 && start_src && start_dst && walk_out && walk_cap > 0)) {
+    gnm::set_error("decode_iteration: bad argument");
+    return -1;
+  }
+  const DecodeCtx ctx{N, scores, prefix_length, read_length, succ_ptr, succ_nbr, succ_eid, pred_ptr, pred_nbr, pred_eid,
+                      visited, start_src, start_dst};
+  const int nw = std::min(threads, nb);
+  std::vector<DecodeWorker> workers((size_t)nw);
+  std::vector<int> rc((size_t)nb, 0);
+  std::atomic<int> next{0};
+  auto run = [&](DecodeWorker& w) {
+    w.seen_f.assign((size_t)N, 0);
+    w.seen_b.assign((size_t)N, 0);
+    int64_t bases;
+    for (int i = next.fetch_add(1); i < nb; i = next.fetch_add(1)) rc[(size_t)i] = decode_candidate(ctx, i, w, &bases);
+  };
+  std::vector<std::thread> pool;
+  for (int t = 1; t < nw; ++t) pool.emplace_back(run, std::ref(workers[(size_t)t]));
+  run(workers[0]);
+  for (auto& th : pool) th.join();
+  for (int i = 0; i < nb; ++i) {
+    if (rc[(size_t)i] == -2) gnm::set_error("decode_iteration: start edge %d outside the graph", i);
+    if (rc[(size_t)i] == -3)
+      gnm::set_error("decode_iteration: walk %d exceeds 2N nodes (a cycle of forced moves; the reference does not "
+                     "terminate on this input)", i);
+    if (rc[(size_t)i] == -4)
+      gnm::set_error("decode_iteration: start edge %d (%d -> %d) is not an edge of the graph", i, start_src[i], start_dst[i]);
+    if (rc[(size_t)i] != 0) return rc[(size_t)i];
+  }
+  const DecodeWorker* best = nullptr;
+  for (const DecodeWorker& w : workers)
+    if (w.best_idx >= 0 && (!best || w.best_len > best->best_len || (w.best_len == best->best_len && w.best_idx < best->best_idx)))
+      best = &w;
+  static const std::vector<int32_t> none;
+  const std::vector<int32_t>& best_walk = best ? best->best_walk : none;
+  const std::vector<int32_t>& best_seen = best ? best->best_seen : none;
+  const int64_t len = (int64_t)best_walk.size();
+  if (len > walk_cap) {
+    gnm::set_error("decode_iteration: walk of %lld nodes does not fit walk_out (%lld)", (long long)len, (long long)walk_cap);
+    return -5;
+  }
+  std::memcpy(walk_out, best_walk.data(), (size_t)len * sizeof(int32_t));
+  if (best_length_out) *best_length_out = best ? best->best_len : -1;
+  if (len >= len_threshold) {
+    for (int32_t v : best_seen) visited[(size_t)v] = 1;
+    for (int64_t j = 0; j + 1 < len; ++j) {          // the nodes the walk jumped over, as gnm_decode_iteration
       const int32_t a = best_walk[(size_t)j], b = best_walk[(size_t)j + 1];
       for (int32_t p = succ_ptr[a]; p < succ_ptr[a + 1]; ++p) {
         const int32_t t = succ_nbr[p];

@@ -14,10 +14,16 @@ Differences from the reference, both deliberate:
   * self loops are dropped from the CANDIDATES only, edge ids are never renumbered (the reference
     calls dgl.remove_self_loop and then indexes the renumbered scores with ids of the original
     graph, which is only consistent when there are no self loops);
-  * a cycle of forced single-successor moves raises instead of looping forever."""
+  * a cycle of forced single-successor moves raises instead of looping forever.
+
+`get_contigs_device` is the opt-in form whose O(E) work per iteration -- the candidate list of the not-yet-visited
+sub-graph, the sigmoid, the normalisation and the draw -- runs on the device where the logits already are
+(gnm_decode_candidate_sums / gnm_decode_pick, inverse-CDF sampling), and whose candidate walks run side by side on host
+threads (gnm_decode_iteration_mt).  It draws from the same distribution as `sample_edges`, not the same random numbers."""
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Callable, List, Optional
 
 import numpy as np
@@ -25,7 +31,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["DecodeGraph", "sample_edges", "get_contigs", "infer_contigs"]
+__all__ = ["DecodeGraph", "sample_edges", "get_contigs", "get_contigs_device", "infer_contigs"]
 
 
 def _p(a: np.ndarray):
@@ -47,6 +53,14 @@ class DecodeGraph:
         lib = _lib.load()
         _lib.check(lib.gnm_decode_build_adjacency(_p(self.src), _p(self.dst), self.n, e, *[_p(a) for a in self.succ],
                                                   *[_p(a) for a in self.pred]), "gnm_decode_build_adjacency")
+        self._dev = {}      # device -> (src, dst) int32 on that device (get_contigs_device uploads them once)
+
+    def on_device(self, device):
+        """(src, dst) as int32 tensors on `device`, uploaded once per DecodeGraph."""
+        device = torch.device(device)
+        if device not in self._dev:
+            self._dev[device] = (torch.from_numpy(self.src).to(device), torch.from_numpy(self.dst).to(device))
+        return self._dev[device]
 
     def successors(self, v: int) -> List[int]:
         ptr, nbr, _ = self.succ
@@ -110,12 +124,110 @@ def get_contigs(graph: DecodeGraph, scores, prefix_length, read_length, nb_paths
     return contigs
 
 
-def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int = 50, len_threshold: int = 20):
+def decode_threads(nb_paths: int) -> int:
+    """Host threads of one iteration's candidate walks: min(nb_paths, 16), or GNM_DECODE_THREADS.  Deliberately not the
+    machine's core count: a job is usually entitled to a slice of a large host."""
+    env = os.environ.get("GNM_DECODE_THREADS", "").strip()
+    return max(1, int(env)) if env else max(1, min(int(nb_paths), 16))
+
+
+def get_contigs_device(graph: DecodeGraph, scores, prefix_length, read_length, nb_paths: int = 50, len_threshold: int = 20,
+                       generator: Optional[torch.Generator] = None,
+                       uniforms: Optional[Callable[[int, int], np.ndarray]] = None, threads: Optional[int] = None,
+                       visited: Optional[np.ndarray] = None, timings: Optional[list] = None) -> List[List[int]]:
+    """`get_contigs` with the start edges sampled on the device and the candidate walks on `threads` host threads
+    (default `decode_threads(nb_paths)`).
+
+    `scores` [E] must be a tensor on a HIP device; it is copied to the host once, for the walks.  Per iteration the device
+    forms the candidate weights w (0 for an edge with a visited end or a self loop, else max(sigmoid(score), 1e-9)) and
+    their fp64 prefix sums over fixed blocks of edge ids, and turns nb_paths uniforms u into the edges
+    min{k : C_k > u * total}; the host reads back nb_paths picks and the candidate count, nothing of size E.  After every
+    accepted contig the N bytes of `visited` go to the device mirror.
+
+    This draws from the SAME DISTRIBUTION as `sample_edges` (inference.py:270-277: p = w / sum(w) over the candidate
+    edges), by inverse CDF from `torch.rand(nb_paths, dtype=float64, generator=generator)` -- not the same random numbers
+    as torch's Categorical / multinomial: a seeded run does not reproduce the reference's draws, `get_contigs` does.
+    `uniforms(iteration, nb_paths) -> float64[nb_paths]` in [0, 1) replaces the generator (tests).
+    `timings`: a list that receives (sampling seconds, walks seconds) per iteration (tools/decode_timing.py)."""
+    import time
+    from .engine import _call, _ptr, _stream, scratch
+    lib = _lib.load()
+    if not torch.is_tensor(scores) or scores.device.type != "cuda":
+        raise _lib.GnmError("get_contigs_device: scores must be a tensor on a HIP device (get_contigs decodes host scores)")
+    dev = scores.device
+    n, e = graph.n, graph.src.size
+    sd = scores.detach().reshape(-1)
+    sd = (sd if sd.dtype == torch.float32 else sd.float()).contiguous()
+    pl = np.ascontiguousarray(torch.as_tensor(prefix_length).cpu().numpy().reshape(-1), dtype=np.int64)
+    rl = np.ascontiguousarray(torch.as_tensor(read_length).cpu().numpy().reshape(-1), dtype=np.int64)
+    if sd.numel() != e or pl.size != e or rl.size != n:
+        raise ValueError("scores / prefix_length need one entry per edge, read_length one per node")
+    vis = np.zeros(n, np.uint8) if visited is None else visited
+    if vis.dtype != np.uint8 or vis.size != n or not vis.flags.c_contiguous:
+        raise ValueError("visited must be a contiguous uint8 array with one entry per node")
+    nb = int(nb_paths)
+    if e == 0 or nb <= 0:
+        return []
+    nthreads = decode_threads(nb) if threads is None else max(1, int(threads))
+    contigs: List[List[int]] = []
+    with torch.cuda.device(dev):
+        sc = np.ascontiguousarray(sd.cpu().numpy())                   # the one copy of the scores, for the walks
+        src_d, dst_d = graph.on_device(dev)
+        vis_h = torch.from_numpy(vis)
+        vis_d = vis_h.to(dev)
+        need = lib.gnm_decode_sample_workspace_bytes(e)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)         # its own buffer: the prefix lives across two calls
+        out_d = torch.zeros(32 + 4 * nb, dtype=torch.uint8, device=dev)   # stats (gnm.h) | picks
+        picks_ptr = C.c_void_p(out_d.data_ptr() + 32)
+        walk = np.empty(2 * n + 2, np.int32)
+        best_len = C.c_int64(0)
+        it = 0
+        while True:
+            t0 = time.perf_counter()
+            u = uniforms(it, nb) if uniforms is not None else torch.rand(nb, dtype=torch.float64, generator=generator)
+            u = torch.as_tensor(u, dtype=torch.float64).reshape(-1)
+            if u.numel() != nb or bool(((u < 0) | (u >= 1)).any()):
+                raise ValueError("uniforms must return nb_paths float64 values in [0, 1)")
+            u_d = u.to(dev)
+            _call("gnm_decode_candidate_sums", e, n, _ptr(sd), _ptr(src_d), _ptr(dst_d), _ptr(vis_d), _ptr(ws), need,
+                  C.c_void_p(0), _ptr(out_d), _stream())
+            _call("gnm_decode_pick", e, n, _ptr(sd), _ptr(src_d), _ptr(dst_d), _ptr(vis_d), _ptr(ws), _ptr(out_d), nb,
+                  _ptr(u_d), picks_ptr, _stream())
+            out = out_d.cpu().numpy()
+            if int(out[8:16].view(np.int64)[0]) == 0:                  # no candidate edge left
+                break
+            picks = out[32:].view(np.int32)
+            s0 = np.ascontiguousarray(graph.src[picks])
+            d0 = np.ascontiguousarray(graph.dst[picks])
+            t1 = time.perf_counter()
+            length = lib.gnm_decode_iteration_mt(n, _p(sc), _p(pl), _p(rl), *[_p(a) for a in graph.succ],
+                                                 *[_p(a) for a in graph.pred], _p(vis), nb, _p(s0), _p(d0),
+                                                 int(len_threshold), _p(walk), walk.size, C.byref(best_len), nthreads)
+            t2 = time.perf_counter()
+            if length < 0:
+                _lib.check(int(length), "gnm_decode_iteration_mt")
+            if length >= len_threshold:
+                vis_d.copy_(vis_h)                                     # N bytes: the device mirror of visited
+            if timings is not None:                                    # the mirror's upload counts as sampling time
+                timings.append((t1 - t0 + time.perf_counter() - t2, t2 - t1))
+            if length < len_threshold:
+                break
+            contigs.append(walk[:length].tolist())
+            it += 1
+    return contigs
+
+
+def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int = 50, len_threshold: int = 20,
+                  device_sampling: bool = False):
     """The per-graph body of inference.inference (inference.py:444-490): logits of the whole graph under
-    no_grad in eval mode, stored by edge id, then greedy decode.  Returns (scores [E], walks)."""
+    no_grad in eval mode, stored by edge id, then greedy decode.  Returns (scores [E], walks).
+    device_sampling=True: the logits stay on the device for `get_contigs_device` (same distribution of start edges,
+    other random numbers); False is `get_contigs` with the reference's seeded draws."""
     model.eval()
     with torch.no_grad():
         scores = model(graph, None, e, pe).squeeze(-1)                 # inference.py:453-454
     src, dst = graph.edges()
     dg = DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), graph.num_nodes())
+    if device_sampling:
+        return scores, get_contigs_device(dg, scores, prefix_length, read_length, nb_paths, len_threshold)
     return scores, get_contigs(dg, scores, prefix_length, read_length, nb_paths, len_threshold)

@@ -129,6 +129,38 @@ int64_t gnm_decode_iteration(int64_t N, const float* scores, const int64_t* pref
                              const int32_t* pred_eid, uint8_t* visited, int nb, const int32_t* start_src,
                              const int32_t* start_dst, int len_threshold, int32_t* walk_out,
                              int64_t walk_cap, int64_t* best_length_out);
+/* decode_iteration_mt: the same iteration, the nb candidates dealt out to min(threads, nb) host threads (each with its own
+ *   seen arrays; the choice of the winner and the visited[] update happen in the calling thread after the join).  Identical
+ *   results: the first of equally long walks, the same visited[], the same error codes (of the lowest failing candidate).
+ *   threads <= 1 IS gnm_decode_iteration.                                                                                  */
+int64_t gnm_decode_iteration_mt(int64_t N, const float* scores, const int64_t* prefix_length,
+                                const int64_t* read_length, const int32_t* succ_ptr, const int32_t* succ_nbr,
+                                const int32_t* succ_eid, const int32_t* pred_ptr, const int32_t* pred_nbr,
+                                const int32_t* pred_eid, uint8_t* visited, int nb, const int32_t* start_src,
+                                const int32_t* start_dst, int len_threshold, int32_t* walk_out,
+                                int64_t walk_cap, int64_t* best_length_out, int threads);
+
+/* ---- decode: start edges sampled on the device (DEVICE pointers; inference.py:256-277) ----------
+ * For edge k = (src[k] -> dst[k]) with logit scores[k] and visited[N] (uint8):
+ *   w_k = 0 if visited[src[k]] | visited[dst[k]] | (src[k] == dst[k]) (get_subgraph, self loops are no candidates),
+ *         else max(sigmoid(scores[k]), 1e-9f) (the fp32 number nearest to the fp64 sigmoid)
+ *   C_k = w_0 + ... + w_k in fp64;  pick(u) = the smallest k with w_k > 0 and C_k > u * C_{E-1}, u in [0, 1)
+ * -- the distribution of the reference's sample_edges (p = w / sum over the candidate edges), drawn by inverse CDF.
+ * decode_candidate_sums: one streaming pass forms the fp64 sums of w over FIXED blocks of 2048 edge ids (the summation tree does
+ *   not depend on the grid, the CU count or gnm_set_occupancy_cap; no atomics: two runs are bit-identical), one workgroup turns
+ *   them into the block prefix in `ws` (gnm_decode_sample_workspace_bytes(E), 16-byte aligned) and writes `stats` (32 bytes:
+ *   double total = C_{E-1}; int64 count = #{w_k > 0}; int64 the last block with a candidate; int64 the block count).
+ *   w_out: NULL, or [E] fp32 that receives w (tests; the product path recomputes w in decode_pick).  E == 0: stats zeroed, no launch.
+ * decode_pick: picks[i] = pick(u[i]) for i < nb, one wave per draw: binary search over the block prefix, then a scan of that
+ *   block's weights in edge-id order.  Same scores / src / dst / visited / ws / stats as the decode_candidate_sums call before it
+ *   on the same stream.  u * total rounding up to total gives the LAST edge with w > 0; an edge with w = 0 is never picked;
+ *   count == 0 leaves picks untouched.  E == 0 or nb == 0: no launch.                                                       */
+size_t gnm_decode_sample_workspace_bytes(int64_t E);
+int gnm_decode_candidate_sums(int64_t E, int64_t N, const float* scores, const int32_t* src, const int32_t* dst,
+                              const uint8_t* visited, void* ws, size_t ws_bytes, float* w_out, void* stats, void* stream);
+int gnm_decode_pick(int64_t E, int64_t N, const float* scores, const int32_t* src, const int32_t* dst,
+                    const uint8_t* visited, const void* ws, const void* stats, int nb, const double* u, int32_t* picks,
+                    void* stream);
 
 /* ---- dense (fp32 MFMA v_mfma_f32_32x32x2_f32): nn.Linear call sites
  *      gated_gcn_full.py:107-113, full_graph.py:23-26, score_predictor.py:15-17 and their
