@@ -51,7 +51,12 @@ __device__ __forceinline__ float4 live_mask(int c4, int width) {
 template <int H>
 __device__ __forceinline__ float4 row_normalize(float4 x, const float4& live, float inv_w, float& rstd) {
   constexpr int G = H / 4;
-  const float mu = row_sum<G>(hsum4(x)) * inv_w;
+  float mu = row_sum<G>(hsum4(x)) * inv_w;
+  // A zero-padded width is no power of two: neither the sum of `width` equal values nor 1 / width is exact, so the mean of a constant
+  // row c came out as c (1 +- 2^-23) and xhat as that rounding error times rstd = 1/sqrt(eps) (3e-3 at |c| ~ 80) where nn.LayerNorm gives
+  // exactly 0.  One correction step, mu += mean(x - mu), makes the mean of such a row exact again (x - mu is exact there) and takes
+  // the same error out of every row with |mean| >> std.  A full width takes the branch-free path and keeps its bits (uniform test).
+  if (inv_w != 1.0f / H) mu += row_sum<G>(hsum4((x - f4(mu)) * live)) * inv_w;
   const float4 d = (x - f4(mu)) * live;
   const float var = row_sum<G>(hsum4(d * d)) * inv_w;
   rstd = 1.0f / sqrtf(var + kEpsLN);

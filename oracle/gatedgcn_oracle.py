@@ -169,8 +169,25 @@ def _bn_bwd(gy, xh, w, rstd):
     return gx, gg, gb
 
 
-def manual_forward_backward(sd, src, dst, n, e_raw, pe, y, pos_weight, keep=False, masks=None):
-    """Forward + hand-derived backward (BatchNorm mode).  Returns (scores, loss, grads[, dbg])
+def _ln_fwd(x, w, b):
+    """nn.LayerNorm(H): statistics over dim 1, biased variance; rstd is a per-row vector [rows]."""
+    mu = x.mean(1, keepdim=True)
+    var = x.var(1, unbiased=False, keepdim=True)
+    rstd = torch.rsqrt(var + EPS_BN)
+    xh = (x - mu) * rstd
+    return xh * w + b, xh, rstd.reshape(-1)
+
+
+def _ln_bwd(gy, xh, w, rstd):
+    """LNbwd(gy) = rstd_row*(a - mean_row(a) - xh*mean_row(a*xh)), a = w*gy; ggamma = sum_rows gy*xh; gbeta = sum_rows gy."""
+    a = w * gy
+    gx = rstd.reshape(-1, 1) * (a - a.mean(1, keepdim=True) - xh * (a * xh).mean(1, keepdim=True))
+    return gx, (gy * xh).sum(0), gy.sum(0)
+
+
+def manual_forward_backward(sd, src, dst, n, e_raw, pe, y, pos_weight, keep=False, masks=None, batch_norm=True):
+    """Forward + hand-derived backward (BatchNorm1d, or with batch_norm=False nn.LayerNorm: the row-wise twins _ln_fwd /
+    _ln_bwd, rstd_e / rstd_h of dbg then per-row vectors).  Returns (scores, loss, grads[, dbg])
     with grads keyed like the state_dict.  Mirrors SURVEY.md section 8a row 8.
 
     `masks` (optional) overrides the relu branch decisions of the backward pass:
@@ -185,6 +202,7 @@ def manual_forward_backward(sd, src, dst, n, e_raw, pe, y, pos_weight, keep=Fals
     E = src.numel()
     g = {}
     dbg = {}
+    norm_fwd, norm_bwd = (_bn_fwd, _bn_bwd) if batch_norm else (_ln_fwd, _ln_bwd)
     # ---- forward, keeping what the kernels keep ----
     h = pe @ sd["linear_pe.weight"].t() + sd["linear_pe.bias"]
     a1_pre = e_raw @ sd["linear1_edge.weight"].t() + sd["linear1_edge.bias"]
@@ -198,7 +216,7 @@ def manual_forward_backward(sd, src, dst, n, e_raw, pe, y, pos_weight, keep=Fals
         P = h @ W5.t() + b5
         A1h, A2h, A3h, B1h, B2h = P.chunk(5, dim=1)
         t = B1h[src] + B2h[dst] + e @ sd[p + "B_3.weight"].t() + sd[p + "B_3.bias"]
-        u, th, rstd_e = _bn_fwd(t, sd[p + "bn_e.weight"], sd[p + "bn_e.bias"])
+        u, th, rstd_e = norm_fwd(t, sd[p + "bn_e.weight"], sd[p + "bn_e.bias"])
         e_out = torch.relu(u) + e
         sig = torch.sigmoid(e_out)
         inv_f = 1.0 / (_seg_sum(dst, sig, n) + EPS_DEN)
@@ -206,7 +224,7 @@ def manual_forward_backward(sd, src, dst, n, e_raw, pe, y, pos_weight, keep=Fals
         hf = _seg_sum(dst, sig * A2h[src], n) * inv_f
         hb = _seg_sum(src, sig * A3h[dst], n) * inv_b
         z = A1h + hf + hb
-        w, zh, rstd_h = _bn_fwd(z, sd[p + "bn_h.weight"], sd[p + "bn_h.bias"])
+        w, zh, rstd_h = norm_fwd(z, sd[p + "bn_h.weight"], sd[p + "bn_h.bias"])
         h_out = torch.relu(w) + h
         saved.append(dict(h=h, e=e, W5=W5, A2h=A2h, A3h=A3h, u=u, th=th, rstd_e=rstd_e, sig=sig,
                           inv_f=inv_f, inv_b=inv_b, hf=hf, hb=hb, w=w, zh=zh, rstd_h=rstd_h,
@@ -236,7 +254,7 @@ def manual_forward_backward(sd, src, dst, n, e_raw, pe, y, pos_weight, keep=Fals
         p = f"gnn.convs.{i}."
         s = saved[i]
         gw = gh * (masks["w"][i] if masks else (s["w"] > 0))
-        gz, g[p + "bn_h.weight"], g[p + "bn_h.bias"] = _bn_bwd(gw, s["zh"], sd[p + "bn_h.weight"], s["rstd_h"])
+        gz, g[p + "bn_h.weight"], g[p + "bn_h.bias"] = norm_bwd(gw, s["zh"], sd[p + "bn_h.weight"], s["rstd_h"])
         Qf = gz * s["inv_f"]
         Rf = Qf * s["hf"]
         Qb = gz * s["inv_b"]
@@ -247,7 +265,7 @@ def manual_forward_backward(sd, src, dst, n, e_raw, pe, y, pos_weight, keep=Fals
         gA3h = _seg_sum(dst, sig * Qb[src], n)
         ge_tot = ge + gsig * sig * (1.0 - sig)
         gu = ge_tot * (masks["u"][i] if masks else (s["u"] > 0))
-        gt, g[p + "bn_e.weight"], g[p + "bn_e.bias"] = _bn_bwd(gu, s["th"], sd[p + "bn_e.weight"], s["rstd_e"])
+        gt, g[p + "bn_e.weight"], g[p + "bn_e.bias"] = norm_bwd(gu, s["th"], sd[p + "bn_e.weight"], s["rstd_e"])
         gB1h = _seg_sum(src, gt, n)
         gB2h = _seg_sum(dst, gt, n)
         g[p + "B_3.weight"] = gt.t() @ s["e"]

@@ -62,8 +62,8 @@ def test_input_grads_match_reference(fname):
     model = _model(synth.synth_state_dict(H, L, seed), H, L, bn, dev)
     g = G.AssemblyGraph(z["src"], z["dst"], int(z["n"])).to(dev)
     _, _, ge, gpe = _run(model, g, z["e_raw"], z["pe"], z["y"], float(z["pos_weight"]), dev)
-    exact = (lambda: _branch_exact(g, synth.synth_state_dict(H, L, seed), H, L, z["e_raw"], z["pe"], z["y"],
-                                   float(z["pos_weight"]), dev)) if bn else None
+    exact = lambda: _branch_exact(g, synth.synth_state_dict(H, L, seed), H, L, z["e_raw"], z["pe"], z["y"],  # noqa: E731
+                                  float(z["pos_weight"]), dev, bn)
     _check(ge.numpy(), gpe.numpy(), z["grad_e_raw"], z["grad_pe"], fname, exact)
 
 

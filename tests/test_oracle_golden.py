@@ -73,6 +73,70 @@ def test_manual_backward_matches_autograd(fname):
         assert np.abs(a - b).max() <= 1e-12 * max(1.0, np.abs(b).max()) + 1e-15, k
 
 
+def _ln_cases():
+    return golden_files("h32l2ln") + ["synth_h96l3"]
+
+
+def _ln_case(case):
+    """(p64 with requires_grad, src, dst, n, e_raw, pe, y, pw) of a LayerNorm fixture or of the synthetic H = 96, L = 3 case."""
+    if case.endswith(".npz"):
+        z, sd, H, L, bn = load_case(case)
+        assert not bn
+        return (sd_to_torch(sd, torch.float64, requires_grad=True),) + _inputs(z, torch.float64)
+    from gnnome_assembly_amd import synth
+    src, dst, n = synth.make_graph(300, seed=5, permute_edge_ids=True)
+    inp = synth.make_inputs(src, dst, n, seed=96)
+    t = lambda a: torch.from_numpy(a).double()  # noqa: E731
+    return (sd_to_torch(synth.synth_state_dict(96, 3, seed=3), torch.float64, requires_grad=True), torch.from_numpy(src).long(),
+            torch.from_numpy(dst).long(), n, t(inp["e"]), t(inp["pe"]), t(inp["y"]), float(inp["pos_weight"]))
+
+
+@pytest.mark.parametrize("case", _ln_cases())
+def test_layernorm_manual_backward_matches_autograd(case):
+    """manual_forward_backward(batch_norm=False) -- the row-wise _ln_fwd / _ln_bwd -- against autograd of model_forward in fp64
+    (the bar of test_manual_backward_matches_autograd); the oracle's own branches passed as `masks` reproduce the unmasked run
+    bitwise, and one flipped mask element changes the gradients (the argument is live in LayerNorm mode)."""
+    p, src, dst, n, e_raw, pe, y, pw = _ln_case(case)
+    s_ag = orc.model_forward(p, src, dst, n, e_raw, pe, False)
+    loss = orc.bce_loss(s_ag, y, pw)
+    loss.backward()
+    pd = {k: v.detach() for k, v in p.items()}
+    with torch.no_grad():
+        s, l2, g, dbg = orc.manual_forward_backward(pd, src, dst, n, e_raw, pe, y, pw, keep=True, batch_norm=False)
+    assert abs(l2.item() - loss.item()) < 1e-13
+    assert rel_l2(s.numpy(), s_ag.detach().numpy()) < 1e-12
+    L = orc.num_layers_of(pd)
+    assert dbg[0]["rstd_e"].shape == (src.numel(),) and dbg[0]["rstd_h"].shape == (n,)
+    for k in p:
+        a, b = g[k].numpy(), p[k].grad.numpy()
+        assert a.shape == b.shape, k
+        assert np.abs(a - b).max() <= 1e-12 * max(1.0, np.abs(b).max()) + 1e-15, k
+    a1_pre = e_raw @ pd["linear1_edge.weight"].t() + pd["linear1_edge.bias"]
+    masks = {"u": [dbg[i]["u"] > 0 for i in range(L)], "w": [dbg[i]["w"] > 0 for i in range(L)], "hid": dbg["hid"] > 0, "a1": a1_pre > 0}
+    with torch.no_grad():
+        _, _, gm = orc.manual_forward_backward(pd, src, dst, n, e_raw, pe, y, pw, masks=masks, batch_norm=False)
+    assert all(torch.equal(gm[k], g[k]) for k in g)
+    for key, i in (("u", 0), ("w", L - 1)):
+        flipped = dict(masks, **{key: [m.clone() for m in masks[key]]})
+        flipped[key][i][3, 5] = ~flipped[key][i][3, 5]
+        with torch.no_grad():
+            _, _, gf = orc.manual_forward_backward(pd, src, dst, n, e_raw, pe, y, pw, masks=flipped, batch_norm=False)
+        assert any(not torch.equal(gf[k], g[k]) for k in g), key
+
+
+def test_manual_backward_default_is_the_batchnorm_form():
+    """batch_norm=True (the default) takes the BatchNorm statistics exactly as before: bitwise the explicit call, and not LayerNorm's."""
+    z, sd, H, L, bn = load_case("tiny_h64l1_s0.npz")
+    src, dst, n, e_raw, pe, y, pw = _inputs(z, torch.float64)
+    p = sd_to_torch(sd, torch.float64)
+    with torch.no_grad():
+        _, _, g0 = orc.manual_forward_backward(p, src, dst, n, e_raw, pe, y, pw)
+        _, _, g1 = orc.manual_forward_backward(p, src, dst, n, e_raw, pe, y, pw, batch_norm=True)
+        _, _, g2 = orc.manual_forward_backward(p, src, dst, n, e_raw, pe, y, pw, batch_norm=False)
+    assert all(torch.equal(g0[k], g1[k]) for k in g0)
+    assert not torch.equal(g0["linear_pe.weight"], g2["linear_pe.weight"])
+
+
 @pytest.mark.parametrize("fname", golden_files("tiny_h64l1"))
 def test_harness_pins(fname):
     """train.py:181 ratio, utils.calculate_tfpn counts, 3-step Adam loss sequence, eval==train."""
