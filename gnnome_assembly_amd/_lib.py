@@ -51,6 +51,13 @@ SIGNATURES = {
     "gnm_ln_node_bwd": (_i32, [_i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _pi, _i32, _p]),
     "gnm_ln_edge_bwd_dst": (_i32, [_i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _pi, _i32, _p]),
     "gnm_ln_edge_bwd_src": (_i32, [_i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "gnm_ln_wide_row_stats": (_i32, [_i64, _i32, _p, _i64, _i32, _p, _p]),
+    "gnm_ln_wide_edge_gate_fwd": (_i32, [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _p]),
+    "gnm_ln_wide_node_update_fwd": (_i32, [_i64, _p, _p, _p, _p, _p, _p, _i32, _i32, _p]),
+    "gnm_ln_wide_node_bwd_sums": (_i32, [_i64, _p, _p, _p, _p, _p, _p, _p, _pi, _i32, _i32, _p]),
+    "gnm_ln_wide_node_bwd_apply": (_i32, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _p]),
+    "gnm_ln_wide_edge_bwd_sums": (_i32, [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _pi, _i32, _i32, _p]),
+    "gnm_ln_wide_edge_bwd_apply": (_i32, [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _p]),
     "gnm_rowtile_workspace_bytes": (_sz, [_i32]),
     "gnm_set_occupancy_cap": (_i32, [_i32]),
     "gnm_debug_set_variant": (_i32, [C.c_char_p, _i32]),

@@ -520,18 +520,20 @@ def _proj_and_t(idx, N, E, H, prm, h_in, e_in, nblk):
 @on_device_of(lambda idx, N, E, H, prm, h_in, *a, **k: h_in)
 @_scoped()
 def layer_forward(idx, N: int, E: int, H: int, prm: LayerParams, h_in, e_in, save: bool, batch_norm: bool = True,
-                  residual: bool = True, plan: Optional[dict] = None, ln_width: Optional[int] = None):
+                  residual: bool = True, plan: Optional[dict] = None, ln_width: Optional[int] = None, wide_ln: Optional[bool] = None):
     """GatedGCN_1d.forward (gated_gcn_full.py:99-157) on internal-order tensors.
     Returns (h_out, e_out, LayerSaved or None).  H = out_channels; h_in [N,Hin], e_in [E,Hin] with Hin != H only
     when residual is False (the reference drops the residual then: gated_gcn_full.py:41-42).
     plan (graph.sweep_plan(device, 2), BatchNorm, H = 128 or 256): gate + by-source aggregation as ONE two-sided sweep.
     ln_width (LayerNorm mode, a layer zero-padded to the kernel width H): the layer's real out_channels -- nn.LayerNorm
-    normalises over those (gated_gcn_full.py:58-59), the dead channels are left out of the row statistics."""
+    normalises over those (gated_gcn_full.py:58-59), the dead channels are left out of the row statistics.
+    wide_ln (LayerNorm mode, H > 256): the opt-in a GatedGCN_1d recorded at construction (layers.WIDE_LAYERNORM); None: the
+    switch's current value.  Off, such a layer raises NotImplementedError as before."""
     lnw = H if ln_width is None else int(ln_width)
     if residual and h_in.shape[1] != H:
         raise _lib.GnmError("layer_forward: a residual layer needs in_channels == out_channels")
     if H > WIDE_CHUNK:
-        return _wide_layer_forward(idx, N, E, H, prm, h_in, e_in, save, batch_norm, residual, plan)
+        return _wide_layer_forward(idx, N, E, H, prm, h_in, e_in, save, batch_norm, residual, plan, lnw, wide_ln)
     nblk = C.c_int(0)
     P, t = _proj_and_t(idx, N, E, H, prm, h_in, e_in, nblk)
     return _layer_forward_tail(idx, N, E, H, prm, h_in, e_in, P, t, nblk, save, batch_norm, residual, plan, lnw)
@@ -605,8 +607,8 @@ def _layer_forward_tail(idx, N, E, H, prm, h_in, e_in, P, t, nblk, save, batch_n
 # A layer wider than the widest kernel instantiation (gated_gcn_full.py:44-50 takes any nn.Linear width): the two dense products
 # run at full width on the generic GEMM route, everything between them -- BatchNorm statistics, gate, both aggregations, node
 # update, and the duals of all of it -- is separable by columns and runs once per WIDE_CHUNK-column problem on contiguous copies
-# of the chunk (strided copies in and out: slow by construction, but a legal width no longer raises).  BatchNorm only: LayerNorm's
-# row statistics span the chunks.
+# of the chunk (strided copies in and out: slow by construction, but a legal width no longer raises).  BatchNorm by default; LayerNorm's
+# row statistics span the chunks: _wide_ln_layer_forward below, opt-in (layers.WIDE_LAYERNORM).
 WIDE_CHUNK = 256
 
 
@@ -628,7 +630,18 @@ def _chunk_params(prm: LayerParams, c0: int, w: int) -> LayerParams:
                        gamma_h=prm.gamma_h[sl], beta_h=prm.beta_h[sl])
 
 
-def _wide_layer_forward(idx, N, E, H, prm, h_in, e_in, save, batch_norm, residual, plan):
+def _wide_ln_enabled(wide_ln: Optional[bool]) -> bool:
+    if wide_ln is None:
+        from . import layers
+        return bool(layers.WIDE_LAYERNORM)
+    return bool(wide_ln)
+
+
+def _wide_layer_forward(idx, N, E, H, prm, h_in, e_in, save, batch_norm, residual, plan, lnw=None, wide_ln=None):
+    if not batch_norm and _wide_ln_enabled(wide_ln):
+        if H % WIDE_CHUNK:
+            raise _lib.GnmError(f"layer_forward: a wide layer runs zero-padded to a multiple of {WIDE_CHUNK} (layers.padded_width), got {H}")
+        return _wide_ln_layer_forward(idx, N, E, H, prm, h_in, e_in, save, residual, H if lnw is None else lnw)
     if not batch_norm:
         raise NotImplementedError(f"GatedGCN_1d with LayerNorm at width {H}: the LayerNorm kernels hold a row in one wavefront "
                                   f"(widths up to {WIDE_CHUNK}); BatchNorm layers run at any width")
@@ -659,6 +672,123 @@ def _wide_layer_forward(idx, N, E, H, prm, h_in, e_in, save, batch_norm, residua
             chunks.append(sv)
     saved = LayerSaved(opts=current(), h_in=h_in, e_in=e_in, chunks=chunks, matmul=_lib.get_matmul_mode()) if save else None
     return h_out, e_out, saved
+
+
+# LayerNorm at a width above 256 (opt-in: layers.WIDE_LAYERNORM).  The same chunking, but a row's statistics span its chunks: the
+# forward forms (mean, rstd) of every whole row once (gnm_ln_wide_row_stats over the stack of chunk copies) and hands them to the
+# per-chunk gate / node update; the backward sums the two row means of LNbwd chunk by chunk (phase A, ascending chunk order on one
+# stream) before any chunk applies them (phase B).  What carries no norm is the BatchNorm path's: gnm_edge_t_stats_fwd (its
+# BatchNorm partial sums are ignored), gnm_node_agg_src_fwd, gnm_ln_edge_bwd_src, the GEMM tail.  Separate passes only (no sweep plan).
+def _wide_row_stats(stack: torch.Tensor, lnw: int) -> torch.Tensor:
+    """(mean, rstd) [R,2] over the lnw live channels of the rows of a [C,R,256] stack of chunk copies."""
+    C_, R, w = stack.shape
+    stat = torch.empty(R, 2, dtype=torch.float32, device=stack.device)
+    _call("gnm_ln_wide_row_stats", R, C_, _ptr(stack), R * w, lnw, _ptr(stat), _stream())
+    return stat
+
+
+def _wide_ln_layer_forward(idx, N, E, H, prm, h_in, e_in, save, residual, lnw):
+    dev = h_in.device
+    sc = scratch(dev)
+    st = _stream()
+    f32 = dict(dtype=torch.float32, device=dev)
+    w = WIDE_CHUNK
+    nc = H // w
+    P = torch.empty(N, 5 * H, **f32)
+    t = torch.empty(E, H, **f32)
+    gemm(NT, h_in, prm.W5, P, bias=prm.b5)                                      # (:107-112)
+    gemm(NT, e_in, prm.W3, t, bias=prm.b3)                                      # (:113)
+    ts = torch.empty(nc, E, w, **f32)
+    Ps = []
+    for ci, c0 in enumerate(range(0, H, w)):
+        Ps.append(_cols(P, c0, w, 5))
+        ts[ci].copy_(t[:, c0:c0 + w])
+        _call("gnm_edge_t_stats_fwd", E, w, _ptr(ts[ci]), _ptr(Ps[ci]), _ptr(idx["isrc"]), _ptr(idx["idst"]), _ptr(sc.partials),
+              C.byref(C.c_int(0)), st)                                          # (:120-121)
+    del P, t
+    stat_e = _wide_row_stats(ts, lnw)
+    h_out, e_out = torch.empty(N, H, **f32), torch.empty(E, H, **f32)
+    zs = torch.empty(nc, N, w, **f32)
+    chunks = []
+    for ci, c0 in enumerate(range(0, H, w)):
+        cp = _chunk_params(prm, c0, w)
+        ec = _cols(e_in, c0, w) if residual else None
+        eo, hf, inv_f, hb, inv_b = (torch.empty(E, w, **f32), torch.empty(N, w, **f32), torch.empty(N, w, **f32),
+                                    torch.empty(N, w, **f32), torch.empty(N, w, **f32))
+        _call("gnm_ln_wide_edge_gate_fwd", N, E, _ptr(ts[ci]), _ptr(ec), _ptr(cp.gamma_e), _ptr(cp.beta_e), _ptr(stat_e), _ptr(Ps[ci]),
+              _ptr(idx["isrc"]), _ptr(idx["in_ptr"]), _ptr(eo), _ptr(hf), _ptr(inv_f), c0, lnw, st)        # (:122-130)
+        _call("gnm_node_agg_src_fwd", N, E, w, _ptr(eo), _ptr(Ps[ci]), _ptr(idx["out_ptr"]), _ptr(idx["out_pos"]), _ptr(idx["out_dst"]),
+              _ptr(hf), _ptr(hb), _ptr(inv_b), _ptr(zs[ci]), _ptr(sc.partials), C.byref(C.c_int(0)), st)   # (:133-147)
+        _put_cols(e_out, eo, c0, w)
+        if save:
+            lean = current().ACTIVATIONS == "lean"
+            chunks.append(LayerSaved(P=None if lean else Ps[ci], t=None if lean else ts[ci], e_out=eo, hf=hf, inv_f=inv_f, hb=hb,
+                                     inv_b=inv_b, z=zs[ci]))
+    stat_h = _wide_row_stats(zs, lnw)
+    for ci, c0 in enumerate(range(0, H, w)):
+        cp = _chunk_params(prm, c0, w)
+        hc = _cols(h_in, c0, w) if residual else None
+        ho = torch.empty(N, w, **f32)
+        _call("gnm_ln_wide_node_update_fwd", N, _ptr(zs[ci]), _ptr(stat_h), _ptr(cp.gamma_h), _ptr(cp.beta_h), _ptr(hc), _ptr(ho), c0, lnw,
+              st)                                                                # (:147-152)
+        _put_cols(h_out, ho, c0, w)
+    saved = LayerSaved(opts=current(), h_in=h_in, e_in=e_in, chunks=chunks, stat_e=stat_e, stat_h=stat_h,
+                       matmul=_lib.get_matmul_mode()) if save else None
+    return h_out, e_out, saved
+
+
+def _wide_ln_layer_backward(idx, N, E, H, prm, s: LayerSaved, gh_out, ge, out, residual, lnw):
+    dev = gh_out.device
+    sc = scratch(dev)
+    st = _stream()
+    f32 = dict(dtype=torch.float32, device=dev)
+    Hin = s.h_in.shape[1]
+    w = WIDE_CHUNK
+    new = lambda key, *shape: out[key] if key in out else torch.empty(*shape, **f32)  # noqa: E731
+    g: Dict[str, torch.Tensor] = {k: new(k, H) for k in ("gamma_e", "beta_e", "gamma_h", "beta_h")}
+    if any(c.P is None or c.t is None for c in s.chunks):      # "lean" activations: the saved stat_e is the forward's
+        _wide_rebuild(idx, N, E, H, prm, s)
+    nblk = C.c_int(0)
+    starts = list(range(0, H, w))
+    rs_h = torch.empty(N, 2, **f32)
+    rs_e = torch.empty(E, 2, **f32)
+    ghc = [_cols(gh_out, c0, w) for c0 in starts]
+    # node side, phase A: the row sums of LNbwd_h over all chunks, the column partials of ggamma_h / gbeta_h
+    for ci, c0 in enumerate(starts):
+        sl, c = slice(c0, c0 + w), s.chunks[ci]
+        _call("gnm_ln_wide_node_bwd_sums", N, _ptr(c.z), _ptr(s.stat_h), _ptr(prm.gamma_h[sl]), _ptr(prm.beta_h[sl]), _ptr(ghc[ci]),
+              _ptr(rs_h), _ptr(sc.partials), C.byref(nblk), c0, lnw, st)
+        bn_bwd_finalize(sc.partials, nblk.value, N, w, dev, g["gamma_h"][sl], g["beta_h"][sl])
+    # node side, phase B (gz, Q); edge side, phase A (ge in place, gA3h, the row sums of LNbwd_e, ggamma_e / gbeta_e)
+    gPs, Qs, ges = [], [], []
+    for ci, c0 in enumerate(starts):
+        sl, c = slice(c0, c0 + w), s.chunks[ci]
+        gPc, Q, gec = torch.empty(N, 5 * w, **f32), torch.empty(N, 4 * w, **f32), _cols(ge, c0, w)
+        _call("gnm_ln_wide_node_bwd_apply", N, _ptr(c.z), _ptr(s.stat_h), _ptr(prm.gamma_h[sl]), _ptr(prm.beta_h[sl]), _ptr(ghc[ci]),
+              _ptr(rs_h), _ptr(c.hf), _ptr(c.inv_f), _ptr(c.hb), _ptr(c.inv_b), _ptr(gPc), _ptr(Q), c0, lnw, st)
+        _call("gnm_ln_wide_edge_bwd_sums", N, E, _ptr(c.e_out), _ptr(c.t), _ptr(s.stat_e), _ptr(prm.gamma_e[sl]), _ptr(prm.beta_e[sl]),
+              _ptr(gec), _ptr(c.P), _ptr(Q), _ptr(idx["isrc"]), _ptr(idx["in_ptr"]), _ptr(gPc), _ptr(rs_e), _ptr(sc.partials),
+              C.byref(nblk), c0, lnw, st)
+        bn_bwd_finalize(sc.partials, nblk.value, E, w, dev, g["gamma_e"][sl], g["beta_e"][sl])
+        gPs.append(gPc), Qs.append(Q), ges.append(gec)
+    del ghc
+    # edge side, phase B: gt and gB2h with the whole rows' sums, then the by-source pass (gA2h, gB1h)
+    gP = torch.empty(N, 5 * H, **f32)
+    gt = torch.empty(E, H, **f32)
+    ge_tot = ge if residual else None
+    for ci, c0 in enumerate(starts):
+        sl, c = slice(c0, c0 + w), s.chunks[ci]
+        gtc = torch.empty(E, w, **f32)
+        _call("gnm_ln_wide_edge_bwd_apply", N, E, _ptr(c.t), _ptr(s.stat_e), _ptr(prm.gamma_e[sl]), _ptr(prm.beta_e[sl]), _ptr(ges[ci]),
+              _ptr(rs_e), _ptr(idx["in_ptr"]), _ptr(gtc), _ptr(gPs[ci]), c0, lnw, st)
+        _call("gnm_ln_edge_bwd_src", N, E, w, _ptr(c.e_out), _ptr(gtc), _ptr(Qs[ci]), _ptr(idx["out_ptr"]), _ptr(idx["out_pos"]),
+              _ptr(idx["out_dst"]), _ptr(gPs[ci]), st)
+        _put_cols(gP, gPs[ci], c0, w, 5)
+        _put_cols(gt, gtc, c0, w)
+        if residual:
+            _put_cols(ge_tot, ges[ci], c0, w)
+        gPs[ci] = Qs[ci] = ges[ci] = s.chunks[ci] = None
+    return _wide_backward_tail(N, E, H, Hin, prm, s, gP, gt, ge_tot, gh_out, g, out, residual)
 
 
 def _same_matmul_mode(s) -> None:
@@ -714,6 +844,13 @@ def _wide_layer_backward(idx, N, E, H, prm, s: LayerSaved, gh_out, ge, out, resi
         if residual:
             _put_cols(ge_tot, gec, c0, w)
         s.chunks[ci] = None
+    return _wide_backward_tail(N, E, H, Hin, prm, s, gP, gt, ge_tot, gh_out, g, out, residual)
+
+
+def _wide_backward_tail(N, E, H, Hin, prm, s, gP, gt, ge_tot, gh_out, g, out, residual):
+    """The full-width dense products behind the chunks of a wide layer's backward (either norm): B_3 and the five projections."""
+    f32 = dict(dtype=torch.float32, device=gh_out.device)
+    new = lambda key, *shape: out[key] if key in out else torch.empty(*shape, **f32)  # noqa: E731
     g["W3"] = new("W3", H, Hin)
     g["b3"] = gemm_tn_colsum(gt, s.e_in, g["W3"], out.get("b3"))
     if residual:
@@ -812,6 +949,8 @@ def layer_backward(idx, N: int, E: int, H: int, prm: LayerParams, s: LayerSaved,
     g: Dict[str, torch.Tensor] = {}
     _same_matmul_mode(s)
     if s.chunks is not None:
+        if not batch_norm:
+            return _wide_ln_layer_backward(idx, N, E, H, prm, s, gh_out, ge, out, residual, lnw)
         return _wide_layer_backward(idx, N, E, H, prm, s, gh_out, ge, out, residual, plan)
     if s.P is None or s.t is None:      # "lean" activations: rebuild P and t with the kernels that made them
         s.P, s.t = _proj_and_t(idx, N, E, H, prm, s.h_in, s.e_in, C.c_int(0))
@@ -1508,6 +1647,7 @@ class ModelSaved:
     matmul: str = None
     checkpoint: int = 0          # k > 0: `layers` stays empty, the backward recomputes the stack in segments of k layers ...
     boundaries: list = field(default_factory=list)      # ... from the (h_in, e_in) of every segment's first layer, kept here
+    wide_ln: Optional[bool] = None      # model_forward's wide_ln (LayerNorm above 256 channels): the recomputation runs under the same
 
 
 def _checkpoint_arg(k) -> int:
@@ -1557,9 +1697,9 @@ def layer_params(P: Dict[str, torch.Tensor], i: int) -> LayerParams:
 @on_device_of(lambda graph, e_raw, pe, *a, **k: pe)
 @_scoped()
 def model_forward(graph, e_raw, pe, P: Dict[str, torch.Tensor], num_layers: int, save: bool, batch_norm: bool = True,
-                  ln_width: Optional[int] = None, checkpoint: int = 0):
+                  ln_width: Optional[int] = None, checkpoint: int = 0, wide_ln: Optional[bool] = None):
     """GraphGatedGCNModel.forward.  e_raw [E,edge_features] in edge-id order, pe [N,nb_pos_enc+2].
-    Returns (scores [E,1] in edge-id order, ModelSaved or None).  ln_width: see layer_forward.
+    Returns (scores [E,1] in edge-id order, ModelSaved or None).  ln_width, wide_ln: see layer_forward.
     checkpoint = k > 0 (with save): layer-segment activation checkpointing -- of the layer stack only the (h_in, e_in) entering
     every k-th layer is kept; model_backward re-runs one segment's forward (same kernels, same inputs: the same bits) right
     before that segment's backward.  The scores are those of checkpoint = 0; without `save` it has no effect."""
@@ -1591,6 +1731,8 @@ def model_forward(graph, e_raw, pe, P: Dict[str, torch.Tensor], num_layers: int,
         gemm(NT, e_int, P["linear1_edge.weight"], a1, bias=P["linear1_edge.bias"], relu=True)
         gemm(NT, a1, P["linear2_edge.weight"], e, bias=P["linear2_edge.bias"])
     ms = ModelSaved(pe=pe, e_int=e_int, a1=a1, e_raw=e_raw, opts=current(), matmul=_lib.get_matmul_mode()) if save else None
+    if save:
+        ms.wide_ln = wide_ln        # a checkpointed backward recomputes its layers under the same decision
     plan2 = graph.sweep_plan(dev, GATE2_WG) if (current().TWO_SIDED_FWD and sweep_width(H, batch_norm) and hasattr(graph, "sweep_plan")) else None
     if save and checkpoint:
         ms.checkpoint = checkpoint
@@ -1598,10 +1740,12 @@ def model_forward(graph, e_raw, pe, P: Dict[str, torch.Tensor], num_layers: int,
         for i in range(num_layers):
             if i in firsts:
                 ms.boundaries.append((h, e))
-            h, e, _ = layer_forward(idx, N, E, H, layer_params(P, i), h, e, False, batch_norm, plan=plan2, ln_width=ln_width)
+            h, e, _ = layer_forward(idx, N, E, H, layer_params(P, i), h, e, False, batch_norm, plan=plan2, ln_width=ln_width,
+                                    wide_ln=wide_ln)
     else:
         for i in range(num_layers):
-            h, e, ls = layer_forward(idx, N, E, H, layer_params(P, i), h, e, save, batch_norm, plan=plan2, ln_width=ln_width)
+            h, e, ls = layer_forward(idx, N, E, H, layer_params(P, i), h, e, save, batch_norm, plan=plan2, ln_width=ln_width,
+                                     wide_ln=wide_ln)
             if save:
                 ms.layers.append(ls)
     scores, ps = predictor_forward(idx, N, E, H, P["predictor.W1.weight"], P["predictor.W1.bias"],
@@ -1674,7 +1818,8 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
                 ms.boundaries[si] = None        # the recomputed first layer keeps them until its own backward is done
                 layers = []
                 for i in range(a, b):
-                    h, e, ls = layer_forward(idx, N, E, H, layer_params(P, i), h, e, True, batch_norm, plan=plan2, ln_width=ln_width)
+                    h, e, ls = layer_forward(idx, N, E, H, layer_params(P, i), h, e, True, batch_norm, plan=plan2, ln_width=ln_width,
+                                             wide_ln=ms.wide_ln)
                     layers.append(ls)
                 del h, e, ls
             else:

@@ -30,10 +30,16 @@ if os.environ.get("GNM_RUN_WIDTHS"):        # e.g. GNM_RUN_WIDTHS=128,256 (A/B r
         raise ValueError(f"GNM_RUN_WIDTHS={os.environ['GNM_RUN_WIDTHS']!r}: expected a subset of {KERNEL_WIDTHS}")
 
 
+# LayerNorm layers wider than the widest kernel instantiation: opt-in.  Off (the default), GatedGCN_1d(batch_norm=False) above 256
+# channels raises NotImplementedError as it always did; on (GNM_WIDE_LN=1, or set this attribute before constructing), such a layer
+# runs as 256-column chunks with its row statistics carried across them (engine._wide_ln_layer_forward).  Read at construction.
+WIDE_LAYERNORM = os.environ.get("GNM_WIDE_LN", "0") == "1"
+
+
 def padded_width(width: int) -> int:
     """The kernel width a layer of `width` output channels runs on: itself, or the next one up with dead channels.  Above the widest
-    instantiation a layer runs as 256-column problems between full-width dense products (engine.WIDE_CHUNK: BatchNorm layers; slow
-    by construction, but nn.Linear(in, out) of gated_gcn_full.py:44-50 takes any width and so does this)."""
+    instantiation a layer runs as 256-column problems between full-width dense products (engine.WIDE_CHUNK: BatchNorm layers, and
+    LayerNorm layers under WIDE_LAYERNORM; slow by construction, but nn.Linear(in, out) of gated_gcn_full.py:44-50 takes any width and so does this)."""
     for w in RUN_WIDTHS:
         if width <= w:
             return w
@@ -51,7 +57,8 @@ class _LayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, graph, need, norm, residual, h, e, *flat):
         names = _LAYER_KEYS
-        batch_norm, ln_width = norm           # ln_width: the layer's real out_channels (LayerNorm statistics, engine.layer_forward)
+        batch_norm, ln_width, *wl = norm      # ln_width: the layer's real out_channels (LayerNorm statistics, engine.layer_forward)
+        wide_ln = wl[0] if wl else None       # the layer's WIDE_LAYERNORM decision (GatedGCN_1d._wide_ln)
         P = {"gnn.convs.0." + k: v for k, v in zip(names, flat)}
         idx = graph.index(h.device)
         N, E, H = graph.num_nodes(), graph.num_edges(), flat[0].shape[0]        # H = out_channels (A_1.weight is [out, in])
@@ -59,7 +66,8 @@ class _LayerFn(torch.autograd.Function):
         e_int = e.detach().index_select(0, perm).contiguous()
         prm = engine.layer_params(P, 0)
         h_int = engine.node_rows_in(idx, engine._f32c(h.detach()))       # caller's node numbering -> internal (graph.py)
-        h_out, e_out, saved = engine.layer_forward(idx, N, E, H, prm, h_int, e_int, need, batch_norm, residual, ln_width=ln_width)
+        h_out, e_out, saved = engine.layer_forward(idx, N, E, H, prm, h_int, e_int, need, batch_norm, residual, ln_width=ln_width,
+                                                          wide_ln=wide_ln)
         ctx.graph, ctx.saved, ctx.P, ctx.dims, ctx.bn, ctx.res, ctx.lnw = graph, saved, P, (N, E, H), batch_norm, residual, ln_width
         out_e = torch.empty_like(e_out)
         out_e.index_copy_(0, perm, e_out)
@@ -111,7 +119,8 @@ class GatedGCN_1d(nn.Module):
         super().__init__()
         if not 0 <= dropout < 1:
             raise ValueError(f"GatedGCN_1d: dropout={dropout}")
-        if not batch_norm and out_channels > KERNEL_WIDTHS[-1]:
+        self._wide_ln = bool(WIDE_LAYERNORM)      # recorded here, passed down to the engine with every forward
+        if not batch_norm and out_channels > KERNEL_WIDTHS[-1] and not self._wide_ln:
             raise NotImplementedError(f"GatedGCN_1d(batch_norm=False) at width {out_channels}: the LayerNorm kernels hold a row in one "
                                       f"wavefront (widths up to {KERNEL_WIDTHS[-1]}); BatchNorm layers run at any width")
         self.in_channels, self.out_channels = in_channels, out_channels
@@ -140,7 +149,7 @@ class GatedGCN_1d(nn.Module):
                     F.pad(t, (0, d), value=1.0 if k in ("bn_h.weight", "bn_e.weight") else 0.0) for k, t in zip(_LAYER_KEYS, flat)]
             if di:
                 h, e = F.pad(h, (0, di)), F.pad(e, (0, di))
-        h, e = _LayerFn.apply(g, need, (bool(self.batch_norm), W), self.residual, h, e, *flat)
+        h, e = _LayerFn.apply(g, need, (bool(self.batch_norm), W, self._wide_ln), self.residual, h, e, *flat)
         if Wp != W:
             h, e = h[:, :W], e[:, :W]
         if self.dropout and self.training:

@@ -73,10 +73,10 @@ class _ModelFn(torch.autograd.Function):
         # norm = (batch_norm, real hidden width): LayerNorm statistics run over the model's real width when the kernels
         # run it zero-padded to the next width up (gated_gcn_full.py:58-59: nn.LayerNorm(out_channels)); its third entry is the
         # model's activation_checkpoint (it rides here so that the positional layout backward() counts on stays as it is)
-        batch_norm, ln_width, checkpoint = norm
+        batch_norm, ln_width, checkpoint, *wl = norm       # a fourth entry: the layers' WIDE_LAYERNORM decision (GatedGCN_1d._wide_ln)
         P = {k: v.detach() for k, v in zip(names, flat)}
         scores, saved = engine.model_forward(graph, e.detach(), pe.detach(), P, num_layers, need, batch_norm, ln_width=ln_width,
-                                             checkpoint=checkpoint)
+                                             checkpoint=checkpoint, wide_ln=wl[0] if wl else None)
         ctx.graph, ctx.saved, ctx.P, ctx.names, ctx.L, ctx.bn, ctx.lnw = graph, saved, P, names, num_layers, batch_norm, ln_width
         ctx.params = flat if need else None
         return scores
@@ -160,6 +160,10 @@ class GraphGatedGCNModel(nn.Module):
         earlier then keeps state_dict order and the kernels' stacked gradients are copied instead of written in place)."""
         return flatten_parameters(self)
 
+    def _wide_ln(self) -> bool:
+        """What the layers recorded of layers.WIDE_LAYERNORM when they were built (LayerNorm above 256 channels)."""
+        return all(getattr(c, "_wide_ln", False) for c in self.gnn.convs)
+
     def forward(self, graph, x, e, pe):
         graph = as_assembly_graph(graph, pe.device)       # a DGLGraph(-like) object is wrapped once and cached on itself
         H = self.linear_pe.out_features
@@ -171,14 +175,14 @@ class GraphGatedGCNModel(nn.Module):
             names, flat = zip(*self.named_parameters())
             padded = tuple(_pad_param(k, v, H, Hp) for k, v in zip(names, flat))
             need = torch.is_grad_enabled() and (any(p.requires_grad for p in flat) or e.requires_grad or pe.requires_grad)
-            return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint), *padded)
+            return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint, self._wide_ln()), *padded)
         if pe.is_cuda and not _is_flat(self):
             flatten_parameters(self)          # once per device placement: stacked-parameter views instead of torch.cat
         names, flat = zip(*self.named_parameters())
         # e / pe requiring grad (input attribution, a frozen model, a learnable transform in front of the encoders) also
         # needs the activations: the backward returns their gradients; x stays dead (full_graph.py:23), its .grad None
         need = torch.is_grad_enabled() and (any(p.requires_grad for p in flat) or e.requires_grad or pe.requires_grad)
-        return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint), *flat)
+        return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint, self._wide_ln()), *flat)
 
 
 class _BCEFn(torch.autograd.Function):

@@ -307,6 +307,44 @@ int gnm_ln_edge_bwd_dst(int64_t N, int64_t E, int H, const float* e_out, const f
 int gnm_ln_edge_bwd_src(int64_t N, int64_t E, int H, const float* e_out, const float* gt, const float* Q,
                         const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst,
                         float* gP, void* stream);
+/* LayerNorm layers wider than 256 channels (additive, ABI 7 unchanged).  Such a layer runs zero-padded to Hp = 256 C columns as C
+ * chunks on contiguous [rows,256] copies, like the BatchNorm wide path, but LayerNorm's row statistics span the chunks: they are
+ * formed once per row and handed to the per-chunk kernels, and the two row means of the backward are summed chunk by chunk.
+ * Every per-chunk call takes c0 >= 0, c0 % 4 == 0 (the chunk's first column in the layer) and width >= 1 (the layer's real channel
+ * count): the channels c0 + j >= width are dead.  gamma / beta point at the chunk's 256 entries.  Call the chunks of one phase in
+ * ASCENDING c0 on one stream: c0 == 0 starts a row sum, every later chunk adds to it.  No atomics; bit-reproducible.
+ *
+ * gnm_ln_wide_row_stats: stat[r] = (mean, rstd = 1/sqrt(var + 1e-5)) over the live channels of row r, r < R, whose chunk c is
+ *   x[c * chunk_stride + r * 256 .. + 255] (a [C,R,256] stack: chunk_stride = 256 R).  Centred variance, mean with one correction step.
+ * gnm_ln_wide_edge_gate_fwd / gnm_ln_wide_node_update_fwd: gnm_ln_edge_gate_fwd / gnm_ln_node_update_fwd at H = 256 on one chunk
+ *   with xhat = (x - mean) rstd from stat ([E,2] / [N,2]).  e_in / h_in NULL: no residual.
+ * gnm_ln_wide_node_bwd_sums (phase A): rowsum[v] (+)= (sum a, sum a zhat), a = gamma gh_out [w > 0]; partials = the chunk's
+ *   (sum gw, sum gw zhat) for gnm_bn_bwd_finalize.  gnm_ln_wide_node_bwd_apply (phase B, after phase A of EVERY chunk): gz ->
+ *   gP[:,0:256] of the chunk's [N,1280] and Q [N,1024] = Qf | Rf | Qb | Rb as gnm_ln_node_bwd.
+ * gnm_ln_wide_edge_bwd_sums (phase A): gnm_ln_edge_bwd_dst up to gu -- ge <- ge + gsigma sigma' in place, gP[:,512:768] = gA3h,
+ *   partials (sum gu, sum gu that) -- and rowsum[j] (+)= (sum gamma gu, sum gamma gu that) instead of gt.
+ *   gnm_ln_wide_edge_bwd_apply (phase B, after phase A of EVERY chunk): gt [E,256] and gP[:,1024:1280] = gB2h; then
+ *   gnm_ln_edge_bwd_src (H = 256) for gA2h / gB1h.                      autograd of gated_gcn_full.py:120-152 under nn.LayerNorm */
+int gnm_ln_wide_row_stats(int64_t R, int C, const float* x, int64_t chunk_stride, int width, float* stat, void* stream);
+int gnm_ln_wide_edge_gate_fwd(int64_t N, int64_t E, const float* t, const float* e_in, const float* gamma,
+                              const float* beta, const float* stat, const float* P, const int32_t* isrc,
+                              const int32_t* in_ptr, float* e_out, float* hf, float* inv_f, int c0, int width,
+                              void* stream);
+int gnm_ln_wide_node_update_fwd(int64_t N, const float* z, const float* stat, const float* gamma, const float* beta,
+                                const float* h_in, float* h_out, int c0, int width, void* stream);
+int gnm_ln_wide_node_bwd_sums(int64_t N, const float* z, const float* stat, const float* gamma, const float* beta,
+                              const float* gh_out, float* rowsum, double* partials, int* nblk_out, int c0, int width,
+                              void* stream);
+int gnm_ln_wide_node_bwd_apply(int64_t N, const float* z, const float* stat, const float* gamma, const float* beta,
+                               const float* gh_out, const float* rowsum, const float* hf, const float* inv_f,
+                               const float* hb, const float* inv_b, float* gP, float* Q, int c0, int width, void* stream);
+int gnm_ln_wide_edge_bwd_sums(int64_t N, int64_t E, const float* e_out, const float* t, const float* stat,
+                              const float* gamma, const float* beta, float* ge, const float* P, const float* Q,
+                              const int32_t* isrc, const int32_t* in_ptr, float* gP, float* rowsum, double* partials,
+                              int* nblk_out, int c0, int width, void* stream);
+int gnm_ln_wide_edge_bwd_apply(int64_t N, int64_t E, const float* t, const float* stat, const float* gamma,
+                               const float* beta, const float* ge, const float* rowsum, const int32_t* in_ptr, float* gt,
+                               float* gP, int c0, int width, void* stream);
 /* round 6 (ABI 7), H = 128 with a sweep plan: gnm_ln_edge_bwd_dst + gnm_ln_edge_bwd_src as ONE two-sided sweep (the LayerNorm form of
  * gnm_edge_bwd_top): ge <- ge + gsigma sigma' in place, gt [E,H] written for gnm_edge_bwd_fused_gt, gP[:, H:5H] = gA2h | gA3h | gB1h | gB2h
  * of the nodes the plan serves, partials = (sum gu, sum gu that); then the plan's unserved sources by gathers.  Q = gnm_ln_node_bwd's [N,4H].
