@@ -79,6 +79,10 @@ SIGNATURES = {
     "gnm_node_bgrad": (_i32, [_i64, _i32] + [_p] * 8 + [_i64, _p, _p]),
     "gnm_graph_build_sweep_plan": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i64, _p, _p, _p, C.POINTER(C.c_int64), _pi]),
     "gnm_graph_build_sweep_plan_device": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "gnm_graph_induce_scan_block": (_i32, []),
+    "gnm_graph_induce_workspace_bytes": (_sz, [_i64, _i64]),
+    "gnm_graph_induce_count": (_i32, [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
+    "gnm_graph_induce_fill": (_i32, [_i64, _i64, _i64, _i64] + [_p] * 11 + [_sz] + [_p] * 13 + [_p]),
     "gnm_sweep_partition": (_i32, [_i64, _i32, C.POINTER(C.c_int64), _pi]),
     "gnm_edge_gate2_fwd": (_i32, [_i64, _i64, _i32] + [_p] * 9 + [_i64, _i64] + [_p] * 11 + [_pi, _p]),
     "gnm_ln_edge_gate2_fwd": (_i32, [_i64, _i64, _i32] + [_p] * 4 + [_i32] + [_p] * 6 + [_i64, _i64] + [_p] * 11 + [_pi, _p]),

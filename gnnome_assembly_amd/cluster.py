@@ -105,15 +105,61 @@ def edge_cut(graph: AssemblyGraph, part: np.ndarray) -> int:
     return int(np.count_nonzero(part[graph._src] != part[graph._dst]))
 
 
-def induced_subgraph(graph: AssemblyGraph, node_mask: torch.Tensor) -> AssemblyGraph:
+# How a sub-graph and its index are built: 'sort' (tensor ops: compaction here, two stable sorts in graph.tensor_index) or
+# 'index' (gnm_graph_induce_count / _fill: the parent's index filtered, no sort).  GNM_INDUCE sets the default; unset: 'sort'.
+INDUCE = os.environ.get("GNM_INDUCE", "sort").strip().lower() or "sort"
+INDUCE_METHODS = ("sort", "index")
+
+
+def _induce_method(method: Optional[str]) -> str:
+    method = INDUCE if method is None else method
+    if method not in INDUCE_METHODS:
+        raise ValueError(f"induce method {method!r}: expected one of {INDUCE_METHODS}")
+    return method
+
+
+def induced_subgraph(graph: AssemblyGraph, node_mask: torch.Tensor, method: Optional[str] = None) -> AssemblyGraph:
     """`g.subgraph(nodes)` of DGL: nodes relabelled in ascending original id, induced edges in
     ascending original edge id, ndata / edata rows sliced, original ids in ndata[NID] / edata[EID].
-    Runs on the graph's device (mask, compaction and relabelling are E- and N-sized tensor ops)."""
+    Runs on the graph's device (mask, compaction and relabelling are E- and N-sized tensor ops).
+
+    method 'sort' (default; None: GNM_INDUCE, else 'sort'): the sub-graph's index is built from its edge list when it is first
+    asked for (graph.tensor_index).  'index': the sub-graph AND its index are derived from the parent's device index by
+    gnm_graph_induce_count / gnm_graph_induce_fill (graph.induced_index_from_parent states what they compute): no sort, one
+    host synchronisation; the result is the same graph with `index(dev)` already filled in.  A parent on the CPU has no device
+    index to filter: 'index' then runs 'sort' and says so in `relabel_info` ('induce': 'sort', 'induce_fallback': why)."""
+    method = _induce_method(method)
     dev = graph.device
-    src, dst = graph.edges()
     node_mask = node_mask.to(dev)
     if node_mask.dtype != torch.bool or node_mask.numel() != graph.num_nodes():
         raise ValueError("node_mask must be a bool tensor with one entry per node")
+    if method == "index" and dev.type == "cuda":
+        return _induced_subgraph_index(graph, node_mask)
+    sub = _induced_subgraph_sort(graph, node_mask)
+    if method == "index":
+        sub.relabel_info.update(induce="sort", induce_fallback="the parent graph is on the CPU: no device index to filter")
+    return sub
+
+
+def _induced_subgraph_index(graph: AssemblyGraph, node_mask: torch.Tensor) -> AssemblyGraph:
+    from .graph import induce_index_device
+    dev = graph.device
+    src, dst = graph.edges()
+    nid, eid, s_sub, d_sub, idx = induce_index_device(src, dst, graph.num_nodes(), graph.index(dev), node_mask)
+    sub = AssemblyGraph.from_tensors(s_sub, d_sub, int(nid.numel()), idx.get("nrank"))
+    sub._dev_index[sub.device] = idx            # index(dev) finds it: no tensor_index, the sweep plans are built from this one
+    sub.relabel_info["induce"] = "index"
+    nid, eid = nid.long(), eid.long()           # as torch.nonzero gives them on the other route
+    sub.ndata = {k: v[nid] for k, v in graph.ndata.items()}
+    sub.edata = {k: v[eid] for k, v in graph.edata.items()}
+    sub.ndata[NID] = nid
+    sub.edata[EID] = eid
+    return sub
+
+
+def _induced_subgraph_sort(graph: AssemblyGraph, node_mask: torch.Tensor) -> AssemblyGraph:
+    dev = graph.device
+    src, dst = graph.edges()
     nid = torch.nonzero(node_mask, as_tuple=False).squeeze(1)
     new_id = torch.cumsum(node_mask.to(torch.int32), 0, dtype=torch.int32) - 1
     keep = node_mask[src.long()] & node_mask[dst.long()]
@@ -161,9 +207,10 @@ class ClusterBatchLoader:
     training kernels."""
 
     def __init__(self, graph: AssemblyGraph, part: np.ndarray, batch_size: int, shuffle: bool = True,
-                 generator: Optional[torch.Generator] = None, prefetch: Optional[bool] = None):
+                 generator: Optional[torch.Generator] = None, prefetch: Optional[bool] = None, induce: Optional[str] = None):
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")
+        self.induce = _induce_method(induce)        # how the batches are built (induced_subgraph's method); None: GNM_INDUCE
         self.graph = graph
         self.part = torch.from_numpy(np.ascontiguousarray(part, dtype=np.int32)).to(graph.device)
         self.num_parts = int(part.max()) + 1 if part.size else 0
@@ -184,7 +231,7 @@ class ClusterBatchLoader:
         dev = self.graph.device
         sel = torch.zeros(self.num_parts, dtype=torch.bool, device=dev)
         sel[ids.to(dev)] = True
-        return induced_subgraph(self.graph, sel[self.part.long()])
+        return induced_subgraph(self.graph, sel[self.part.long()], self.induce)
 
     def __iter__(self) -> Iterator[AssemblyGraph]:
         dev = self.graph.device

@@ -74,6 +74,116 @@ def tensor_index(src: torch.Tensor, dst: torch.Tensor, n: int, nrank: torch.Tens
     return idx
 
 
+def _xscan(flags: torch.Tensor) -> torch.Tensor:
+    """exclusive prefix sum of a bool tensor, with the total appended: [len + 1] int64"""
+    out = torch.zeros(flags.numel() + 1, dtype=torch.int64, device=flags.device)
+    torch.cumsum(flags, 0, out=out[1:])
+    return out
+
+
+def induced_index_from_parent(parent_idx, n_parent: int, node_mask: torch.Tensor):
+    """The induced sub-graph of `node_mask` ([n_parent] bool, the caller's numbering) and ITS index, by filtering the parent's
+    index `parent_idx` (the dict of index() / tensor_index) -- no sort: the parent's lists are sorted already, the sub-graph keeps
+    the parent's node order and its edges in ascending edge id, so old node -> new node and old edge -> new edge are monotone
+    and the sub-graph's destination-sorted (by-source) list is the parent's with the dropped entries removed.  Returns
+    (nid, eid, s_sub, d_sub, idx_sub): what cluster.induced_subgraph computes and what tensor_index builds from it, equal
+    element for element.  Tensor ops only; this is the specification of gnm_graph_induce_count / gnm_graph_induce_fill
+    (csrc/gnm_induce.hip), which do the same with flags, five prefix sums and one gather / scatter pass."""
+    L = lambda k: parent_idx[k].long()  # noqa: E731
+    perm, isrc, idst, in_ptr, out_ptr, out_pos = (L(k) for k in ("perm", "isrc", "idst", "in_ptr", "out_ptr", "out_pos"))
+    nrank, nperm = parent_idx.get("nrank"), parent_idx.get("nperm")
+    keepN = node_mask.to(perm.device)
+    if keepN.dtype != torch.bool or keepN.numel() != n_parent:
+        raise ValueError("node_mask must be a bool tensor with one entry per node")
+    e_parent = perm.numel()
+    i32 = lambda t: t.to(torch.int32).contiguous()  # noqa: E731
+    # the edge list in the caller's order and numbering, recovered from the index
+    src = torch.empty(e_parent, dtype=torch.int64, device=perm.device)
+    dst = torch.empty_like(src)
+    src[perm], dst[perm] = isrc, idst
+    if nperm is not None:
+        src, dst = nperm.long()[src], nperm.long()[dst]
+    kI = keepN[nperm.long()] if nperm is not None else keepN      # the mask in internal order
+    newC, newI = _xscan(keepN), _xscan(kI)
+    keepE = keepN[src] & keepN[dst]
+    newE = _xscan(keepE)
+    kP = keepE[perm]                                              # ... in the parent's destination order
+    q = _xscan(kP)
+    kS = kP[out_pos]                                              # ... in the parent's by-source order
+    r = _xscan(kS)
+    n_sub, e_sub = int(newC[-1]), int(newE[-1])
+    nid = torch.nonzero(keepN, as_tuple=False).squeeze(1)
+    eid = torch.nonzero(keepE, as_tuple=False).squeeze(1)
+    s_sub, d_sub = i32(newC[src[eid]]), i32(newC[dst[eid]])
+
+    def scatter(size, where, what):
+        out = torch.empty(size, dtype=torch.int64, device=perm.device)
+        out[where] = what
+        return out
+    pos, by_src, kept_i = q[:-1][kP], r[:-1][kS], newI[:-1][kI]
+    idx = {"perm": scatter(e_sub, pos, newE[perm[kP]]),
+           "isrc": scatter(e_sub, pos, newI[isrc[kP]]),
+           "idst": scatter(e_sub, pos, newI[idst[kP]]),
+           "in_ptr": scatter(n_sub + 1, kept_i, q[in_ptr[:-1][kI]]),
+           "out_ptr": scatter(n_sub + 1, kept_i, r[out_ptr[:-1][kI]]),
+           "out_pos": scatter(e_sub, by_src, q[out_pos[kS]])}
+    idx["in_ptr"][n_sub] = e_sub
+    idx["out_ptr"][n_sub] = e_sub
+    idx["out_dst"] = idx["idst"][idx["out_pos"]]
+    idx = {k: i32(idx[k]) for k in _INDEX_KEYS}
+    if nrank is not None:
+        nrank_sub = scatter(n_sub, newC[:-1][keepN], newI[nrank.long()[keepN]])
+        idx["nrank"] = i32(nrank_sub)
+        idx["nperm"] = i32(scatter(n_sub, nrank_sub, torch.arange(n_sub, device=perm.device)))
+    return nid, eid, s_sub, d_sub, idx
+
+
+def induce_index_device(src: torch.Tensor, dst: torch.Tensor, n_parent: int, parent_idx, node_mask: torch.Tensor):
+    """induced_index_from_parent on the device, by gnm_graph_induce_count / gnm_graph_induce_fill on the current stream: `src` /
+    `dst` the parent's edge list (int32, caller ids), `parent_idx` its index, all on the device of `node_mask` ([n_parent] bool).
+    One host synchronisation: the two sizes.  nid / eid come back as int32."""
+    lib = _lib.load()
+    dev = node_mask.device
+    n, e = int(n_parent), int(src.numel())
+    if n >= 2 ** 31 - 1 or e >= 2 ** 31 - 1:
+        raise _lib.GnmError(f"induce_index_device: N = {n}, E = {e}: the index holds 32-bit positions")
+    if node_mask.dtype != torch.bool or node_mask.numel() != n:
+        raise ValueError("node_mask must be a bool tensor with one entry per node")
+    node_mask = node_mask.contiguous()
+    if node_mask.data_ptr() % 4:
+        node_mask = node_mask.clone()
+    ci = lambda t: t if t.dtype == torch.int32 and t.is_contiguous() else t.to(torch.int32).contiguous()  # noqa: E731
+    src, dst = ci(src), ci(dst)
+    pi = {k: ci(parent_idx[k]) for k in _INDEX_KEYS}
+    nrank, nperm = parent_idx.get("nrank"), parent_idx.get("nperm")
+    if nrank is not None:
+        nrank, nperm = ci(nrank), ci(nperm)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    i32 = dict(dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ws_bytes = int(lib.gnm_graph_induce_workspace_bytes(n, e))
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        sizes = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(lib.gnm_graph_induce_count(n, e, p(src), p(dst), p(node_mask), p(pi["perm"]), p(pi["out_pos"]), p(nperm),
+                                              p(ws), ws_bytes, p(sizes), stream), "gnm_graph_induce_count")
+        n_sub, e_sub = sizes.tolist()                  # the one synchronisation: the sizes are allocation and launch arguments
+        nid, eid, s_sub, d_sub = (torch.empty(m, **i32) for m in (n_sub, e_sub, e_sub, e_sub))
+        idx = {k: torch.empty(n_sub + 1 if k in ("in_ptr", "out_ptr") else e_sub, **i32) for k in _INDEX_KEYS}
+        if nrank is not None:
+            idx["nrank"], idx["nperm"] = torch.empty(n_sub, **i32), torch.empty(n_sub, **i32)
+        _lib.check(lib.gnm_graph_induce_fill(n, e, n_sub, e_sub, p(src), p(dst), *[p(pi[k]) for k in _INDEX_KEYS], p(nrank),
+                                             p(ws), ws_bytes, p(nid), p(eid), p(s_sub), p(d_sub),
+                                             *[p(idx[k]) for k in _INDEX_KEYS], p(idx.get("nrank")), p(idx.get("nperm")), stream),
+                   "gnm_graph_induce_fill")
+    return nid, eid, s_sub, d_sub, idx
+
+
+def induce_scan_block() -> int:
+    """elements per block of the prefix sums of gnm_graph_induce_count (kIndBlk, csrc/gnm_induce.hip)"""
+    return int(_lib.load().gnm_graph_induce_scan_block())
+
+
 class AssemblyGraph:
     @classmethod
     def from_tensors(cls, src: torch.Tensor, dst: torch.Tensor, num_nodes: int, nrank: torch.Tensor = None) -> "AssemblyGraph":

@@ -108,6 +108,34 @@ int gnm_graph_build_sweep_plan_device(const int32_t* isrc, const int32_t* idst, 
  * wg_per_cu: 1 for gnm_edge_bwd_chain_src, 2 for gnm_edge_gate2_fwd (a plan serves ONE partition)            */
 int gnm_sweep_partition(int64_t N, int wg_per_cu, int64_t* nodes_per_block, int* grid_out);
 
+/* ---- the index of an induced sub-graph, derived from its parent's index (additive, ABI 7 unchanged) ----
+ * dgl's g.subgraph(nodes) of the ClusterGCN mini-batches (train.py:288-293): nodes relabelled in ascending id, induced edges in
+ * ascending edge id.  The parent's index (gnm_graph_build_index over its internal node numbering) is sorted already and both
+ * relabellings are monotone, so every array of the sub-graph's index is the parent's with the dropped entries removed and the
+ * kept ones renumbered: flags -> exclusive prefix sums -> gather / scatter.  No sort, no atomics, no allocation; DEVICE pointers,
+ * kernels queued on `stream`.  node_mask [N] bytes (0 = dropped; 4-byte aligned); src / dst [E] the caller's edge list;
+ * perm .. out_dst the parent's index; nperm / nrank: the parent's internal numbering, both NULL when it has none.
+ * induce_count: writes the flags and the five prefix sums (new caller id, new internal id, new edge id, new destination-order
+ *   and new by-source position) into ws (gnm_graph_induce_workspace_bytes(N, E), 16-byte aligned) and sizes[0] = n', sizes[1] = e'
+ *   (device int64): the only two numbers the host has to read.  The prefix sums run over fixed blocks of
+ *   gnm_graph_induce_scan_block() elements in three phases (block sums, one workgroup per sequence over the block sums, apply);
+ *   no workgroup waits for another.  N, E >= 2^31 - 1 are rejected.
+ * induce_fill: with n' and e' from the count on the same stream and ws untouched since, writes nid [n'] / eid [e'] (the kept
+ *   nodes' / edges' ids, ascending), s_sub / d_sub [e'] (their ends, relabelled), the seven index arrays (in_ptr / out_ptr
+ *   [n' + 1], the others [e']) and, when nrank is given, nrank_sub / nperm_sub [n'].  Arrays of length 0 may be NULL.  Sizes
+ *   that are not the count's give wrong numbers but no access outside the arrays as sized by n_sub / e_sub.                */
+int gnm_graph_induce_scan_block(void);
+size_t gnm_graph_induce_workspace_bytes(int64_t N, int64_t E);
+int gnm_graph_induce_count(int64_t N, int64_t E, const int32_t* src, const int32_t* dst, const uint8_t* node_mask,
+                           const int32_t* perm, const int32_t* out_pos, const int32_t* nperm, void* ws, size_t ws_bytes,
+                           int64_t* sizes, void* stream);
+int gnm_graph_induce_fill(int64_t N, int64_t E, int64_t n_sub, int64_t e_sub, const int32_t* src, const int32_t* dst,
+                          const int32_t* perm, const int32_t* isrc, const int32_t* idst, const int32_t* in_ptr,
+                          const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, const int32_t* nrank,
+                          const void* ws, size_t ws_bytes, int32_t* nid, int32_t* eid, int32_t* s_sub, int32_t* d_sub,
+                          int32_t* perm_sub, int32_t* isrc_sub, int32_t* idst_sub, int32_t* in_ptr_sub, int32_t* out_ptr_sub,
+                          int32_t* out_pos_sub, int32_t* out_dst_sub, int32_t* nrank_sub, int32_t* nperm_sub, void* stream);
+
 /* ---- greedy decode (HOST pointers, sequential CPU work; inference.py:31-77,182-253) ----------
  * build_adjacency: successors / predecessors of every node in edge-id order, as the reference's
  *   succ / pred dicts (graph_parser.py:13-73); *_eid[p] = edges[(node, nbr)] of its edges dict, i.e. the

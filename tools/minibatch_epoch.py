@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--shuffle-nodes", action="store_true")
     ap.add_argument("--method", default="locality")
     ap.add_argument("--hidden", type=int, default=128)
+    ap.add_argument("--induce", default=None, choices=["sort", "index"],
+                    help="how the batches are built (cluster.induced_subgraph's method); default: GNM_INDUCE, else sort")
     ap.add_argument("--layers", type=int, default=8)     # --hidden 256 --layers 16: the reference's default model (hyperparameters.py:8,13)
     a = ap.parse_args()
     import gnnome_assembly_amd as G
@@ -63,7 +65,7 @@ def main():
     epochs = []
     torch.cuda.reset_peak_memory_stats()
     for ep in range(a.epochs):
-        loader = cluster.ClusterBatchLoader(g, part, a.batch, shuffle=True, generator=gen)
+        loader = cluster.ClusterBatchLoader(g, part, a.batch, shuffle=True, generator=gen, induce=a.induce)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         seen_e = seen_n = 0
@@ -84,7 +86,7 @@ def main():
                        "edges_per_s": seen_e / dt, "mean_loss": float(torch.stack(losses).mean())})
     res = {"what": "one graph, ClusterGCN mini-batch epochs (train.py:288-343 counterpart), reference settings",
            "reads": a.reads, "nodes": n, "edges": E, "hidden": H, "layers": L, "num_parts": a.parts, "clusters_per_batch": a.batch,
-           "partition_method": a.method, "node_ids": "shuffled" if a.shuffle_nodes else "position-sorted",
+           "partition_method": a.method, "induce": loader.induce, "node_ids": "shuffled" if a.shuffle_nodes else "position-sorted",
            "index_seconds": round(t_index, 3), "partition_seconds": round(t_part, 3), "edge_cut": cut,
            "edge_cut_fraction": cut / E, "edges_kept_per_epoch_fraction": epochs[-1]["edges_in_batches"] / E,
            "epochs": epochs, "peak_mem_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
@@ -93,7 +95,7 @@ def main():
                    "on the device (graph.tensor_index) and run the separate-pass schedule (no sweep plan for device-born graphs)"}
     print(json.dumps(res))
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
-    tag = ("_shuffled" if a.shuffle_nodes else "") + (f"_h{H}l{L}" if (H, L) != (128, 8) else "")
+    tag = ("_shuffled" if a.shuffle_nodes else "") + (f"_h{H}l{L}" if (H, L) != (128, 8) else "") + (f"_{a.induce}" if a.induce else "")
     with open(os.path.join(REPO, "gpurun_out", "minibatch" + tag + ".json"), "w") as f:
         json.dump(res, f, indent=1)
 
