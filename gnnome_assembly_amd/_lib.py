@@ -120,6 +120,8 @@ SIGNATURES = {
     "gnm_pagerank_pe": (_i32, [_i64, _i64, _p, _p, _p, _i32, C.c_double, _p, _p, _sz, _p]),
     "gnm_edge_feats_zscore": (_i32, [_i64, _p, _p, _p, _p, _sz, _p]),
     "gnm_bce_fwd_bwd": (_i32, [_i64, _p, _p, _f32, _p, _p, _p, _sz, _p]),
+    "gnm_bce_stats_workspace_bytes": (_sz, []),
+    "gnm_bce_stats_fwd_bwd": (_i32, [_i64, _p, _p, _f32, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 

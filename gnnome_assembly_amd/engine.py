@@ -1915,5 +1915,28 @@ def bce_with_logits(scores, y, pos_weight: float):
     return loss, gs
 
 
+@on_device_of(lambda scores, *a, **k: scores)
+def bce_with_logits_counts(scores, y, pos_weight: float, need_grad: bool = True, epoch_acc=None):
+    """(loss [1], dloss/dscores [E,1] or None, counts int64 [4] = TP TN FP FN) from one pass (gnm_bce_stats_fwd_bwd): the loss and
+    the gradient are bce_with_logits' bit for bit.  need_grad=False stores no per-edge output.  epoch_acc: 48-byte device records
+    ({double loss_sum; int64 steps; int64 counts[4]} as int64 [6] tensors, train.EpochStats.buf) that the step is added to."""
+    lib = _lib.load()
+    _chk_dev(scores, y)
+    x = _f32c(scores.reshape(-1))
+    y = _f32c(y.reshape(-1))
+    E = x.numel()
+    sc = scratch(x.device)
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    gs = torch.empty(E, 1, dtype=torch.float32, device=x.device) if need_grad else None
+    counts = torch.empty(4, dtype=torch.int64, device=x.device)
+    if epoch_acc is not None:
+        _chk_dev(scores, epoch_acc)
+        if epoch_acc.dtype != torch.int64 or epoch_acc.numel() != 6 or not epoch_acc.is_contiguous():
+            raise ValueError("epoch_acc: a contiguous int64 [6] tensor (train.EpochStats.buf)")
+    _call("gnm_bce_stats_fwd_bwd", E, _ptr(x), _ptr(y), float(pos_weight), _ptr(loss), _ptr(gs), _ptr(counts), _ptr(epoch_acc),
+          _ptr(sc.partials), sc.partials.numel() * 8, _stream())
+    return loss, gs, counts
+
+
 _default = Options(**{k: (globals()["_D_" + k] if k not in ("ACTIVATIONS", "TN_AT") else {"ACTIVATIONS": "saved", "TN_AT": "auto"}[k])
                       for k in _OPTION_NAMES}).replace(ACTIVATIONS=_D_ACTIVATIONS, TN_AT=_D_TN_AT)     # environment values are validated

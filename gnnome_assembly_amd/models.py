@@ -197,6 +197,19 @@ class _BCEFn(torch.autograd.Function):
         return ctx.gs * gl, None, None
 
 
+class _BCECountsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, y, pos_weight, need_grad, epoch_acc):
+        loss, gs, counts = engine.bce_with_logits_counts(scores.detach(), y, pos_weight, need_grad, epoch_acc)
+        ctx.gs = gs.reshape(scores.shape) if need_grad else None
+        ctx.mark_non_differentiable(counts)
+        return loss.reshape(()), counts
+
+    @staticmethod
+    def backward(ctx, gl, _gc):
+        return ctx.gs * gl, None, None, None, None
+
+
 class BCEWithLogitsLoss(nn.Module):
     """torch.nn.BCEWithLogitsLoss(pos_weight=[pw]) with mean reduction as train.py:210-211 uses
     it, as one fused HIP pass that also produces d loss / d logits."""
@@ -207,3 +220,11 @@ class BCEWithLogitsLoss(nn.Module):
 
     def forward(self, scores, y):
         return _BCEFn.apply(scores, y, self.pos_weight)
+
+    def with_counts(self, pred, y, epoch_acc=None):
+        """(loss, counts): forward's loss (same bits, same gradient) and [TP, TN, FP, FN] of round(sigmoid(pred)) against y
+        (train.tfpn_counts) as a device int64 [4] tensor, from the same pass over the logits.  Where no gradient can be asked for
+        (torch.no_grad(), a detached pred) the pass stores no per-edge output.  epoch_acc: a train.EpochStats that the step's
+        loss and counts are added to on the device."""
+        need = torch.is_grad_enabled() and pred.requires_grad
+        return _BCECountsFn.apply(pred, y, self.pos_weight, need, getattr(epoch_acc, "buf", epoch_acc))

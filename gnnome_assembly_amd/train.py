@@ -14,6 +14,8 @@ Differences from the reference, all deliberate:
     package's own partitioner (cluster.py: METIS is part of DGL and not available), otherwise with
     the reference's loop: a fresh partition per graph and epoch with a random number of clusters in
     [num_parts-100, num_parts+100), shuffled batches of clusters, one Adam step per batch;
+  * with the hyper-parameter "fused_metrics" (default: GNM_FUSED_METRICS=1, else off) the loss kernel also counts TP..FN and adds
+    the step to the epoch's sums (BCEWithLogitsLoss.with_counts + EpochStats): same History, no metric launches in the loop;
   * wandb and the data pipeline are out of scope.
 `calculate_metrics` keeps the reference's naming, in which "precision" and "recall" are swapped
 (utils.py:227-234)."""
@@ -30,7 +32,7 @@ import torch.distributed as dist
 
 from . import cluster, dp, models
 
-__all__ = ["get_hyperparameters", "GraphSample", "tfpn_counts", "calculate_metrics", "train", "save_checkpoint"]
+__all__ = ["get_hyperparameters", "GraphSample", "tfpn_counts", "calculate_metrics", "train", "save_checkpoint", "EpochStats"]
 
 
 def get_hyperparameters() -> Dict:
@@ -41,6 +43,8 @@ def get_hyperparameters() -> Dict:
         "batch_size_train": 1, "batch_size_eval": 1, "patience": 2, "decay": 0.95, "batch_norm": True,
         # only read when batch_size_* > 1 (hyperparameters.py:15-18 has 500 / 500 / 50 / 50)
         "num_parts_metis_train": 500, "num_parts_metis_eval": 500, "partition_method": "locality",
+        # loss, TP..FN and the epoch sums from one pass over the logits (criterion.with_counts); same History either way
+        "fused_metrics": os.environ.get("GNM_FUSED_METRICS", "0").strip() == "1",
     }
 
 
@@ -59,6 +63,27 @@ def tfpn_counts(edge_predictions: torch.Tensor, edge_labels: torch.Tensor) -> to
     p = torch.round(torch.sigmoid(edge_predictions))
     return torch.stack([((p == 1) & (edge_labels == 1)).sum(), ((p == 0) & (edge_labels == 0)).sum(),
                         ((p == 1) & (edge_labels == 0)).sum(), ((p == 0) & (edge_labels == 1)).sum()])
+
+
+class EpochStats:
+    """The running sums of an epoch (or of one graph's batches) on the device, in the 48-byte record that
+    BCEWithLogitsLoss.with_counts(..., epoch_acc=self) adds every step to: {double loss_sum; int64 steps; int64 counts[4]}.
+    loss_sum is the fp64 sum of the steps' fp32 losses in call order.  `loss_sum`, `steps` and `counts` are views of `buf`."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(6, dtype=torch.int64, device=device)
+        self.loss_sum = self.buf[0:1].view(torch.float64)[0]
+        self.steps = self.buf[1]
+        self.counts = self.buf[2:6]
+
+    def zero_(self):
+        self.buf.zero_()
+        return self
+
+    def read(self):
+        """(loss_sum, steps, (TP, TN, FP, FN)) with one device-to-host copy."""
+        b = self.buf.cpu()
+        return float(b[0:1].view(torch.float64)[0]), int(b[1]), tuple(int(c) for c in b[2:6].tolist())
 
 
 def calculate_metrics(TP, TN, FP, FN):
@@ -154,6 +179,10 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                  else models.BCEWithLogitsLoss(pos_weight=1.0 / ratio))                         # train.py:210-211
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=hp["decay"],
                                                            patience=hp["patience"])             # train.py:212
+    # one pass for loss + TP..FN + epoch sums; a criterion without with_counts (a criterion_factory stand-in) takes the torch route
+    fused = bool(hp["fused_metrics"]) and hasattr(criterion, "with_counts")
+    if fused:
+        ep_stats, graph_stats = EpochStats(dev), EpochStats(dev)       # the epoch's sums; one graph's batches (mini-batch mode)
     hist = History()
     order = list(range(len(train_samples)))
     model_path = os.path.join(workdir, "pretrained", f"model_{out}.pt")
@@ -163,6 +192,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         loss_sum = torch.zeros((), device=dev, dtype=torch.float64)
         counts = torch.zeros(4, device=dev, dtype=torch.int64)
         ep_losses = []                       # device scalars; read back once per epoch
+        if fused:
+            ep_stats.zero_()
         # every rank takes the same number of optimizer steps: shards may be uneven (dp.shard_graphs), the
         # shorter ranks pad with zero-contribution steps so that the gradient collectives stay matched
         nsteps = dp.steps_per_epoch(len(order), dev)
@@ -172,13 +203,16 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                 flat.zero_()
                 if s is not None:
                     pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)                           # train.py:252-253
-                    loss = criterion(pred, s.y)
+                    loss = criterion.with_counts(pred, s.y, ep_stats)[0] if fused else criterion(pred, s.y)
                     loss.backward()
                 flat.all_reduce_mean(contributed=s is not None)
                 if "after_exchange" in hooks:
                     hooks["after_exchange"](epoch, it, flat)
                 optimizer.step()                                                                # train.py:256-258
-                if s is not None:
+                if s is not None and fused:              # the loss kernel has added the step to ep_stats
+                    ep_losses.append(loss.detach())
+                    hist.step_graph.append(order[it])
+                elif s is not None:
                     loss_sum += loss.detach().double()
                     ep_losses.append(loss.detach())
                     hist.step_graph.append(order[it])
@@ -191,21 +225,29 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                 loader = _cluster_batches(s, nparts, hp["batch_size_train"], hp["partition_method"]) if s is not None else []
                 nbatches = dp.steps_per_epoch(len(loader), dev)          # the ranks' cluster counts differ
                 batches = iter(loader)
+                if fused:
+                    graph_stats.zero_()
                 for _ in range(nbatches):
                     sub = next(batches, None)
                     flat.zero_()
                     if sub is not None:
                         pred = model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1)    # train.py:306
-                        loss = criterion(pred, sub.edata["y"])
+                        loss = (criterion.with_counts(pred, sub.edata["y"], graph_stats)[0] if fused
+                                else criterion(pred, sub.edata["y"]))
                         loss.backward()
                     flat.all_reduce_mean(contributed=sub is not None)
                     optimizer.step()
-                    if sub is not None:
+                    if sub is not None and not fused:
                         gl += loss.detach().double()
                         nb += 1
                         counts += tfpn_counts(pred.detach(), sub.edata["y"])
-                if s is not None:
+                if s is not None and fused:              # once per graph, on the device: the mean of its batches, its counts
+                    loss_sum += graph_stats.loss_sum / graph_stats.steps.clamp(min=1)
+                    counts += graph_stats.counts
+                elif s is not None:
                     loss_sum += gl / max(nb, 1)                                                 # train.py:330
+        if fused and hp["batch_size_train"] <= 1:
+            loss_sum, counts = ep_stats.loss_sum.clone(), ep_stats.counts.clone()
         n_train = torch.tensor(float(len(order)), device=dev, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(loss_sum); dist.all_reduce(n_train); dist.all_reduce(counts)        # noqa: E702
@@ -219,12 +261,24 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         model.eval()
         vloss = torch.zeros((), device=dev, dtype=torch.float64)
         vcounts = torch.zeros(4, device=dev, dtype=torch.int64)
+        if fused:
+            ep_stats.zero_()
         with torch.no_grad():
             for s in valid_samples:
-                if hp["batch_size_eval"] <= 1:
+                if hp["batch_size_eval"] <= 1 and fused:
+                    criterion.with_counts(model(s.graph, s.x, s.e, s.pe).squeeze(-1), s.y, ep_stats)
+                elif hp["batch_size_eval"] <= 1:
                     pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)
                     vloss += criterion(pred, s.y).double()
                     vcounts += tfpn_counts(pred, s.y)
+                elif fused:
+                    graph_stats.zero_()
+                    for sub in _cluster_batches(s, hp["num_parts_metis_eval"], hp["batch_size_eval"],
+                                                hp["partition_method"]):
+                        criterion.with_counts(model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1), sub.edata["y"],
+                                              graph_stats)
+                    vloss += graph_stats.loss_sum / graph_stats.steps.clamp(min=1)
+                    vcounts += graph_stats.counts
                 else:                                                                           # train.py:428-486
                     gl = torch.zeros((), device=dev, dtype=torch.float64)
                     nb = 0
@@ -235,6 +289,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                         nb += 1
                         vcounts += tfpn_counts(pred, sub.edata["y"])
                     vloss += gl / max(nb, 1)
+        if fused and hp["batch_size_eval"] <= 1:
+            vloss, vcounts = ep_stats.loss_sum.clone(), ep_stats.counts.clone()
         n_val = torch.tensor(float(len(valid_samples)), device=dev, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(vloss); dist.all_reduce(n_val); dist.all_reduce(vcounts)            # noqa: E702

@@ -597,6 +597,21 @@ int gnm_edge_feats_zscore(int64_t E, const float* overlap_length, const float* o
  * ws: double[gnm_max_partial_blocks()] */
 int gnm_bce_fwd_bwd(int64_t E, const float* scores, const float* y, float pos_weight,
                     float* loss_out, float* gscore, void* ws, size_t ws_bytes, void* stream);
+/* The same loss and gradient (bit for bit: same per-element arithmetic, grid and summation order) with the step's metric
+ * counts and the epoch's running sums from the same pass over the logits (utils.calculate_tfpn, utils.py:217-223;
+ * train.py:259-262 epoch sums).
+ * counts_out[4] = TP TN FP FN (overwritten) of p = round(sigmoid(x)), half to even, against y: p == 1 exactly when x >= 0x1.800002p-24
+ *             (the smallest fp32 logit whose fp32 sigmoid exceeds 0.5), p == 0 when x is below it; a NaN logit and a label that is
+ *             neither 0 nor 1 are counted nowhere, as in torch.
+ * gscore:     NULL under no_grad: no per-edge output is stored.
+ * epoch_acc:  NULL, or a device {double loss_sum; int64_t steps; int64_t counts[4]} (48 bytes, 8-byte aligned) that the call ADDS
+ *             to: loss_out[0] widened to double, 1, the four counts.  Calls on one stream add in call order.
+ * ws:         gnm_bce_stats_workspace_bytes() bytes, 16-byte aligned; its previous content is not read.  No atomics: two runs
+ *             give the same bits.  E must be positive, as for gnm_bce_fwd_bwd.                                                  */
+size_t gnm_bce_stats_workspace_bytes(void);
+int gnm_bce_stats_fwd_bwd(int64_t E, const float* scores, const float* y, float pos_weight,
+                          float* loss_out, float* gscore, int64_t* counts_out, void* epoch_acc,
+                          void* ws, size_t ws_bytes, void* stream);
 
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:

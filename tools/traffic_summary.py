@@ -17,6 +17,8 @@ for c, key, nk in (("FETCH_SIZE", "fetch_kib", "n_f"), ("WRITE_SIZE", "write_kib
         k = r["Kernel_Name"].split("(")[0].replace("void gnm::", "").replace("gnm::", "")
         if k.startswith("edge_bwd_chain_k"):
             k = "edge_bwd_chain_k"
+        if k.startswith("bce_fwd_bwd_k"):        # bce_fwd_bwd_k<false> / <true> (with the metric counts): one per step either way
+            k = "bce_fwd_bwd_k"
         res[k][key] += float(r["Counter_Value"])
         res[k][nk] += 1
 table = {}
