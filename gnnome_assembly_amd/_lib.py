@@ -16,6 +16,8 @@ _i64 = C.c_int64
 _i32 = C.c_int
 _f32 = C.c_float
 _sz = C.c_size_t
+_u64 = C.c_uint64
+_u32 = C.c_uint32
 _pi = C.POINTER(C.c_int)
 
 # name -> (restype, argtypes); must list every symbol include/gnm.h declares
@@ -122,6 +124,8 @@ SIGNATURES = {
     "gnm_bce_fwd_bwd": (_i32, [_i64, _p, _p, _f32, _p, _p, _p, _sz, _p]),
     "gnm_bce_stats_workspace_bytes": (_sz, []),
     "gnm_bce_stats_fwd_bwd": (_i32, [_i64, _p, _p, _f32, _p, _p, _p, _p, _p, _sz, _p]),
+    "gnm_node_dropout_apply": (_i32, [_i64, _i32, _i64, _p, _p, _p, C.c_double, _u64, _u32, _i32, _p]),
+    "gnm_node_dropout_mask": (_i32, [_i64, _i32, _p, _p, C.c_double, _u64, _u32, _i32, _p]),
 }
 
 

@@ -15,7 +15,7 @@ from typing import Iterable, Optional
 import torch
 import torch.distributed as dist
 
-__all__ = ["init_process_group", "FlatGradients", "shard_graphs", "steps_per_epoch", "fresh_flat_gradients"]
+__all__ = ["init_process_group", "FlatGradients", "shard_graphs", "steps_per_epoch", "fresh_flat_gradients", "current_rank"]
 
 _live = weakref.WeakSet()      # the FlatGradients objects alive in this process
 # GNM_FORCE_COLLECTIVE=1: do not skip the collectives at world size 1 (lets a 1-GPU box execute the RCCL path end to end)
@@ -35,6 +35,12 @@ def fresh_flat_gradients(params) -> "Optional[FlatGradients]":
                 return None
             return fg
     return None
+
+
+def current_rank() -> int:
+    """This process's data-parallel rank (0 outside torch.distributed): what engine.dropout_key folds into the dropout seed, so
+    that the ranks of a step draw different masks from one user seed."""
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
 def init_process_group(backend: str | None = None):

@@ -125,6 +125,8 @@ def _scoped(saved_arg: Optional[int] = None):
             if opts is None and saved_arg is not None and len(a) > saved_arg:
                 opts = getattr(a[saved_arg], "opts", None)
                 scoped = getattr(_tls, "opts", None)
+                if scoped is not None and getattr(a[saved_arg], "dropout", None) is not None:
+                    scoped = _dropout_opts(scoped)      # what a forward with dropout saves of them: no difference to warn about
                 if opts is not None and scoped is not None and scoped is not opts and repr(scoped) != repr(opts):
                     # `with engine.options(...)` around a backward only: the saved forward options win (the backward kernels must
                     # match the activations the forward kept) -- say so instead of silently comparing two identical paths
@@ -444,6 +446,109 @@ def node_rows_out(idx, x: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(x)
     _call("gnm_gather_rows_f32", x.shape[0], x.shape[1], _ptr(x), _ptr(nrank), _ptr(out), _stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# node-output dropout of the layer stack (gated_gcn_full.py:154): counter-based masks, nothing stored (gnm_dropout.hip)
+# ---------------------------------------------------------------------------------------
+# A pass takes dropout=(p, key, step): the keep decision of (layer, caller's node id, channel) is a pure function of those, so the
+# backward, a checkpoint recomputation and a test all re-derive the mask the forward used.  p = 0 / None: no launch, nothing changes.
+_M64 = (1 << 64) - 1
+DROPOUT_RANK_MIX = 0x9E3779B97F4A7C15       # the key of data-parallel rank r is seed ^ r * this (mod 2^64)
+_dropout_state: Dict[torch.device, list] = {}       # device -> [seed, step]: the stream the MODULES draw (key, step) from
+
+
+def dropout_p(p) -> float:
+    """A module's dropout argument as a float in [0, 1), or ValueError (what GatedGCN_1d raises)."""
+    try:
+        ok = 0 <= p < 1
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"dropout={p!r}: expected a probability 0 <= p < 1")
+    return float(p)
+
+
+def dropout_key(seed: int, rank: Optional[int] = None) -> int:
+    """The 64-bit Philox key of a data-parallel rank: seed ^ rank * 0x9E3779B97F4A7C15 (rank None: this process's, dp.current_rank)."""
+    if rank is None:
+        from . import dp
+        rank = dp.current_rank()
+    return (int(seed) ^ (int(rank) * DROPOUT_RANK_MIX)) & _M64
+
+
+def _dropout_dev(device) -> torch.device:
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    return torch.device("cuda", torch.cuda.current_device()) if device.type == "cuda" and device.index is None else device
+
+
+def dropout_seed(seed: int, step: int = 0, device=None) -> None:
+    """Set the seed of `device`'s dropout stream (default: the current device) and restart its step counter at `step`: the
+    forwards that follow draw the masks they drew after the same call before.  Without a call the seed is torch.initial_seed()
+    at the first training forward with p > 0."""
+    _dropout_state[_dropout_dev(device)] = [int(seed) & _M64, int(step) & 0xFFFFFFFF]
+
+
+def dropout_draw(p: float, device=None):
+    """(p, key, step) for ONE training forward with p > 0 on `device`: the key of this rank, the step counter's value, which
+    is then incremented (32 bits, wrapping)."""
+    st = _dropout_state.setdefault(_dropout_dev(device), [torch.initial_seed() & _M64, 0])
+    step = st[1]
+    st[1] = (step + 1) & 0xFFFFFFFF
+    return (float(p), dropout_key(st[0]), step)
+
+
+def _dropout_arg(dropout):
+    """A pass's `dropout` argument as (p, key, step) with p > 0, or None (no dropout)."""
+    if dropout is None:
+        return None
+    p, key, step = dropout
+    p = dropout_p(p)
+    return (p, int(key) & _M64, int(step) & 0xFFFFFFFF) if p > 0 else None
+
+
+@on_device_of(lambda x, *a, **k: x)
+def node_dropout(x: torch.Tensor, dropout, layer: int, width: Optional[int] = None, node_ids: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mask * x / (1 - p) of layer `layer`'s node rows x [N, ld] (gnm_node_dropout_apply), IN PLACE unless `out` (same shape) is
+    given.  width: the model's real width when x is zero-padded to a kernel width (columns width .. ld-1 are left alone).
+    node_ids: caller's node id of each row (int32 [N]: the index's 'nperm'); None: the row number.  Its own backward."""
+    drop = _dropout_arg(dropout)
+    y = x if out is None else out
+    _chk_dev(x, y, node_ids)
+    if (x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32 or y.shape != x.shape or y.dtype != x.dtype
+            or y.stride() != x.stride()):
+        raise _lib.GnmError("node_dropout: x (and out) must be 2-D float32 with unit inner stride and the same layout")
+    if node_ids is not None and (node_ids.dtype != torch.int32 or node_ids.numel() != x.shape[0] or not node_ids.is_contiguous()):
+        raise _lib.GnmError("node_dropout: node_ids must be a contiguous int32 [N] tensor")
+    if drop is None:
+        return y if out is None else y.copy_(x)
+    H = x.shape[1] if width is None else int(width)
+    _call("gnm_node_dropout_apply", x.shape[0], H, x.stride(0), _ptr(x), _ptr(y), _ptr(node_ids), drop[0], drop[1], drop[2], int(layer),
+          _stream())
+    return y
+
+
+def dropout_mask(N: int, H: int, dropout, layer: int, device, node_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The keep decisions node_dropout takes, as a uint8 [N,H] tensor (gnm_node_dropout_mask).  node_ids None: row v is the
+    caller's node v -- the mask of a model's layer in the caller's numbering, whatever the graph's internal order."""
+    drop = _dropout_arg(dropout)
+    if drop is None:
+        raise _lib.GnmError("dropout_mask: p = 0 has no mask")
+    _chk_dev(node_ids)
+    if node_ids is not None and (node_ids.dtype != torch.int32 or node_ids.numel() != N or not node_ids.is_contiguous()):
+        raise _lib.GnmError("dropout_mask: node_ids must be a contiguous int32 [N] tensor")
+    with torch.cuda.device(device):
+        mask = torch.empty(N, H, dtype=torch.uint8, device=device)
+        _call("gnm_node_dropout_mask", N, H, _ptr(mask), _ptr(node_ids), drop[0], drop[1], drop[2], int(layer), _stream())
+    return mask
+
+
+def _dropout_opts(o: "Options") -> "Options":
+    """The switches a pass with p > 0 runs under: the gradient entering a layer's node backward must exist as a finished [N,H]
+    tensor, so the one schedule that consumes it inside a matrix kernel's epilogue is pinned off -- NODE_FUSED (the projection
+    backward that also takes the BatchNorm_h backward sums of the layer below: gnm_node_proj_bwd_nn_stats)."""
+    return o.replace(NODE_FUSED=False) if o.NODE_FUSED else o
 
 
 # ---------------------------------------------------------------------------------------
@@ -1145,7 +1250,7 @@ def chain_eligible(H: int, batch_norm: bool) -> bool:
 
 def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tensor], L: int, saved: List[LayerSaved],
                             gh, ge, outs: List[Optional[Dict[str, torch.Tensor]]], plan: Optional[dict] = None,
-                            lane: Optional[SideLane] = None, first: int = 0):
+                            lane: Optional[SideLane] = None, first: int = 0, mask=None):
     """Backward of the L-layer stack (layers L-1 .. 0), same arithmetic as L x layer_backward, other schedule:
         node(L-1), dst(L-1);   then for i = L-1 .. 0:   finalize_e(i), src(i), proj(i),
                                                          i > 0:  node(i-1), CHAIN[fused(i) + dst(i-1)]
@@ -1156,7 +1261,10 @@ def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tens
     fix(i) [right after CHAIN(i+1, i)] + bgrad(i) [after finalize_e(i)].  With `lane` the node-projection weight gradients run on
     its side stream (TN_AT, TN_SPLIT say when); the caller drains it.
     first: the stack is the model's layers first .. first+L-1 (a checkpoint segment: `saved` and `outs` hold those L layers, the
-    parameters are read at the offset); its top layer is treated like a model's top layer, its bottom layer like layer 0."""
+    parameters are read at the offset); its top layer is treated like a model's top layer, its bottom layer like layer 0.
+    mask (node-output dropout, p > 0): mask(layer, gh) applies that model layer's dropout mask to the gradient of its output IN
+    PLACE; every layer's node backward is preceded by it.  Not with NODE_FUSED, which forms the BatchNorm_h backward sums of the
+    unmasked gradient inside the projection backward (model_forward pins it off: _dropout_opts)."""
     lib = _lib.load()
     dev = gh.device
     sc, sc2 = scratch(dev), scratch(dev, "chain")     # sc2: the chained kernel's second partials buffer
@@ -1184,6 +1292,8 @@ def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tens
         o = outs[i] or {}
         gP = torch.empty(N, 5 * H, **f32)
         Q = torch.empty(N, 2 * H, **f32)
+        if mask is not None:
+            mask(first + i, gh_out)
         if nblk_h is None:
             nblk_h = C.c_int(0)
             _call("gnm_node_bwd_stats", N, H, _ptr(s.z), _ptr(s.stat_h), _ptr(gh_out), _ptr(sc.partials), C.byref(nblk_h), st)
@@ -1221,6 +1331,9 @@ def layers_backward_chained(idx, N: int, E: int, H: int, P: Dict[str, torch.Tens
         s.P = None              # as below: only the by-destination pass reads the rebuilt P
     # not in the lean mode: the deferred kernel keeps its gP (one [E,H]-sized tensor) alive one layer longer
     fusedn = current().NODE_FUSED and plan is not None      # the node side without node_bgrad / node_bwd_stats launches (see NODE_FUSED)
+    if fusedn and mask is not None:
+        raise _lib.GnmError("node-output dropout cannot run under NODE_FUSED (the projection backward would take the BatchNorm_h "
+                            "backward sums of the unmasked gradient): run the backward under the options its forward saved")
     at_now = tn_at(N) == "now"          # when the deferred weight-gradient kernel is launched (TN_AT; "auto": by graph size)
     pending = None              # (gP, h_in, gW5, gb5) of the layer above: its weight-gradient kernel, not yet launched
     pending2 = None             # the same, when only its first launch (TN_SPLIT) has been issued
@@ -1354,7 +1467,7 @@ def ln_chain_eligible(H: int, batch_norm: bool) -> bool:
 
 def layers_backward_chained_ln(idx, N: int, E: int, H: int, P: Dict[str, torch.Tensor], L: int, saved: List[LayerSaved], gh, ge,
                                outs: List[Optional[Dict[str, torch.Tensor]]], plan: dict, lnw: int, lane: Optional[SideLane] = None,
-                               first: int = 0):
+                               first: int = 0, mask=None):
     """Backward of an L-layer LayerNorm stack (batch_norm=False), chained like layers_backward_chained.  LayerNorm has no global
     statistics, so the schedule is shorter than BatchNorm's -- no finalisation between a layer's passes, no conversion of raw sums:
         node(L-1), sweep(L-1) [+ fix];   then for i = L-1 .. 0:   nn(i), tn(i) [side stream],
@@ -1362,7 +1475,7 @@ def layers_backward_chained_ln(idx, N: int, E: int, H: int, P: Dict[str, torch.T
                                               i = 0:  fused(0) with gt(0) given
     The sweep of layer i writes gt(i) once; the chained kernel of the next iteration reads it back as layer i's given gt (6 [E,H]
     streams per layer where the layer-by-layer schedule moves 9).  Returns (gh_in of layer 0, ge_in of layer 0, [grads dict per layer]).
-    With `lane` tn(i) runs on its side stream; the caller drains it.  first: as in layers_backward_chained."""
+    With `lane` tn(i) runs on its side stream; the caller drains it.  first, mask: as in layers_backward_chained."""
     lib = _lib.load()
     dev = gh.device
     sc, sc2 = scratch(dev), scratch(dev, "chain")
@@ -1392,6 +1505,8 @@ def layers_backward_chained_ln(idx, N: int, E: int, H: int, P: Dict[str, torch.T
         gP = torch.empty(N, 5 * H, **f32)
         Q = torch.empty(N, 4 * H, **f32)
         nb = C.c_int(0)
+        if mask is not None:
+            mask(first + i, gh_out)
         _call("gnm_ln_node_bwd", N, H, _ptr(s.z), _ptr(prm.gamma_h), _ptr(prm.beta_h), _ptr(gh_out), _ptr(s.hf),
               _ptr(s.inv_f), _ptr(s.hb), _ptr(s.inv_b), _ptr(gP), _ptr(Q), _ptr(sc.partials), C.byref(nb), lnw, st)
         _, grads[i]["gamma_h"], grads[i]["beta_h"] = bn_bwd_finalize(sc.partials, nb.value, N, H, dev, o.get("gamma_h"), o.get("beta_h"))
@@ -1648,6 +1763,7 @@ class ModelSaved:
     checkpoint: int = 0          # k > 0: `layers` stays empty, the backward recomputes the stack in segments of k layers ...
     boundaries: list = field(default_factory=list)      # ... from the (h_in, e_in) of every segment's first layer, kept here
     wide_ln: Optional[bool] = None      # model_forward's wide_ln (LayerNorm above 256 channels): the recomputation runs under the same
+    dropout: Optional[tuple] = None     # (p, key, step) of the forward's node-output dropout (p > 0), or None: the backward's masks
 
 
 def _checkpoint_arg(k) -> int:
@@ -1697,13 +1813,22 @@ def layer_params(P: Dict[str, torch.Tensor], i: int) -> LayerParams:
 @on_device_of(lambda graph, e_raw, pe, *a, **k: pe)
 @_scoped()
 def model_forward(graph, e_raw, pe, P: Dict[str, torch.Tensor], num_layers: int, save: bool, batch_norm: bool = True,
-                  ln_width: Optional[int] = None, checkpoint: int = 0, wide_ln: Optional[bool] = None):
+                  ln_width: Optional[int] = None, checkpoint: int = 0, wide_ln: Optional[bool] = None, dropout=None):
     """GraphGatedGCNModel.forward.  e_raw [E,edge_features] in edge-id order, pe [N,nb_pos_enc+2].
     Returns (scores [E,1] in edge-id order, ModelSaved or None).  ln_width, wide_ln: see layer_forward.
     checkpoint = k > 0 (with save): layer-segment activation checkpointing -- of the layer stack only the (h_in, e_in) entering
     every k-th layer is kept; model_backward re-runs one segment's forward (same kernels, same inputs: the same bits) right
-    before that segment's backward.  The scores are those of checkpoint = 0; without `save` it has no effect."""
+    before that segment's backward.  The scores are those of checkpoint = 0; without `save` it has no effect.
+    dropout = (p, key, step) with p > 0: every layer's node output (the last layer's included) is dropped IN PLACE right behind
+    the layer (gated_gcn_full.py:154) with the mask of (key, step, layer, caller's node id, channel) -- no backward kernel reads
+    the undropped rows -- and the saved state carries the triple for the backward and the recomputation.  None / p = 0: no launch."""
     checkpoint = _checkpoint_arg(checkpoint)
+    drop = _dropout_arg(dropout)
+    if drop is not None and _dropout_opts(current()) is not current():
+        # p > 0: the whole pass -- what it saves per layer included -- under the pinned switches (see _dropout_opts)
+        with use(_dropout_opts(current())):
+            return model_forward(graph, e_raw, pe, P, num_layers, save, batch_norm, ln_width=ln_width, checkpoint=checkpoint,
+                                 wide_ln=wide_ln, dropout=drop)
     lib = _lib.load()
     dev = pe.device
     _chk_dev(e_raw, pe)
@@ -1733,6 +1858,9 @@ def model_forward(graph, e_raw, pe, P: Dict[str, torch.Tensor], num_layers: int,
     ms = ModelSaved(pe=pe, e_int=e_int, a1=a1, e_raw=e_raw, opts=current(), matmul=_lib.get_matmul_mode()) if save else None
     if save:
         ms.wide_ln = wide_ln        # a checkpointed backward recomputes its layers under the same decision
+    if save and drop is not None:
+        ms.dropout = drop           # the backward's and the recomputation's masks
+    real_w = H if ln_width is None else int(ln_width)               # the mask function's H: the model's real width
     plan2 = graph.sweep_plan(dev, GATE2_WG) if (current().TWO_SIDED_FWD and sweep_width(H, batch_norm) and hasattr(graph, "sweep_plan")) else None
     if save and checkpoint:
         ms.checkpoint = checkpoint
@@ -1742,10 +1870,14 @@ def model_forward(graph, e_raw, pe, P: Dict[str, torch.Tensor], num_layers: int,
                 ms.boundaries.append((h, e))
             h, e, _ = layer_forward(idx, N, E, H, layer_params(P, i), h, e, False, batch_norm, plan=plan2, ln_width=ln_width,
                                     wide_ln=wide_ln)
+            if drop is not None:
+                node_dropout(h, drop, i, real_w, idx.get("nperm"))
     else:
         for i in range(num_layers):
             h, e, ls = layer_forward(idx, N, E, H, layer_params(P, i), h, e, save, batch_norm, plan=plan2, ln_width=ln_width,
                                      wide_ln=wide_ln)
+            if drop is not None:
+                node_dropout(h, drop, i, real_w, idx.get("nperm"))
             if save:
                 ms.layers.append(ls)
     scores, ps = predictor_forward(idx, N, E, H, P["predictor.W1.weight"], P["predictor.W1.bias"],
@@ -1798,6 +1930,14 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
     G["predictor.W2.weight"], G["predictor.W2.bias"] = gp["W2"], gp["b2"]
     ms.pred = None
     louts = [grad_targets(out, i) if out else None for i in range(num_layers)]
+    # node-output dropout: the gradient of layer i's output passes through layer i's mask, in place, before its node backward
+    mask = None
+    if ms.dropout is not None:
+        if current().NODE_FUSED:        # an explicit opts= that undoes the forward's pin: see _dropout_opts
+            raise _lib.GnmError("model_backward: a forward with node-output dropout cannot be followed by a backward under "
+                                "NODE_FUSED; run it under the options the forward saved (ms.opts)")
+        real_w, nperm = (H if ln_width is None else int(ln_width)), idx.get("nperm")
+        mask = lambda layer, g: node_dropout(g, ms.dropout, layer, real_w, nperm)       # noqa: E731
     # layer-by-layer backward on the two-sided sweep (the chained schedule's top-layer kernel for every layer): H = 256, and H = 128
     # where the chained schedule does not apply (fp32-MFMA matmul mode, GNM_CHAIN=0)
     plan_w = graph.sweep_plan(dev) if (sweep_width(H, batch_norm) and current().TWO_SIDED and not chain_eligible(H, batch_norm)
@@ -1821,17 +1961,21 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
                     h, e, ls = layer_forward(idx, N, E, H, layer_params(P, i), h, e, True, batch_norm, plan=plan2, ln_width=ln_width,
                                              wide_ln=ms.wide_ln)
                     layers.append(ls)
+                    if mask is not None and i < b - 1:      # what the next layer of the segment reads (and keeps as its h_in)
+                        mask(i, h)
                 del h, e, ls
             else:
                 layers = ms.layers
             if chain_eligible(H, batch_norm):
                 plan = graph.sweep_plan(dev) if current().TWO_SIDED and hasattr(graph, "sweep_plan") else None
-                gh, ge, grads[a:b] = layers_backward_chained(idx, N, E, H, P, b - a, layers, gh, ge, louts[a:b], plan, lane, first=a)
+                gh, ge, grads[a:b] = layers_backward_chained(idx, N, E, H, P, b - a, layers, gh, ge, louts[a:b], plan, lane, first=a, mask=mask)
             elif ln_chain_eligible(H, batch_norm) and plan_w is not None:
                 gh, ge, grads[a:b] = layers_backward_chained_ln(idx, N, E, H, P, b - a, layers, gh, ge, louts[a:b], plan_w,
-                                                                H if ln_width is None else int(ln_width), lane, first=a)
+                                                                H if ln_width is None else int(ln_width), lane, first=a, mask=mask)
             else:
                 for i in reversed(range(a, b)):
+                    if mask is not None:
+                        mask(i, gh)
                     gh, ge, grads[i] = layer_backward(idx, N, E, H, layer_params(P, i), layers[i - a], gh, ge, batch_norm, louts[i],
                                                       plan=plan_w, ln_width=ln_width, lane=lane)
                     layers[i - a] = None    # release this layer's activations
@@ -1897,6 +2041,52 @@ def model_backward(graph, P: Dict[str, torch.Tensor], num_layers: int, ms: Model
             g_e_raw = torch.empty_like(g_int)
             _call("gnm_gather_rows_f32", E, g_int.shape[1], _ptr(g_int), _ptr(edge_rank(idx)), _ptr(g_e_raw), _stream())
     return (G, g_e_raw, g_pe) if inputs else G
+
+
+# ---------------------------------------------------------------------------------------
+# the layer stack alone (processor.py:15-20): what layers.GraphGatedGCN runs when its node-output dropout is on
+# ---------------------------------------------------------------------------------------
+
+@dataclass
+class StackSaved:
+    layers: List[LayerSaved] = field(default_factory=list)
+    dropout: Optional[tuple] = None
+    opts: "Options" = None
+
+
+@on_device_of(lambda idx, N, E, H, P, num_layers, h, *a, **k: h)
+@_scoped()
+def stack_forward(idx, N: int, E: int, H: int, P: Dict[str, torch.Tensor], num_layers: int, h, e, save: bool, batch_norm: bool = True,
+                  ln_width: Optional[int] = None, wide_ln: Optional[bool] = None, dropout=None):
+    """GraphGatedGCN.forward on internal-order tensors h [N,H], e [E,H] (P: 'gnn.convs.<i>.' keys as in model_forward): layer
+    after layer, each node output through node_dropout (dropout = (p, key, step), as in model_forward).  Returns (h, e, StackSaved
+    or None)."""
+    drop = _dropout_arg(dropout)
+    real_w = H if ln_width is None else int(ln_width)
+    ss = StackSaved(dropout=drop, opts=current()) if save else None
+    for i in range(num_layers):
+        h, e, ls = layer_forward(idx, N, E, H, layer_params(P, i), h, e, save, batch_norm, ln_width=ln_width, wide_ln=wide_ln)
+        if drop is not None:
+            node_dropout(h, drop, i, real_w, idx.get("nperm"))
+        if save:
+            ss.layers.append(ls)
+    return h, e, ss
+
+
+@on_device_of(lambda idx, N, E, H, P, num_layers, ss, gh, *a, **k: gh)
+@_scoped(6)
+def stack_backward(idx, N: int, E: int, H: int, P: Dict[str, torch.Tensor], num_layers: int, ss: StackSaved, gh, ge,
+                   batch_norm: bool = True, ln_width: Optional[int] = None):
+    """Backward of stack_forward, layer by layer.  gh [N,H] is read (never written), ge [E,H] is OVERWRITTEN as in layer_backward.
+    Returns (gh_in, ge_in, [grads dict per layer])."""
+    real_w = H if ln_width is None else int(ln_width)
+    grads = [None] * num_layers
+    for i in reversed(range(num_layers)):
+        if ss.dropout is not None:      # the gradient of layer i's output through layer i's mask (the caller's gh: out of place)
+            gh = node_dropout(gh, ss.dropout, i, real_w, idx.get("nperm"), out=torch.empty_like(gh) if i == num_layers - 1 else None)
+        gh, ge, grads[i] = layer_backward(idx, N, E, H, layer_params(P, i), ss.layers[i], gh, ge, batch_norm, ln_width=ln_width)
+        ss.layers[i] = None
+    return gh, ge, grads
 
 
 @on_device_of(lambda scores, *a, **k: scores)

@@ -134,21 +134,26 @@ class GatedGCN_1d(nn.Module):
         self.bn_h = _Norm(out_channels)
         self.bn_e = _Norm(out_channels)
 
-    def forward(self, g, h, e):
-        g = as_assembly_graph(g, h.device)
+    def _padded_parameters(self):
+        """The layer's parameters in _LAYER_KEYS order, at the kernel width it runs on: the next one up with dead output channels
+        (zero weight rows, bias 0, norm weight 1 / bias 0; with the residual, in == out, dead input columns too).  autograd slices
+        the gradients back."""
         P = dict(self.named_parameters())
         flat = [P[k] for k in _LAYER_KEYS]
-        need = torch.is_grad_enabled() and any(t.requires_grad for t in [h, e] + flat)
-        W, Wp = self.out_channels, padded_width(self.out_channels)
-        if Wp != W:
-            # run the next kernel width up with dead output channels (zero weight rows, bias 0, norm weight 1 / bias 0); with
-            # the residual (in == out) the inputs get the same dead channels.  autograd slices everything back.
-            d = Wp - W
+        d = padded_width(self.out_channels) - self.out_channels
+        if d:
             di = d if self.residual else 0
             flat = [F.pad(t, (0, di, 0, d)) if t.dim() == 2 else
                     F.pad(t, (0, d), value=1.0 if k in ("bn_h.weight", "bn_e.weight") else 0.0) for k, t in zip(_LAYER_KEYS, flat)]
-            if di:
-                h, e = F.pad(h, (0, di)), F.pad(e, (0, di))
+        return flat
+
+    def forward(self, g, h, e):
+        g = as_assembly_graph(g, h.device)
+        flat = self._padded_parameters()
+        need = torch.is_grad_enabled() and any(t.requires_grad for t in [h, e] + flat)
+        W, Wp = self.out_channels, padded_width(self.out_channels)
+        if Wp != W and self.residual:     # the inputs of a residual layer get the same dead channels
+            h, e = F.pad(h, (0, Wp - W)), F.pad(e, (0, Wp - W))
         h, e = _LayerFn.apply(g, need, (bool(self.batch_norm), W, self._wide_ln), self.residual, h, e, *flat)
         if Wp != W:
             h, e = h[:, :W], e[:, :W]
@@ -159,20 +164,81 @@ class GatedGCN_1d(nn.Module):
         return h, e
 
 
-class GraphGatedGCN(nn.Module):
-    """processor.py:8-20.  forward(graph, h, e) -> (h, e)."""
+class _StackFn(torch.autograd.Function):
+    """GraphGatedGCN.forward with node-output dropout: the whole stack through engine.stack_forward / stack_backward, so that the
+    masks come from the device counter (engine.node_dropout) and the backward re-derives them."""
 
-    def __init__(self, num_layers, hidden_features, batch_norm):
+    @staticmethod
+    def forward(ctx, graph, need, norm, dropout, num_layers, h, e, *flat):
+        batch_norm, ln_width, wide_ln = norm
+        nk = len(_LAYER_KEYS)
+        P = {f"gnn.convs.{i}.{k}": v.detach() for i in range(num_layers) for k, v in zip(_LAYER_KEYS, flat[i * nk:(i + 1) * nk])}
+        idx = graph.index(h.device)
+        N, E, H = graph.num_nodes(), graph.num_edges(), flat[0].shape[0]
+        perm = idx["perm"].long()
+        e_int = e.detach().index_select(0, perm).contiguous()
+        h_int = engine.node_rows_in(idx, engine._f32c(h.detach()))
+        h_out, e_out, saved = engine.stack_forward(idx, N, E, H, P, num_layers, h_int, e_int, need, batch_norm, ln_width=ln_width,
+                                                   wide_ln=wide_ln, dropout=dropout)
+        ctx.graph, ctx.saved, ctx.P, ctx.dims, ctx.bn, ctx.lnw = graph, saved, P, (N, E, H, num_layers), batch_norm, ln_width
+        out_e = torch.empty_like(e_out)
+        out_e.index_copy_(0, perm, e_out)
+        return engine.node_rows_out(idx, h_out), out_e
+
+    @staticmethod
+    def backward(ctx, gh_out, ge_out):
+        if ctx.saved is None:
+            raise RuntimeError("GraphGatedGCN: backward called twice (retain_graph is not supported) or forward ran without grad")
+        N, E, H, L = ctx.dims
+        idx = ctx.graph.index(gh_out.device)
+        perm = idx["perm"].long()
+        ge = ge_out.index_select(0, perm).contiguous()        # fresh buffer, overwritten below
+        gh_in, ge_in, gl = engine.stack_backward(idx, N, E, H, ctx.P, L, ctx.saved, engine.node_rows_in(idx, engine._f32c(gh_out)),
+                                                 ge, ctx.bn, ln_width=ctx.lnw)
+        gh_in = engine.node_rows_out(idx, gh_in)
+        ctx.saved = None
+        ge_user = torch.empty_like(ge_in)
+        ge_user.index_copy_(0, perm, ge_in)
+        grads = []
+        for g in gl:
+            for j in range(len(engine.LIN5)):
+                grads += [g["W5"][j * H:(j + 1) * H], g["b5"][j * H:(j + 1) * H]]
+            grads += [g["W3"], g["b3"], g["gamma_h"], g["beta_h"], g["gamma_e"], g["beta_e"]]
+        return (None, None, None, None, None, gh_in, ge_user) + tuple(grads)
+
+
+class GraphGatedGCN(nn.Module):
+    """processor.py:8-20.  forward(graph, h, e) -> (h, e).
+
+    dropout (keyword, default 0.0; not in the reference's signature, whose processor passes none to its layers): in training mode
+    with grad enabled, every layer's node output is dropped with probability p and the rest scaled by 1 / (1 - p)
+    (gated_gcn_full.py:154), with masks from the device counter (engine.dropout_seed, engine.dropout_draw) instead of torch's
+    generator.  `last_dropout` then holds the forward's (p, key, step): engine.dropout_mask(N, H, it, layer, device) is layer's mask."""
+
+    def __init__(self, num_layers, hidden_features, batch_norm, dropout=0.0):
         super().__init__()
+        self.dropout = engine.dropout_p(dropout)
+        self.last_dropout = None
         self.convs = nn.ModuleList([
             GatedGCN_1d(hidden_features, hidden_features, batch_norm) for _ in range(num_layers)
         ])
 
     def forward(self, graph, h, e):
         graph = as_assembly_graph(graph, h.device)
-        for conv in self.convs:
-            h, e = conv(graph, h, e)
-        return h, e
+        if not (self.dropout and self.training and torch.is_grad_enabled()) or not len(self.convs):
+            for conv in self.convs:
+                h, e = conv(graph, h, e)
+            return h, e
+        c0 = self.convs[0]
+        flat = [t for conv in self.convs for t in conv._padded_parameters()]
+        need = any(t.requires_grad for t in [h, e] + flat)
+        W, Wp = c0.out_channels, padded_width(c0.out_channels)
+        if Wp != W:
+            h, e = F.pad(h, (0, Wp - W)), F.pad(e, (0, Wp - W))
+        self.last_dropout = engine.dropout_draw(self.dropout, h.device)
+        norm = (bool(c0.batch_norm), W, all(c._wide_ln for c in self.convs))
+        h, e = _StackFn.apply(graph, need, norm, self.last_dropout, len(self.convs), h, e, *flat)
+        return (h[:, :W], e[:, :W]) if Wp != W else (h, e)
 
 
 class _PredFn(torch.autograd.Function):

@@ -74,9 +74,10 @@ class _ModelFn(torch.autograd.Function):
         # run it zero-padded to the next width up (gated_gcn_full.py:58-59: nn.LayerNorm(out_channels)); its third entry is the
         # model's activation_checkpoint (it rides here so that the positional layout backward() counts on stays as it is)
         batch_norm, ln_width, checkpoint, *wl = norm       # a fourth entry: the layers' WIDE_LAYERNORM decision (GatedGCN_1d._wide_ln)
-        P = {k: v.detach() for k, v in zip(names, flat)}
+        P = {k: v.detach() for k, v in zip(names, flat)}            # a fifth: this forward's node-output dropout (p, key, step) or None
         scores, saved = engine.model_forward(graph, e.detach(), pe.detach(), P, num_layers, need, batch_norm, ln_width=ln_width,
-                                             checkpoint=checkpoint, wide_ln=wl[0] if wl else None)
+                                             checkpoint=checkpoint, wide_ln=wl[0] if wl else None,
+                                             dropout=wl[1] if len(wl) > 1 else None)
         ctx.graph, ctx.saved, ctx.P, ctx.names, ctx.L, ctx.bn, ctx.lnw = graph, saved, P, names, num_layers, batch_norm, ln_width
         ctx.params = flat if need else None
         return scores
@@ -140,15 +141,22 @@ class GraphGatedGCNModel(nn.Module):
     `activation_checkpoint` (a plain int attribute, default 0 or the environment's GNM_CHECKPOINT; set it after construction):
     k > 0 keeps, of the layer stack, only the inputs of every k-th layer for the backward, which recomputes one k-layer segment at
     a time (engine.model_forward, `checkpoint`).  Same logits; less memory for one more forward of the stack per step.  No effect
-    under torch.no_grad().  A negative or non-integer value raises GnmError at the next forward."""
+    under torch.no_grad().  A negative or non-integer value raises GnmError at the next forward.
+
+    `dropout` (keyword, default 0.0; the reference's model passes none to its layers): node-output dropout of every GatedGCN layer
+    (gated_gcn_full.py:154) in training mode with grad enabled -- masks from the device counter (engine.dropout_seed; one step per
+    such forward), re-derived by the backward and by a checkpoint recomputation, never stored.  `last_dropout` holds the latest
+    forward's (p, key, step) for engine.dropout_mask.  No effect under eval() or torch.no_grad(); 0.0 changes nothing at all."""
 
     def __init__(self, node_features, edge_features, hidden_features, hidden_edge_features, num_layers,
-                 hidden_edge_scores, batch_norm, nb_pos_enc):
+                 hidden_edge_scores, batch_norm, nb_pos_enc, dropout=0.0):
         super().__init__()
+        self.dropout = engine.dropout_p(dropout)
+        self.last_dropout = None
         self.linear_pe = nn.Linear(nb_pos_enc + 2, hidden_features)
         self.linear1_edge = nn.Linear(edge_features, hidden_edge_features)
         self.linear2_edge = nn.Linear(hidden_edge_features, hidden_features)
-        self.gnn = layers.GraphGatedGCN(num_layers, hidden_features, batch_norm)
+        self.gnn = layers.GraphGatedGCN(num_layers, hidden_features, batch_norm, dropout=self.dropout)
         self.predictor = layers.ScorePredictor(hidden_features, hidden_edge_scores)
         self.num_layers = num_layers
         self.batch_norm = bool(batch_norm)
@@ -168,6 +176,9 @@ class GraphGatedGCNModel(nn.Module):
         graph = as_assembly_graph(graph, pe.device)       # a DGLGraph(-like) object is wrapped once and cached on itself
         H = self.linear_pe.out_features
         Hp = layers.padded_width(H)
+        drop = None
+        if self.dropout and self.training and torch.is_grad_enabled():
+            drop = self.last_dropout = engine.dropout_draw(self.dropout, pe.device)
         if Hp != H:
             # a width the kernels are not built for (they are for 32 / 64 / 128 / 256): run the next one up with zero-padded
             # parameters -- the extra channels stay exactly zero through every layer (t = 0 -> bn -> relu -> 0; their gates
@@ -175,14 +186,14 @@ class GraphGatedGCNModel(nn.Module):
             names, flat = zip(*self.named_parameters())
             padded = tuple(_pad_param(k, v, H, Hp) for k, v in zip(names, flat))
             need = torch.is_grad_enabled() and (any(p.requires_grad for p in flat) or e.requires_grad or pe.requires_grad)
-            return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint, self._wide_ln()), *padded)
+            return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint, self._wide_ln(), drop), *padded)
         if pe.is_cuda and not _is_flat(self):
             flatten_parameters(self)          # once per device placement: stacked-parameter views instead of torch.cat
         names, flat = zip(*self.named_parameters())
         # e / pe requiring grad (input attribution, a frozen model, a learnable transform in front of the encoders) also
         # needs the activations: the backward returns their gradients; x stays dead (full_graph.py:23), its .grad None
         need = torch.is_grad_enabled() and (any(p.requires_grad for p in flat) or e.requires_grad or pe.requires_grad)
-        return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint, self._wide_ln()), *flat)
+        return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint, self._wide_ln(), drop), *flat)
 
 
 class _BCEFn(torch.autograd.Function):

@@ -45,6 +45,8 @@ def get_hyperparameters() -> Dict:
         "num_parts_metis_train": 500, "num_parts_metis_eval": 500, "partition_method": "locality",
         # loss, TP..FN and the epoch sums from one pass over the logits (criterion.with_counts); same History either way
         "fused_metrics": os.environ.get("GNM_FUSED_METRICS", "0").strip() == "1",
+        # node-output dropout of the GatedGCN layers (GraphGatedGCNModel's dropout keyword); validation runs in eval mode: none there
+        "dropout": 0.0,
     }
 
 
@@ -167,7 +169,7 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     else:
         model = models.GraphGatedGCNModel(hp["node_features"], hp["edge_features"], hp["dim_latent"],
                                           hp["hidden_edge_features"], hp["num_gnn_layers"], hp["hidden_edge_scores"],
-                                          hp["batch_norm"], hp["nb_pos_enc"]).to(dev)            # train.py:195-198
+                                          hp["batch_norm"], hp["nb_pos_enc"], dropout=hp["dropout"]).to(dev)   # train.py:195-198
     if world > 1:
         for p in model.parameters():
             dist.broadcast(p.data, 0)

@@ -613,6 +613,25 @@ int gnm_bce_stats_fwd_bwd(int64_t E, const float* scores, const float* y, float 
                           float* loss_out, float* gscore, int64_t* counts_out, void* epoch_acc,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* ---- node-output dropout of the layer stack (gated_gcn_full.py:154) with a counter-based mask, nothing stored --------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: two new symbols, no existing signature changes, and the binding checks
+ * every symbol by name when it loads.)
+ * The keep decision of element (row r, channel c) is a pure function of (seed, step, layer, v, c), v = node_ids[r] (the caller's
+ * node id of internal row r: the index's internal -> caller array; NULL: v = r): Philox4x32-10 with key (seed low word, seed
+ * high word) and counter (q low, q high, layer, step), q = (v * H + c) >> 2 in 64 bits; word c & 3 of its output is the draw x,
+ * u = (x >> 8) * 2^-24, kept iff u >= (float)p, compared in fp32 (p travels as a double so that the scale float(1 / (1 - p)) is
+ * rounded once).  It does not depend on the internal node numbering, the grid or the occupancy cap.
+ *   gnm_node_dropout_apply  y[r, c] = kept ? x[r, c] * float(1 / (1 - p)) : +0 for c < H; rows ld >= H elements apart in x and y
+ *                           (a padded width, a column chunk: columns H .. ld-1 are neither read nor written).  y == x (in place)
+ *                           is allowed, any other overlap is not.  The backward is the same call on the gradient.
+ *                           H % 4 == 0, ld % 4 == 0 and 16-byte aligned x, y: one float4 per Philox call; else element by element.
+ *   gnm_node_dropout_mask   mask[r * H + c] = kept (uint8 0 / 1, contiguous [N,H]): the same decisions, for inspection.
+ * 0 <= p < 1, layer >= 0, N >= 0.                                                                                             */
+int gnm_node_dropout_apply(int64_t N, int H, int64_t ld, const float* x, float* y, const int32_t* node_ids, double p,
+                           uint64_t seed, uint32_t step, int layer, void* stream);
+int gnm_node_dropout_mask(int64_t N, int H, uint8_t* mask, const int32_t* node_ids, double p, uint64_t seed, uint32_t step,
+                          int layer, void* stream);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
