@@ -126,6 +126,9 @@ SIGNATURES = {
     "gnm_bce_stats_fwd_bwd": (_i32, [_i64, _p, _p, _f32, _p, _p, _p, _p, _p, _sz, _p]),
     "gnm_node_dropout_apply": (_i32, [_i64, _i32, _i64, _p, _p, _p, C.c_double, _u64, _u32, _i32, _p]),
     "gnm_node_dropout_mask": (_i32, [_i64, _i32, _p, _p, C.c_double, _u64, _u32, _i32, _p]),
+    "gnm_optim_workspace_bytes": (_sz, [_i64]),
+    "gnm_optim_grad_stats": (_i32, [_i64, _p, _p, _p, _sz, _p]),
+    "gnm_optim_adam_step": (_i32, [_i64, _p, _p, _p, _p, _p, _p, _p, _sz] + [C.c_double] * 5 + [_p, _i32, _p]),
 }
 
 

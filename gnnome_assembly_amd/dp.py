@@ -15,7 +15,7 @@ from typing import Iterable, Optional
 import torch
 import torch.distributed as dist
 
-__all__ = ["init_process_group", "FlatGradients", "shard_graphs", "steps_per_epoch", "fresh_flat_gradients", "current_rank"]
+__all__ = ["init_process_group", "FlatGradients", "shard_graphs", "steps_per_epoch", "fresh_flat_gradients", "current_rank", "LibAdam"]
 
 _live = weakref.WeakSet()      # the FlatGradients objects alive in this process
 # GNM_FORCE_COLLECTIVE=1: do not skip the collectives at world size 1 (lets a 1-GPU box execute the RCCL path end to end)
@@ -162,6 +162,147 @@ def make_adam(params, lr: float):
         if float(lo) != float(hi):
             raise RuntimeError("dp.make_adam: the ranks chose different Adam implementations (fused on some, default on others)")
     return opt
+
+
+class LibAdam(torch.optim.Optimizer):
+    """torch.optim.Adam(params, lr, betas, eps) (no weight decay, no amsgrad) as the library's own step over the flat buffers
+    (gnm_optim_grad_stats + gnm_optim_adam_step, include/gnm.h): two launches per step that read the gradient once, clip its
+    global norm to `max_norm` (0: off; torch.nn.utils.clip_grad_norm_'s formula), update m, v and the parameters, can leave the
+    gradient buffer zeroed (step(zero_grad=True): the `fresh` state the direct-write backward wants) and skip the whole step on
+    the device when the gradient holds a NaN or an infinity -- the host reads nothing.
+
+    Preconditions, checked here (no other route is taken when one fails): every parameter is a float32 view of ONE flat buffer
+    (models.flatten_parameters) and requires grad, and their .grads are the views of one FlatGradients (`flat`, or the live one
+    that owns them) at the same offsets.  One param group; lr, betas, eps and max_norm are read from it at every step, so
+    ReduceLROnPlateau works as with any optimizer.  state[p] holds views (exp_avg, exp_avg_sq) of the flat m and v and the
+    shared device step scalar; state_dict() / load_state_dict() speak torch Adam's schema in both directions."""
+
+    gnm_impl = "library"
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, max_norm: float = 0.0, flat=None):
+        if not (isinstance(lr, (int, float)) and 0.0 <= lr < float("inf")):
+            raise ValueError(f"LibAdam: invalid learning rate {lr!r}")
+        if not (len(betas) == 2 and all(isinstance(b, (int, float)) and 0.0 <= b < 1.0 for b in betas)):
+            raise ValueError(f"LibAdam: invalid betas {betas!r}")
+        if not (isinstance(eps, (int, float)) and 0.0 <= eps < float("inf")):
+            raise ValueError(f"LibAdam: invalid eps {eps!r}")
+        if not (isinstance(max_norm, (int, float)) and 0.0 <= max_norm < float("inf")):
+            raise ValueError(f"LibAdam: invalid max_norm {max_norm!r} (0 switches clipping off)")
+        # torch Adam's own group keys ride along (weight_decay 0, amsgrad False, ...), so that a state_dict of this class loads
+        # into torch.optim.Adam, whose step reads them from the group
+        defaults = dict(torch.optim.Adam([torch.zeros(1)], lr=float(lr), betas=tuple(betas), eps=float(eps)).defaults)
+        defaults["max_norm"] = float(max_norm)
+        super().__init__(params, defaults)
+        if len(self.param_groups) != 1:
+            raise ValueError("LibAdam: one param group (the flat buffers have one set of hyper-parameters)")
+        ps = self.param_groups[0]["params"]
+        if not all(hasattr(p, "_gnm_slot") for p in ps):
+            raise ValueError("LibAdam: the parameters are not flattened: call models.flatten_parameters(model) first")
+        order = sorted(ps, key=lambda p: p._gnm_slot)
+        first = order[0]
+        n = sum(p.numel() for p in order)
+        o = 0
+        for p in order:
+            if p.dtype != torch.float32 or not p.requires_grad or p.device != first.device or not p.data.is_contiguous() or \
+                    p.data.untyped_storage().data_ptr() != first.data.untyped_storage().data_ptr() or \
+                    p.data.storage_offset() != first.data.storage_offset() + o:
+                raise ValueError("LibAdam: the parameters do not tile ONE flat float32 buffer in models.flatten_parameters' order "
+                                 "(every parameter of the flattened model must be passed and must require grad; model.to(device) "
+                                 "un-flattens: flatten again)")
+            o += p.numel()
+        self._p = torch.empty(0, dtype=torch.float32, device=first.device).set_(first.data.untyped_storage(),
+                                                                               first.data.storage_offset(), (n,), (1,))
+        if flat is None:
+            flat = next((fg for fg in _live if fg.owns(order)), None)
+            if flat is None:
+                raise ValueError("LibAdam: the parameters' .grads are not the views of a live dp.FlatGradients: build "
+                                 "dp.FlatGradients(model.parameters()) after flatten_parameters and before LibAdam")
+        o = 0
+        for p in order:
+            if flat.grads.numel() != n or p.grad is None or p.grad.dtype != torch.float32 or not p.grad.is_contiguous() or \
+                    p.grad.data_ptr() != flat.flat.data_ptr() + 4 * o:
+                raise ValueError("LibAdam: the .grads are not the views of `flat` in the parameters' order (a FlatGradients built "
+                                 "before flatten_parameters keeps another layout; a re-allocated .grad is no view)")
+            o += p.numel()
+        self.flat = flat
+        dev = first.device
+        # what make_adam's group says on a HIP device: a torch.optim.Adam that loads this optimizer's state_dict takes over the
+        # saved group, and must stay on (or move to) its fused kernel rather than drop to the foreach implementation
+        self.param_groups[0]["fused"] = True if dev.type == "cuda" else None
+        self._m = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._v = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._step = torch.zeros((), dtype=torch.float32, device=dev)
+        self._stats = torch.zeros(4, dtype=torch.int64, device=dev)      # gnm_optim_stats: double, int64, int64, double
+        self._ws = None
+        self._order = order
+        self._bind_state()
+
+    def _bind_state(self):
+        o = 0
+        for p in self._order:
+            k = p.numel()
+            self.state[p] = {"step": self._step, "exp_avg": self._m[o:o + k].view_as(p), "exp_avg_sq": self._v[o:o + k].view_as(p)}
+            o += k
+
+    @torch.no_grad()
+    def step(self, closure=None, zero_grad: bool = False):
+        """The two launches, on the current stream.  A mean over data-parallel contributors is all_reduce_mean's business and is
+        not applied again here (the C ABI's inv_count is for hosts without it).  zero_grad=True: the gradient buffer is left all
+        zeros by the same pass and `flat` is marked fresh."""
+        from . import engine
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        g = self.param_groups[0]
+        if self._ws is None:
+            self._ws = engine.optim_workspace(self._p.numel(), self._p.device)
+        engine.optim_step(self._p, self.flat.grads, self._m, self._v, self._step, self._stats, self._ws, g["lr"], g["betas"][0],
+                          g["betas"][1], g["eps"], g["max_norm"], None, zero_grad)
+        if zero_grad:
+            self.flat.fresh = True
+        return loss
+
+    def zero_grad(self, set_to_none: bool = False):
+        """Zeroes the flat gradient buffer in place (the .grads stay its views) and marks it fresh."""
+        self.flat.zero_()
+
+    def stats(self) -> torch.Tensor:
+        """float64 [4] on the device, no synchronisation: the last step's total_norm, its non-finite count, the number of
+        steps skipped so far, the last step's clip factor."""
+        f = self._stats.view(torch.float64)
+        return torch.stack([f[0], self._stats[1].double(), self._stats[2].double(), f[3]])
+
+    def state_dict(self):
+        """torch.optim.Adam's schema: per parameter `step` (float32 scalar), `exp_avg`, `exp_avg_sq`, as clones."""
+        sd = super().state_dict()
+        sd["state"] = {k: {name: (t.clone() if torch.is_tensor(t) else t) for name, t in st.items()} for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """Accepts what state_dict() returns and what torch.optim.Adam (default, foreach or fused) writes: the moments are
+        copied into the flat buffers and state[p] keeps viewing them.  Per-parameter step counts that disagree are refused (one
+        shared scalar advances here), and so are weight decay, amsgrad and maximize."""
+        for grp in state_dict["param_groups"]:
+            if grp.get("weight_decay", 0) or grp.get("amsgrad", False) or grp.get("maximize", False):
+                raise ValueError("LibAdam.load_state_dict: weight_decay, amsgrad and maximize are not supported")
+        states = list(state_dict["state"].values())
+        steps = {float(st["step"]) for st in states if "step" in st}
+        if len(steps) > 1 or (steps and (len(states) != len(self._order) or any("step" not in st for st in states))):
+            raise ValueError(f"LibAdam.load_state_dict: the parameters' step counts disagree ({sorted(steps)}, "
+                             f"{len(self._order) - sum('step' in st for st in states)} without one); one shared count advances here")
+        super().load_state_dict(state_dict)          # param groups (lr, betas, ...) and a cast copy of the state onto the device
+        loaded = {p: dict(self.state.get(p, {})) for p in self._order}
+        self._step.fill_(steps.pop() if steps else 0.0)
+        self._bind_state()
+        for p in self._order:
+            st = loaded[p]
+            for name in ("exp_avg", "exp_avg_sq"):
+                if name in st:
+                    self.state[p][name].copy_(st[name])
+                else:
+                    self.state[p][name].zero_()
+        self.param_groups[0].setdefault("max_norm", self.defaults["max_norm"])       # a torch Adam checkpoint has none
 
 
 def steps_per_epoch(local_steps: int, device=None) -> int:

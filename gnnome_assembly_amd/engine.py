@@ -2128,5 +2128,30 @@ def bce_with_logits_counts(scores, y, pos_weight: float, need_grad: bool = True,
     return loss, gs, counts
 
 
+def optim_workspace(n: int, device) -> torch.Tensor:
+    """The workspace of optim_step for flat buffers of n elements (gnm_optim_workspace_bytes), as int64 words: 8-byte aligned."""
+    return torch.empty((_lib.load().gnm_optim_workspace_bytes(int(n)) + 7) // 8, dtype=torch.int64, device=device)
+
+
+@on_device_of(lambda p, *a, **k: p)
+def optim_step(p, g, m, v, step, stats, ws, lr, beta1, beta2, eps, max_norm=0.0, inv_count=None, zero_grad=False):
+    """One optimizer step over flat fp32 buffers, two launches on the current stream (gnm_optim_grad_stats, gnm_optim_adam_step;
+    include/gnm.h): Adam with the gradient's norm clipped to max_norm (0: off), skipped as a whole when g holds a non-finite
+    entry.  step: device float scalar; stats: int64 [4] holding a gnm_optim_stats; ws: optim_workspace(n)."""
+    _chk_dev(p, g, m, v, step, stats, ws, inv_count)
+    n = p.numel()
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise ValueError(f"optim_step: {name} must be a contiguous float32 tensor of {n} elements")
+    if step.dtype != torch.float32 or step.numel() != 1 or (inv_count is not None and (inv_count.dtype != torch.float32 or inv_count.numel() != 1)):
+        raise ValueError("optim_step: step (and inv_count) must be float32 scalars")
+    if stats.dtype != torch.int64 or stats.numel() != 4 or not stats.is_contiguous():
+        raise ValueError("optim_step: stats must be a contiguous int64 [4] tensor")
+    wsb = ws.numel() * ws.element_size()
+    _call("gnm_optim_grad_stats", n, _ptr(g), _ptr(step), _ptr(ws), wsb, _stream())
+    _call("gnm_optim_adam_step", n, _ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(step), _ptr(stats), _ptr(ws), wsb, float(lr),
+          float(beta1), float(beta2), float(eps), float(max_norm), _ptr(inv_count), int(bool(zero_grad)), _stream())
+
+
 _default = Options(**{k: (globals()["_D_" + k] if k not in ("ACTIVATIONS", "TN_AT") else {"ACTIVATIONS": "saved", "TN_AT": "auto"}[k])
                       for k in _OPTION_NAMES}).replace(ACTIVATIONS=_D_ACTIVATIONS, TN_AT=_D_TN_AT)     # environment values are validated

@@ -16,6 +16,9 @@ Differences from the reference, all deliberate:
     [num_parts-100, num_parts+100), shuffled batches of clusters, one Adam step per batch;
   * with the hyper-parameter "fused_metrics" (default: GNM_FUSED_METRICS=1, else off) the loss kernel also counts TP..FN and adds
     the step to the epoch's sums (BCEWithLogitsLoss.with_counts + EpochStats): same History, no metric launches in the loop;
+  * with the hyper-parameter "optimizer": "library" (default: GNM_OPTIM=library, else "torch") the step is dp.LibAdam's: two
+    launches over the flat buffers that also leave the gradient zeroed for the next backward, clip the gradient's norm to
+    "clip_grad_norm" (0: off) and skip a step whose gradient is not finite, counted in History.skipped_steps;
   * wandb and the data pipeline are out of scope.
 `calculate_metrics` keeps the reference's naming, in which "precision" and "recall" are swapped
 (utils.py:227-234)."""
@@ -47,6 +50,10 @@ def get_hyperparameters() -> Dict:
         "fused_metrics": os.environ.get("GNM_FUSED_METRICS", "0").strip() == "1",
         # node-output dropout of the GatedGCN layers (GraphGatedGCNModel's dropout keyword); validation runs in eval mode: none there
         "dropout": 0.0,
+        # "torch": dp.make_adam.  "library": dp.LibAdam (Adam, norm clip and non-finite guard in the library's own two launches)
+        "optimizer": "library" if os.environ.get("GNM_OPTIM", "").strip().lower() == "library" else "torch",
+        # the gradient's global norm is clipped to this before the step (torch's clip_grad_norm_); 0: off; "library" route only
+        "clip_grad_norm": 0.0,
     }
 
 
@@ -135,6 +142,8 @@ class History:
     tfpn_valid: List[tuple] = field(default_factory=list)
     best_epoch: int = -1
     final_lr: float = 0.0
+    skipped_steps: int = 0                                      # "optimizer": "library": steps skipped so far for a non-finite gradient
+    total_norm: List[float] = field(default_factory=list)       # ... and per epoch the gradient norm of its last step (before clipping)
 
 
 def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSample], out: str = "model",
@@ -153,6 +162,14 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     hooks = hooks or {}
     hp = dict(get_hyperparameters())
     hp.update(hyperparameters or {})
+    if hp["optimizer"] not in ("torch", "library"):
+        raise ValueError(f"hyper-parameter optimizer={hp['optimizer']!r}: expected 'torch' or 'library'")
+    lib_opt = hp["optimizer"] == "library"
+    if not float(hp["clip_grad_norm"]) >= 0.0:
+        raise ValueError(f"hyper-parameter clip_grad_norm={hp['clip_grad_norm']!r}: expected a number >= 0 (0: off)")
+    if hp["clip_grad_norm"] > 0 and not lib_opt:
+        raise ValueError("hyper-parameter clip_grad_norm > 0 needs \"optimizer\": \"library\": the torch route does not clip, and "
+                         "the value is not silently ignored")
     seed = hp["seed"]
     random.seed(seed)
     torch.manual_seed(seed)                                                     # utils.set_seed
@@ -176,7 +193,10 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     best_state = copy.deepcopy(model.state_dict())                                              # train.py:203
     models.flatten_parameters(model)
     flat = dp.FlatGradients(model.parameters(), direct_write=True)       # the loop below zero_()s before every backward
-    optimizer = dp.make_adam(model.parameters(), hp["lr"])                               # train.py:209
+    if lib_opt:
+        optimizer = dp.LibAdam(model.parameters(), hp["lr"], max_norm=float(hp["clip_grad_norm"]), flat=flat)
+    else:
+        optimizer = dp.make_adam(model.parameters(), hp["lr"])                           # train.py:209
     criterion = (hooks["criterion_factory"](1.0 / ratio) if "criterion_factory" in hooks
                  else models.BCEWithLogitsLoss(pos_weight=1.0 / ratio))                         # train.py:210-211
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=hp["decay"],
@@ -199,10 +219,15 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         # every rank takes the same number of optimizer steps: shards may be uneven (dp.shard_graphs), the
         # shorter ranks pad with zero-contribution steps so that the gradient collectives stay matched
         nsteps = dp.steps_per_epoch(len(order), dev)
+        # library route: every step leaves the gradient buffer zeroed (step(zero_grad=True)); only the epoch's first step zeroes it
+        # explicitly -- validation and the hooks have run since the last one
+        zero_first = True
         for it in range(nsteps):
             s = train_samples[order[it]] if it < len(order) else None
             if hp["batch_size_train"] <= 1:                                                     # full graph
-                flat.zero_()
+                if zero_first or not lib_opt:
+                    flat.zero_()
+                    zero_first = False
                 if s is not None:
                     pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)                           # train.py:252-253
                     loss = criterion.with_counts(pred, s.y, ep_stats)[0] if fused else criterion(pred, s.y)
@@ -210,7 +235,10 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                 flat.all_reduce_mean(contributed=s is not None)
                 if "after_exchange" in hooks:
                     hooks["after_exchange"](epoch, it, flat)
-                optimizer.step()                                                                # train.py:256-258
+                if lib_opt:
+                    optimizer.step(zero_grad=True)
+                else:
+                    optimizer.step()                                                            # train.py:256-258
                 if s is not None and fused:              # the loss kernel has added the step to ep_stats
                     ep_losses.append(loss.detach())
                     hist.step_graph.append(order[it])
@@ -231,14 +259,19 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                     graph_stats.zero_()
                 for _ in range(nbatches):
                     sub = next(batches, None)
-                    flat.zero_()
+                    if zero_first or not lib_opt:
+                        flat.zero_()
+                        zero_first = False
                     if sub is not None:
                         pred = model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1)    # train.py:306
                         loss = (criterion.with_counts(pred, sub.edata["y"], graph_stats)[0] if fused
                                 else criterion(pred, sub.edata["y"]))
                         loss.backward()
                     flat.all_reduce_mean(contributed=sub is not None)
-                    optimizer.step()
+                    if lib_opt:
+                        optimizer.step(zero_grad=True)
+                    else:
+                        optimizer.step()
                     if sub is not None and not fused:
                         gl += loss.detach().double()
                         nb += 1
@@ -255,6 +288,10 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
             dist.all_reduce(loss_sum); dist.all_reduce(n_train); dist.all_reduce(counts)        # noqa: E702
         train_loss = float(loss_sum / n_train)
         hist.loss_train.append(train_loss)
+        if lib_opt:                          # the step kernels' device record, read here with the losses and never per step
+            st = optimizer.stats().cpu()
+            hist.skipped_steps = int(st[2])
+            hist.total_norm.append(float(st[0]))
         if ep_losses:
             hist.step_losses += torch.stack(ep_losses).double().cpu().tolist()
         hist.tfpn_train.append(tuple(int(c) for c in counts.tolist()))

@@ -632,6 +632,37 @@ int gnm_node_dropout_apply(int64_t N, int H, int64_t ld, const float* x, float* 
 int gnm_node_dropout_mask(int64_t N, int H, uint8_t* mask, const int32_t* node_ids, double p, uint64_t seed, uint32_t step,
                           int layer, void* stream);
 
+/* ---- the optimizer step over the flat buffers: Adam, gradient-norm clip, non-finite guard ------------------------------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: three new symbols, no existing signature changes.)
+ * torch.optim.Adam (train.py:209,256-258; no weight decay, no amsgrad) over flat fp32 buffers of n elements -- the layout
+ * models.flatten_parameters and dp.FlatGradients share -- in two launches on one stream, with no host read-back:
+ *   gnm_optim_grad_stats   one pass over g: per block of 2048 elements the fp64 sum of squares of the finite entries and the count
+ *                          of the non-finite ones, one pair per block into `workspace`; it also copies *step into the workspace,
+ *                          so that every workgroup of the step kernel sees the count of before the call, however late it starts.
+ *   gnm_optim_adam_step    consumes the workspace of the gnm_optim_grad_stats call before it on the stream (same n, g, step):
+ *                            c          = 1, or 1 / max(*inv_count, 1) with inv_count (device float: a contributor count)
+ *                            total_norm = c * sqrt(sum of squares);  clip = max_norm > 0 ? min(1, max_norm / (total_norm + 1e-6)) : 1
+ *                            guard:       a non-finite entry anywhere in g -> p, m, v and *step keep their bits, stats.skipped += 1
+ *                            otherwise    t = *step + 1 -> *step;  gh = g * c * clip;  m = beta1 m + (1 - beta1) gh;
+ *                                         v = beta2 v + (1 - beta2) gh^2;
+ *                                         p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *                            zero_grad != 0: g is left all zeros, in the skipped case too.
+ *                          Scalars in fp64; each element evaluated in fp64 from the fp32 inputs and rounded once per stored value.
+ * step:      device float, the step count (the dtype of torch's fused Adam); written by one thread.
+ * stats:     device gnm_optim_stats, 8-byte aligned; total_norm, nonfinite and clip are overwritten by every call (in a skipped
+ *            call total_norm covers the finite entries), skipped accumulates: zero it once.  Read it whenever convenient.
+ * workspace: gnm_optim_workspace_bytes(n) bytes, 8-byte aligned; its previous content is not read by gnm_optim_grad_stats.
+ * Bit-identical between runs and independent of the grid, the CU count and gnm_set_occupancy_cap: a block partial depends on its
+ * 2048 elements alone, the combination on the number of blocks alone; no atomics.  16-byte loads and stores when every buffer is
+ * 16-byte aligned, element by element otherwise and in the tail -- same bits.  n == 0: nothing is launched, *step stays.
+ * lr >= 0, 0 <= beta < 1, eps >= 0, max_norm >= 0 (0: no clipping), all finite.                                                 */
+typedef struct gnm_optim_stats { double total_norm; int64_t nonfinite; int64_t skipped; double clip; } gnm_optim_stats;
+size_t gnm_optim_workspace_bytes(int64_t n);
+int gnm_optim_grad_stats(int64_t n, const float* g, const float* step, void* workspace, size_t workspace_bytes, void* stream);
+int gnm_optim_adam_step(int64_t n, float* p, float* g, float* m, float* v, float* step, void* stats, const void* workspace,
+                        size_t workspace_bytes, double lr, double beta1, double beta2, double eps, double max_norm,
+                        const float* inv_count, int zero_grad, void* stream);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
