@@ -129,6 +129,8 @@ SIGNATURES = {
     "gnm_optim_workspace_bytes": (_sz, [_i64]),
     "gnm_optim_grad_stats": (_i32, [_i64, _p, _p, _p, _sz, _p]),
     "gnm_optim_adam_step": (_i32, [_i64, _p, _p, _p, _p, _p, _p, _p, _sz] + [C.c_double] * 5 + [_p, _i32, _p]),
+    "gnm_rank_hist_workspace_bytes": (_sz, [_i64]),
+    "gnm_rank_hist": (_i32, [_i64, _p, _p, _p, _p, _sz, _p]),
 }
 
 

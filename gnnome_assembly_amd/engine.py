@@ -2128,6 +2128,28 @@ def bce_with_logits_counts(scores, y, pos_weight: float, need_grad: bool = True,
     return loss, gs, counts
 
 
+RANK_BINS = 16384                      # bins per label of a gnm_rank_record (include/gnm.h): the 14-bit key of an fp32 logit
+RANK_RECORD_WORDS = 2 * RANK_BINS + 4  # int64 hist[2][RANK_BINS], then tail[4] = nan_pos, nan_neg, other_label, calls
+
+
+@on_device_of(lambda scores, *a, **k: scores)
+def rank_hist(scores, y, record):
+    """Add the (score, label) pairs to `record` (gnm_rank_hist, one launch on the current stream): a contiguous int64
+    [RANK_RECORD_WORDS] device tensor holding a gnm_rank_record (train.RankingStats.buf), which the caller zeroes once."""
+    lib = _lib.load()
+    _chk_dev(scores, y, record)
+    x = _f32c(scores.reshape(-1).float())          # .float(): a half or bf16 tensor is counted as its fp32 copy (exact widening)
+    y = _f32c(y.reshape(-1).float())
+    E = x.numel()
+    if y.numel() != E:
+        raise ValueError(f"rank_hist: {E} scores, {y.numel()} labels")
+    if record.dtype != torch.int64 or record.numel() != RANK_RECORD_WORDS or not record.is_contiguous():
+        raise ValueError(f"rank_hist: record must be a contiguous int64 [{RANK_RECORD_WORDS}] tensor (train.RankingStats.buf)")
+    need = lib.gnm_rank_hist_workspace_bytes(E)
+    ws = scratch(x.device).ws(need) if need else None
+    _call("gnm_rank_hist", E, _ptr(x), _ptr(y), _ptr(record), _ptr(ws), need, _stream())
+
+
 def optim_workspace(n: int, device) -> torch.Tensor:
     """The workspace of optim_step for flat buffers of n elements (gnm_optim_workspace_bytes), as int64 words: 8-byte aligned."""
     return torch.empty((_lib.load().gnm_optim_workspace_bytes(int(n)) + 7) // 8, dtype=torch.int64, device=device)

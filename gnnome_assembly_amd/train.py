@@ -19,6 +19,10 @@ Differences from the reference, all deliberate:
   * with the hyper-parameter "optimizer": "library" (default: GNM_OPTIM=library, else "torch") the step is dp.LibAdam's: two
     launches over the flat buffers that also leave the gradient zeroed for the next backward, clip the gradient's norm to
     "clip_grad_norm" (0: off) and skip a step whose gradient is not finite, counted in History.skipped_steps;
+  * with the hyper-parameter "ranking_metrics" (default: GNM_RANKING_METRICS=1, else off) every validation forward also adds its
+    logits to a per-label histogram on the device (RankingStats, one launch, no sort, nothing of size [E]); once per epoch the 256 KiB
+    record is read and History gains the threshold-free figures the fixed sigmoid(x) = 0.5 counts cannot give: AUROC, average
+    precision and the best-F1 threshold.  Loss, schedule, best-model choice and every other History field are the same either way;
   * wandb and the data pipeline are out of scope.
 `calculate_metrics` keeps the reference's naming, in which "precision" and "recall" are swapped
 (utils.py:227-234)."""
@@ -30,12 +34,14 @@ import random
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import cluster, dp, models
 
-__all__ = ["get_hyperparameters", "GraphSample", "tfpn_counts", "calculate_metrics", "train", "save_checkpoint", "EpochStats"]
+__all__ = ["get_hyperparameters", "GraphSample", "tfpn_counts", "calculate_metrics", "train", "save_checkpoint", "EpochStats",
+           "RankingStats", "RankingMetrics", "BestF1"]
 
 
 def get_hyperparameters() -> Dict:
@@ -54,6 +60,8 @@ def get_hyperparameters() -> Dict:
         "optimizer": "library" if os.environ.get("GNM_OPTIM", "").strip().lower() == "library" else "torch",
         # the gradient's global norm is clipped to this before the step (torch's clip_grad_norm_); 0: off; "library" route only
         "clip_grad_norm": 0.0,
+        # AUROC, average precision and the best-F1 threshold of every validation epoch from a histogram of the logits (RankingStats)
+        "ranking_metrics": os.environ.get("GNM_RANKING_METRICS", "0").strip() == "1",
     }
 
 
@@ -93,6 +101,128 @@ class EpochStats:
         """(loss_sum, steps, (TP, TN, FP, FN)) with one device-to-host copy."""
         b = self.buf.cpu()
         return float(b[0:1].view(torch.float64)[0]), int(b[1]), tuple(int(c) for c in b[2:6].tolist())
+
+
+RANK_BINS = 16384            # bins per label: the 14-bit key of an fp32 logit (include/gnm.h, gnm_rank_record)
+
+
+def rank_bin_lower_edge(k) -> np.ndarray:
+    """The smallest fp32 value whose key is k (fp64 array): the logit threshold "predict positive from bin k upwards".  Invert
+    key = u >> 18 with u = bits ^ (sign ? 0xFFFFFFFF : 0x80000000): a bin of positive values starts at its smallest bit pattern, a
+    bin of negative values at its largest.  Bin 31 holds -inf alone among the values that are not NaN: its edge is -inf."""
+    u = np.asarray(k, dtype=np.uint64) << np.uint64(18)
+    bits = np.where(u >> np.uint64(31) != 0, u ^ np.uint64(0x80000000), ~u & np.uint64(0xFFFFFFFF))
+    with np.errstate(invalid="ignore"):              # the edges of the bins that only NaN patterns fall into
+        x = bits.astype(np.uint32).view(np.float32).astype(np.float64)
+    return np.where(np.isnan(x), np.where(u >> np.uint64(31) != 0, np.inf, -np.inf), x)
+
+
+@dataclass
+class BestF1:
+    """The threshold "positive iff logit >= logit" (the lower edge of bin `bin`) with the largest F1 = 2TP / (2TP + FP + FN) among
+    the occupied bins; of equal F1 values the highest bin.  prob = sigmoid(logit)."""
+    f1: float
+    logit: float
+    prob: float
+    bin: int
+    TP: int
+    TN: int
+    FP: int
+    FN: int
+
+
+@dataclass
+class RankingMetrics:
+    """What a gnm_rank_record says about how the logits order positives and negatives (host code, fp64 numpy on integers).
+    auroc counts a (positive, negative) pair in one bin as 1/2, auroc_lo as 0 and auroc_hi as 1: the exact Mann-Whitney AUROC of the
+    raw logits (ties 1/2) lies in [auroc_lo, auroc_hi], because two edges in different bins are ordered as their bins are."""
+    auroc: float
+    auroc_lo: float
+    auroc_hi: float
+    average_precision: float
+    best_f1: Optional[BestF1]
+    n_pos: int               # binned positives and negatives (NaN logits and other labels are in n_nan / n_other)
+    n_neg: int
+    n_nan: int
+    n_other: int
+    calls: int
+    hist: np.ndarray = field(repr=False, compare=False, default=None)       # int64 [2, RANK_BINS]: negatives, positives
+
+    @classmethod
+    def from_counts(cls, hist, tail) -> "RankingMetrics":
+        hist = np.asarray(hist, dtype=np.int64).reshape(2, RANK_BINS)
+        tail = np.asarray(tail, dtype=np.int64).reshape(4)
+        neg, pos = hist[0].astype(np.float64), hist[1].astype(np.float64)
+        P, N = float(pos.sum()), float(neg.sum())
+        nan = float("nan")
+        if P > 0 and N > 0:
+            above = P - np.cumsum(pos)                                        # positives in the bins above k
+            lo = float((neg * above).sum())
+            tie = float((neg * pos).sum())
+            auroc, auroc_lo, auroc_hi = (lo + 0.5 * tie) / (P * N), lo / (P * N), (lo + tie) / (P * N)
+        else:
+            auroc = auroc_lo = auroc_hi = nan
+        occ = np.flatnonzero(hist[0] + hist[1])[::-1]                         # occupied bins, from the top
+        best, ap = None, nan
+        if occ.size:
+            tp, fp = np.cumsum(pos[occ]), np.cumsum(neg[occ])                 # predicted positive from bin occ[i] upwards
+            if P > 0 and N > 0:
+                ap = float((pos[occ] / P * (tp / (tp + fp))).sum())           # sum over bins of (R_k - R_{k-1}) Prec_k
+            den = 2.0 * tp + fp + (P - tp)
+            f1 = np.where(den > 0, 2.0 * tp / np.where(den > 0, den, 1.0), 0.0)
+            i = int(np.argmax(f1))                                            # first maximum from the top: the highest bin
+            edge = float(rank_bin_lower_edge(occ[i]))
+            with np.errstate(over="ignore"):
+                prob = float(1.0 / (1.0 + np.exp(-edge)))
+            best = BestF1(float(f1[i]), edge, prob, int(occ[i]), int(tp[i]), int(N - fp[i]), int(fp[i]), int(P - tp[i]))
+        return cls(auroc, auroc_lo, auroc_hi, ap, best, int(P), int(N), int(tail[0] + tail[1]), int(tail[2]), int(tail[3]), hist)
+
+    def _curve(self):
+        occ = np.flatnonzero(self.hist[0] + self.hist[1])[::-1]
+        tp, fp = np.cumsum(self.hist[1][occ]).astype(np.float64), np.cumsum(self.hist[0][occ]).astype(np.float64)
+        return occ, tp, fp
+
+    def roc(self):
+        """(fpr, tpr, logit thresholds) over the occupied bins from the top; NaN where a class is empty."""
+        occ, tp, fp = self._curve()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return fp / float(self.n_neg), tp / float(self.n_pos), rank_bin_lower_edge(occ)
+
+    def pr(self):
+        """(precision, recall, logit thresholds) over the occupied bins from the top."""
+        occ, tp, fp = self._curve()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return tp / (tp + fp), tp / float(self.n_pos), rank_bin_lower_edge(occ)
+
+
+class RankingStats:
+    """A gnm_rank_record as one int64 tensor `buf` of 2 * RANK_BINS + 4 words: hist[2][RANK_BINS] (negatives, positives) and
+    tail[4] = nan_pos, nan_neg, other_label, calls (`hist` and `tail` are views).  add() is one launch on the current stream and
+    needs a HIP device; the buffer itself may live on the CPU (all_reduce_ under gloo, RankingMetrics.from_counts).  Records add:
+    across steps, graphs and -- all_reduce_ -- ranks."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(2 * RANK_BINS + 4, dtype=torch.int64, device=device)
+        self.hist = self.buf[:2 * RANK_BINS].view(2, RANK_BINS)
+        self.tail = self.buf[2 * RANK_BINS:]
+
+    def zero_(self):
+        self.buf.zero_()
+        return self
+
+    def add(self, scores, y):
+        from . import engine
+        engine.rank_hist(scores.detach(), y, self.buf)
+        return self
+
+    def all_reduce_(self):
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.buf)
+        return self
+
+    def read(self) -> RankingMetrics:
+        b = self.buf.cpu().numpy()
+        return RankingMetrics.from_counts(b[:2 * RANK_BINS], b[2 * RANK_BINS:])
 
 
 def calculate_metrics(TP, TN, FP, FN):
@@ -144,6 +274,9 @@ class History:
     final_lr: float = 0.0
     skipped_steps: int = 0                                      # "optimizer": "library": steps skipped so far for a non-finite gradient
     total_norm: List[float] = field(default_factory=list)       # ... and per epoch the gradient norm of its last step (before clipping)
+    auroc_valid: List[float] = field(default_factory=list)      # "ranking_metrics": per epoch RankingMetrics.auroc of the validation logits,
+    ap_valid: List[float] = field(default_factory=list)         # ... .average_precision,
+    best_f1_valid: List[tuple] = field(default_factory=list)    # ... and (best_f1.f1, best_f1.logit); all three stay empty when it is off
 
 
 def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSample], out: str = "model",
@@ -205,6 +338,9 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     fused = bool(hp["fused_metrics"]) and hasattr(criterion, "with_counts")
     if fused:
         ep_stats, graph_stats = EpochStats(dev), EpochStats(dev)       # the epoch's sums; one graph's batches (mini-batch mode)
+    ranking = bool(hp["ranking_metrics"])
+    if ranking:
+        rank_stats = RankingStats(dev)                                 # the validation epoch's logit histogram
     hist = History()
     order = list(range(len(train_samples)))
     model_path = os.path.join(workdir, "pretrained", f"model_{out}.pt")
@@ -302,20 +438,29 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         vcounts = torch.zeros(4, device=dev, dtype=torch.int64)
         if fused:
             ep_stats.zero_()
+        if ranking:
+            rank_stats.zero_()
         with torch.no_grad():
             for s in valid_samples:
                 if hp["batch_size_eval"] <= 1 and fused:
-                    criterion.with_counts(model(s.graph, s.x, s.e, s.pe).squeeze(-1), s.y, ep_stats)
+                    pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)
+                    criterion.with_counts(pred, s.y, ep_stats)
+                    if ranking:
+                        rank_stats.add(pred, s.y)
                 elif hp["batch_size_eval"] <= 1:
                     pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)
                     vloss += criterion(pred, s.y).double()
                     vcounts += tfpn_counts(pred, s.y)
+                    if ranking:
+                        rank_stats.add(pred, s.y)
                 elif fused:
                     graph_stats.zero_()
                     for sub in _cluster_batches(s, hp["num_parts_metis_eval"], hp["batch_size_eval"],
                                                 hp["partition_method"]):
-                        criterion.with_counts(model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1), sub.edata["y"],
-                                              graph_stats)
+                        pred = model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1)
+                        criterion.with_counts(pred, sub.edata["y"], graph_stats)
+                        if ranking:
+                            rank_stats.add(pred, sub.edata["y"])
                     vloss += graph_stats.loss_sum / graph_stats.steps.clamp(min=1)
                     vcounts += graph_stats.counts
                 else:                                                                           # train.py:428-486
@@ -327,12 +472,19 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                         gl += criterion(pred, sub.edata["y"]).double()
                         nb += 1
                         vcounts += tfpn_counts(pred, sub.edata["y"])
+                        if ranking:
+                            rank_stats.add(pred, sub.edata["y"])
                     vloss += gl / max(nb, 1)
         if fused and hp["batch_size_eval"] <= 1:
             vloss, vcounts = ep_stats.loss_sum.clone(), ep_stats.counts.clone()
         n_val = torch.tensor(float(len(valid_samples)), device=dev, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(vloss); dist.all_reduce(n_val); dist.all_reduce(vcounts)            # noqa: E702
+        if ranking:                              # the record adds across ranks like the counts; one read per epoch
+            rm = rank_stats.all_reduce_().read()
+            hist.auroc_valid.append(rm.auroc)
+            hist.ap_valid.append(rm.average_precision)
+            hist.best_f1_valid.append((rm.best_f1.f1, rm.best_f1.logit) if rm.best_f1 is not None else None)
         val_loss = float(vloss / n_val.clamp(min=1))
         hist.loss_valid.append(val_loss)
         hist.tfpn_valid.append(tuple(int(c) for c in vcounts.tolist()))

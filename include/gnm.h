@@ -663,6 +663,28 @@ int gnm_optim_adam_step(int64_t n, float* p, float* g, float* m, float* v, float
                         size_t workspace_bytes, double lr, double beta1, double beta2, double eps, double max_norm,
                         const float* inv_count, int zero_grad, void* stream);
 
+/* ---- threshold-free validation metrics: a per-label histogram of the logits from one pass, no sort ----------------------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: two new symbols, no existing signature changes.)
+ * The key of an fp32 logit x that is not NaN:  u = bits(x + 0.0f) (-0 counts as +0);  u ^= (u >> 31) ? 0xFFFFFFFF : 0x80000000;
+ * key = u >> 18: sign, 8 exponent bits, 5 mantissa bits.  It is monotone non-decreasing in x; -inf has the lowest key a value can
+ * take (31) and +inf the highest (16352).  Bin k of hist[l] counts the edges with label l and key k: AUROC with exact lower and
+ * upper bounds, average precision, the ROC / PR curves and the best-F1 threshold follow from the record on the host
+ * (train.RankingMetrics.from_counts).
+ *   gnm_rank_hist   ADDS one call's E (score, label) pairs to *record: y == 1 is a positive, y == 0 a negative, any other label
+ *                   (NaN included) adds to tail[2] alone; a NaN score adds to tail[0] (y == 1) or tail[1] (y == 0) and to no bin;
+ *                   tail[3] += 1 per call.  E == 0 is a valid call that adds 1 to tail[3] and nothing else (scores and y may then
+ *                   be NULL).  The caller zeroes the record; records add across calls, graphs and ranks.
+ * record:    device gnm_rank_record, 8-byte aligned.
+ * workspace: gnm_rank_hist_workspace_bytes(E) bytes -- currently 0, and ws may then be NULL: every workgroup keeps its histogram
+ *            in LDS and adds its non-zero bins to the record with 64-bit integer atomics.
+ * The record is a function of (scores, y, previous record) alone: all of its fields are integer sums, which commute, so it does
+ * not depend on the grid, the CU count, gnm_set_occupancy_cap or the order in which the atomics land, and two runs give the same
+ * bits.  E < 0, a NULL record, NULL scores or y with E > 0, a short workspace and an E that would give one workgroup 2^31 or more
+ * elements (its bins are 32-bit) are errors, returned before anything is launched.                                              */
+typedef struct gnm_rank_record { int64_t hist[2][16384]; int64_t tail[4]; /* nan_pos, nan_neg, other_label, calls */ } gnm_rank_record;
+size_t gnm_rank_hist_workspace_bytes(int64_t E);
+int gnm_rank_hist(int64_t E, const float* scores, const float* y, void* record, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
