@@ -131,6 +131,8 @@ SIGNATURES = {
     "gnm_optim_adam_step": (_i32, [_i64, _p, _p, _p, _p, _p, _p, _p, _sz] + [C.c_double] * 5 + [_p, _i32, _p]),
     "gnm_rank_hist_workspace_bytes": (_sz, [_i64]),
     "gnm_rank_hist": (_i32, [_i64, _p, _p, _p, _p, _sz, _p]),
+    "gnm_read_mask": (_i32, [_i64, C.c_double, _u64, _u32, _u32, _p, _p]),
+    "gnm_index_degrees": (_i32, [_i64, _p, _p, _p, _p, _i64, _p]),
 }
 
 

@@ -31,7 +31,8 @@ import torch
 from . import engine
 from .graph import AssemblyGraph
 
-__all__ = ["node_order", "partition_graph", "edge_cut", "induced_subgraph", "ClusterBatchLoader", "NID", "EID"]
+__all__ = ["node_order", "partition_graph", "edge_cut", "induced_subgraph", "ClusterBatchLoader", "NID", "EID",
+           "masked_subgraph", "MaskedGraphLoader", "read_mask_host", "index_degrees_torch"]
 
 NID = "_ID"     # dgl.NID / dgl.EID: original ids of a subgraph's nodes / edges
 EID = "_ID"
@@ -192,6 +193,58 @@ def _graph_tensors(sub: AssemblyGraph):
 PREFETCH = os.environ.get("GNM_BATCH_PREFETCH", "1") != "0"
 
 
+def _iterate_built(loader, items: Sequence, build_one, parents: Sequence[AssemblyGraph]) -> Iterator[AssemblyGraph]:
+    """The one iteration of every loader here (ClusterBatchLoader, MaskedGraphLoader): yields build_one(item) for every item.
+    With `loader.prefetch`, item k+1 -- its sub-graph, its index and both sweep plans -- is built on the loader's side stream
+    (`loader._side`, created on first use) while the caller's kernels of item k run, and handed over with an event wait and
+    record_stream.  `parents`: the graphs the items are cut from, whose index is built before anything runs on the side stream."""
+    if not loader.prefetch:
+        for item in items:
+            yield build_one(item)
+        return
+    dev = parents[0].device
+    for parent in parents:
+        parent.index(dev)                           # the parent's index (cached) before anything runs on the side stream
+    if loader._side is None:
+        loader._side = torch.cuda.Stream(device=dev)
+    side = loader._side
+
+    def build(item):
+        # device and stream contexts are entered HERE only -- never held across a yield (a generator that yields inside
+        # `with torch.cuda.device(...)` leaks the context into its consumer until it is closed) -- and the consumer's stream is
+        # looked up at every hand-over: whatever stream is current in the caller when it asks for a batch is the one that
+        # waits for the build and that the batch's tensors are recorded on
+        with torch.cuda.device(dev):
+            with torch.cuda.stream(side):
+                sub = build_one(item)
+                sub.index(dev)
+                if hasattr(sub, "sweep_plan"):
+                    sub.sweep_plan(dev, 1)
+                    sub.sweep_plan(dev, engine.GATE2_WG)
+                ev = torch.cuda.Event()
+                ev.record(side)
+        return sub, ev
+
+    def hand_over(sub, ev):
+        with torch.cuda.device(dev):
+            consumer = torch.cuda.current_stream(dev)
+            consumer.wait_event(ev)
+            for t in _graph_tensors(sub):
+                t.record_stream(consumer)
+        return sub
+    # The side stream waits for the caller's stream ONCE, here: the parent graph's tensors as they are when the iteration starts.
+    # (Waiting before every build -- tried in round 6 on ADVICE r5 -- makes build k+1 wait for batch k's training kernels: the overlap
+    # this loader exists for is gone, 43 -> 38 M edges/s on the mini-batch epoch.)  The contract instead: the parent's ndata / edata
+    # are read-only while its batches are being iterated, as in the reference's loop (train.py:296-343 only reads them).
+    with torch.cuda.device(dev):
+        side.wait_stream(torch.cuda.current_stream(dev))
+    nxt = build(items[0]) if len(items) else None
+    for k in range(len(items)):
+        sub = hand_over(*nxt)
+        yield sub                                   # the caller issues item k's kernels, then asks for the next one:
+        nxt = build(items[k + 1]) if k + 1 < len(items) else None               # built while those kernels run
+
+
 class ClusterBatchLoader:
     """Iterates the mini-batches of one graph: `batch_size` clusters per batch, clusters shuffled when
     `shuffle` (DataLoader(..., shuffle=True, drop_last=False)); yields induced subgraphs.
@@ -204,10 +257,15 @@ class ClusterBatchLoader:
     bound) sit on the critical path of a 21 ms step.  On the side stream the synchronisations wait for the small build kernels
     only, which run in the gaps of the training kernels.  The caller's stream waits for the build's event before it touches the
     batch; every tensor of the batch is handed over with record_stream, so the caching allocator does not recycle it under the
-    training kernels."""
+    training kernels.
+
+    read_mask (optional; the read-masking augmentation in mini-batch mode): dict(key, epoch, graph_index, fractions) with one
+    kept fraction per batch.  Batch k is then the sub-graph of `cluster selection & read mask(fractions[k])` -- ONE induce, through
+    masked_subgraph, so its `pe` carries the thinned batch's degrees; the partition stays the parent's."""
 
     def __init__(self, graph: AssemblyGraph, part: np.ndarray, batch_size: int, shuffle: bool = True,
-                 generator: Optional[torch.Generator] = None, prefetch: Optional[bool] = None, induce: Optional[str] = None):
+                 generator: Optional[torch.Generator] = None, prefetch: Optional[bool] = None, induce: Optional[str] = None,
+                 read_mask: Optional[Dict] = None):
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")
         self.induce = _induce_method(induce)        # how the batches are built (induced_subgraph's method); None: GNM_INDUCE
@@ -219,6 +277,12 @@ class ClusterBatchLoader:
         self.generator = generator
         self.prefetch = (PREFETCH if prefetch is None else bool(prefetch)) and graph.device.type == "cuda"
         self._side = None
+        self.read_mask = read_mask
+        if read_mask is not None:
+            if len(read_mask["fractions"]) != len(self):
+                raise ValueError(f"read_mask: {len(read_mask['fractions'])} fractions for {len(self)} batches")
+            if read_mask.get("recompute_pe"):       # features.positional_encoding works in the device's shared scratch buffers
+                self.prefetch = False
 
     def __len__(self) -> int:
         return (self.num_parts + self.batch_size - 1) // self.batch_size
@@ -227,55 +291,140 @@ class ClusterBatchLoader:
         ids = torch.randperm(self.num_parts, generator=self.generator) if self.shuffle else torch.arange(self.num_parts)
         return [ids[i:i + self.batch_size] for i in range(0, self.num_parts, self.batch_size)]
 
-    def _build(self, ids: torch.Tensor) -> AssemblyGraph:
+    def selection(self, ids: torch.Tensor) -> torch.Tensor:
+        """bool [N]: the nodes of the clusters `ids`"""
         dev = self.graph.device
         sel = torch.zeros(self.num_parts, dtype=torch.bool, device=dev)
         sel[ids.to(dev)] = True
-        return induced_subgraph(self.graph, sel[self.part.long()], self.induce)
+        return sel[self.part.long()]
+
+    def _build(self, ids: torch.Tensor, k: Optional[int] = None) -> AssemblyGraph:
+        rm = self.read_mask
+        if rm is None or k is None:
+            return induced_subgraph(self.graph, self.selection(ids), self.induce)
+        return masked_subgraph(self.graph, rm["fractions"][k], rm["key"], rm["epoch"], rm["graph_index"], self.induce,
+                               select=self.selection(ids), recompute_pe=bool(rm.get("recompute_pe")))
 
     def __iter__(self) -> Iterator[AssemblyGraph]:
-        dev = self.graph.device
         batches = self.batches()
-        if not self.prefetch:
-            for ids in batches:
-                yield self._build(ids)
-            return
-        self.graph.index(dev)                       # the parent's index (cached) before anything runs on the side stream
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=dev)
-        side = self._side
+        if self.read_mask is None:
+            yield from _iterate_built(self, batches, self._build, [self.graph])
+        else:
+            yield from _iterate_built(self, list(enumerate(batches)), lambda kb: self._build(kb[1], kb[0]), [self.graph])
 
-        def build(ids):
-            # device and stream contexts are entered HERE only -- never held across a yield (a generator that yields inside
-            # `with torch.cuda.device(...)` leaks the context into its consumer until it is closed) -- and the consumer's stream is
-            # looked up at every hand-over: whatever stream is current in the caller when it asks for a batch is the one that
-            # waits for the build and that the batch's tensors are recorded on
-            with torch.cuda.device(dev):
-                with torch.cuda.stream(side):
-                    sub = self._build(ids)
-                    sub.index(dev)
-                    if hasattr(sub, "sweep_plan"):
-                        sub.sweep_plan(dev, 1)
-                        sub.sweep_plan(dev, engine.GATE2_WG)
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-            return sub, ev
 
-        def hand_over(sub, ev):
-            with torch.cuda.device(dev):
-                consumer = torch.cuda.current_stream(dev)
-                consumer.wait_event(ev)
-                for t in _graph_tensors(sub):
-                    t.record_stream(consumer)
-            return sub
-        # The side stream waits for the caller's stream ONCE, here: the parent graph's tensors as they are when the iteration starts.
-        # (Waiting before every build -- tried in round 6 on ADVICE r5 -- makes build k+1 wait for batch k's training kernels: the overlap
-        # this loader exists for is gone, 43 -> 38 M edges/s on the mini-batch epoch.)  The contract instead: the parent's ndata / edata
-        # are read-only while its batches are being iterated, as in the reference's loop (train.py:296-343 only reads them).
-        with torch.cuda.device(dev):
-            side.wait_stream(torch.cuda.current_stream(dev))
-        nxt = build(batches[0]) if batches else None
-        for k in range(len(batches)):
-            sub = hand_over(*nxt)
-            yield sub                               # the caller issues batch k's kernels, then asks for the next batch:
-            nxt = build(batches[k + 1]) if k + 1 < len(batches) else None           # built while those kernels run
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Read-masking coverage augmentation: a training step on the sub-graph induced by a random subset of the READS.  A read set thinned
+# to the fraction f is, to first order, the same genome sequenced at f times the coverage, so a model trained on thinned graphs
+# meets at inference the node degrees of the coverages it will be used at -- and the degrees are the first two columns of `pe`.
+# The mask is a pure function of (f, key, epoch, graph_index, node) (include/gnm.h, gnm_read_mask): nothing is stored, and any
+# rank, test or later run re-derives it from five numbers.
+# ---------------------------------------------------------------------------------------------------------------------------------
+_PHILOX_M = (np.uint64(0xD2511F53), np.uint64(0xCD9E8D57))
+_PHILOX_W = (np.uint64(0x9E3779B9), np.uint64(0xBB67AE85))
+
+
+def read_mask_host(n: int, f: float, key: int, epoch: int, graph_index: int) -> np.ndarray:
+    """gnm_read_mask on the host (numpy, bool [n]): the route of a parent graph on the CPU, as induced_subgraph has one.  Read
+    r = v >> 1, Philox4x32-10 with key (key low, key high) on the counter (q low, q high, graph_index, epoch), q = r >> 2; word
+    r & 3 is the draw x; kept iff (x >> 8) * 2^-24 < float32(f)."""
+    f = engine.read_mask_fraction(f)
+    n = int(n)
+    key = int(key) & (2 ** 64 - 1)
+    lo, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    q = np.arange((n + 7) // 8, dtype=np.uint64)
+    c0, c1 = q & lo, q >> s32
+    c2 = np.full_like(q, int(graph_index) & 0xFFFFFFFF)
+    c3 = np.full_like(q, int(epoch) & 0xFFFFFFFF)
+    k0, k1 = np.uint64(key & 0xFFFFFFFF), np.uint64(key >> 32)
+    for _ in range(10):
+        p0, p1 = _PHILOX_M[0] * c0, _PHILOX_M[1] * c2          # 32 x 32 -> 64 bits: no overflow in uint64
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & lo, (p0 >> s32) ^ c3 ^ k1, p0 & lo
+        k0, k1 = (k0 + _PHILOX_W[0]) & lo, (k1 + _PHILOX_W[1]) & lo
+    x = np.stack((c0, c1, c2, c3), 1).reshape(-1)              # one word per read, in read order
+    u = (x >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return np.repeat(u < np.float32(f), 2)[:n]
+
+
+def index_degrees_torch(idx, pe: torch.Tensor) -> torch.Tensor:
+    """gnm_index_degrees in tensor ops (the host route, and the statement the kernel is tested against): columns 0 and 1 of the
+    caller's row nperm[i] of pe [n, >= 2] = in_ptr[i+1] - in_ptr[i], out_ptr[i+1] - out_ptr[i]; in place."""
+    ind = (idx["in_ptr"][1:] - idx["in_ptr"][:-1]).to(pe.dtype)
+    outd = (idx["out_ptr"][1:] - idx["out_ptr"][:-1]).to(pe.dtype)
+    nperm = idx.get("nperm")
+    if nperm is None:
+        pe[:, 0], pe[:, 1] = ind, outd
+    else:
+        pe[nperm.long(), 0], pe[nperm.long(), 1] = ind, outd
+    return pe
+
+
+def masked_subgraph(graph: AssemblyGraph, f: float, key: int, epoch: int, graph_index: int, method: Optional[str] = None,
+                    select: Optional[torch.Tensor] = None, recompute_pe: bool = False) -> AssemblyGraph:
+    """The graph thinned to the reads that engine.read_mask(n, f, key, epoch, graph_index) keeps: induced_subgraph of that mask
+    (`method` / GNM_INDUCE choose the route; `select`, bool [N]: ANDed into it first -- a mini-batch's cluster selection, still one
+    induce).  Every ndata / edata row is carried from the parent as induced_subgraph carries it, with one exception: `ndata["pe"]`
+    ([N, 2 + k]: in-degree | out-degree | k PageRank columns, as train._cluster_batches attaches it) is a copy whose columns 0 and
+    1 are the THINNED graph's degrees (engine.index_degrees on the sub-graph's own index); the PageRank columns stay the parent's
+    unless `recompute_pe`, which runs features.positional_encoding on the sub-graph (HIP device only).  relabel_info records
+    'mask_fraction', 'mask_kept_nodes' and 'mask' ('device', or 'host' for a parent on the CPU: read_mask_host)."""
+    f = engine.read_mask_fraction(f)
+    dev = graph.device
+    n = graph.num_nodes()
+    if dev.type == "cuda":
+        mask = engine.read_mask(n, f, key, epoch, graph_index, dev)
+    else:
+        mask = torch.from_numpy(read_mask_host(n, f, key, epoch, graph_index))
+    if select is not None:
+        select = select.to(dev)
+        if select.dtype != torch.bool or select.numel() != n:
+            raise ValueError("select must be a bool tensor with one entry per node")
+        mask = mask & select
+    sub = induced_subgraph(graph, mask, method)
+    pe = sub.ndata.get("pe")
+    if pe is not None:
+        if pe.dim() != 2 or pe.shape[1] < 2:
+            raise ValueError("masked_subgraph: ndata['pe'] must be [N, 2 + k]: in-degree | out-degree | positional encoding")
+        if recompute_pe:
+            from . import features
+            sub.ndata["pe"] = features.positional_encoding(sub, pe.shape[1] - 2)
+        elif dev.type == "cuda":
+            sub.ndata["pe"] = engine.index_degrees(sub.index(dev), pe.contiguous())     # pe: the slice's own memory already
+        else:
+            sub.ndata["pe"] = index_degrees_torch(sub.index(dev), pe.contiguous())
+    sub.relabel_info.update(mask_fraction=f, mask_kept_nodes=sub.num_nodes(), mask="device" if dev.type == "cuda" else "host")
+    return sub
+
+
+class MaskedGraphLoader:
+    """One thinned graph per training step of an epoch: `steps` is the epoch's list of (graph, f, graph_index) in step order, the
+    graphs with their features on ndata / edata (train._attach_features); yields masked_subgraph(graph, f, key, epoch,
+    graph_index) for each.  With prefetch (default on a HIP device; GNM_BATCH_PREFETCH=0 turns it off) step k+1's graph, its index
+    and both sweep plans are built on a side stream while step k runs, with ClusterBatchLoader's hand-over (_iterate_built); the
+    parents' ndata / edata are read-only while the iteration is in flight.  recompute_pe builds in line: the PageRank kernels
+    work in the device's shared scratch buffers, which the training step on the caller's stream uses too."""
+
+    def __init__(self, steps: Sequence[Tuple[AssemblyGraph, float, int]], key: int, epoch: int, prefetch: Optional[bool] = None,
+                 induce: Optional[str] = None, recompute_pe: bool = False):
+        self.steps = list(steps)
+        self.key, self.epoch = int(key), int(epoch)
+        self.induce = _induce_method(induce)
+        self.recompute_pe = bool(recompute_pe)
+        devs = {g.device for g, _, _ in self.steps}
+        if len(devs) > 1:
+            raise ValueError(f"MaskedGraphLoader: the graphs of an epoch live on {sorted(map(str, devs))}: expected one device")
+        on_gpu = bool(devs) and next(iter(devs)).type == "cuda"
+        self.prefetch = (PREFETCH if prefetch is None else bool(prefetch)) and on_gpu and not self.recompute_pe
+        self._side = None
+
+    def __len__(self) -> int:
+        return len(self.steps)
+
+    def _build(self, step) -> AssemblyGraph:
+        g, f, graph_index = step
+        return masked_subgraph(g, f, self.key, self.epoch, graph_index, self.induce, recompute_pe=self.recompute_pe)
+
+    def __iter__(self) -> Iterator[AssemblyGraph]:
+        parents = list({id(g): g for g, _, _ in self.steps}.values())
+        yield from _iterate_built(self, self.steps, self._build, parents)
+

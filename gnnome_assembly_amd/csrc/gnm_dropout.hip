@@ -11,21 +11,9 @@
 // row share one Philox call and one float4: one thread per call.  Any other H takes the same definition element by element (one
 // call per element; there the elements (v, c) and (v', c') with equal q and equal c & 3 share a draw -- a property of the
 // definition, not of this kernel).  Plain loads and stores, no LDS, no atomics: the result does not depend on the grid.
-#include "gnm_common.h"
+#include "gnm_philox.h"        // philox4x32_10
 
 namespace gnm {
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
 
 struct DropArgs {
   int64_t N;

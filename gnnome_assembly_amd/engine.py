@@ -552,6 +552,61 @@ def _dropout_opts(o: "Options") -> "Options":
 
 
 # ---------------------------------------------------------------------------------------
+# read-masking coverage augmentation (gnm_mask.hip): the mask of a training step, the degrees of the thinned graph
+# ---------------------------------------------------------------------------------------
+READ_MASK_KEY_XOR = 0xA0761D6478BD642F      # GNM_READ_MASK_KEY_XOR of include/gnm.h: odd, so the key never equals the dropout key
+
+
+def read_mask_key(seed: int, rank: Optional[int] = None) -> int:
+    """The Philox key of a rank's read masks: dropout_key(seed, rank) ^ READ_MASK_KEY_XOR -- the rank-mixed key of the dropout
+    stream moved by a fixed constant, so that the two streams of one seed never share a (key, counter) pair."""
+    return (dropout_key(seed, rank) ^ READ_MASK_KEY_XOR) & _M64
+
+
+def read_mask_fraction(f) -> float:
+    """A kept fraction as a float in [0, 1], or ValueError."""
+    try:
+        ok = 0 <= f <= 1
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"read mask fraction {f!r}: expected 0 <= f <= 1")
+    return float(f)
+
+
+def read_mask(n: int, f: float, key: int, epoch: int, graph_index: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bool [n]: node v (the caller's numbering; nodes 2i, 2i+1 are the strands of read i) is kept (gnm_read_mask, one launch on
+    the current stream of `device`).  A pure function of (f, key, epoch, graph_index, v).  `out`: a contiguous uint8 [n] tensor
+    to fill (any alignment); the result is its bool view."""
+    f = read_mask_fraction(f)
+    device = _dropout_dev(device)
+    if device.type != "cuda":
+        raise _lib.GnmError("read_mask: needs a HIP device (cluster.masked_subgraph has the host route for graphs on the CPU)")
+    n = int(n)
+    with torch.cuda.device(device):
+        if out is None:
+            out = torch.empty(max(n, 0), dtype=torch.uint8, device=device)
+        elif out.dtype != torch.uint8 or out.numel() != n or not out.is_contiguous() or out.device != device:
+            raise _lib.GnmError("read_mask: out must be a contiguous uint8 [n] tensor on the device")
+        _call("gnm_read_mask", n, f, int(key) & _M64, int(epoch) & 0xFFFFFFFF, int(graph_index) & 0xFFFFFFFF, _ptr(out), _stream())
+    return out.view(torch.bool)
+
+
+@on_device_of(lambda idx, pe: pe)
+def index_degrees(idx, pe: torch.Tensor) -> torch.Tensor:
+    """Columns 0 and 1 of pe [n, ld] (fp32, the caller's node order, written IN PLACE) = the in- and out-degrees the index `idx`
+    (dict of graph.index()) holds: gnm_index_degrees, one launch.  The other columns are left alone."""
+    n = int(idx["in_ptr"].numel()) - 1
+    nperm = idx.get("nperm")
+    _chk_dev(pe, idx["in_ptr"], idx["out_ptr"], nperm)
+    if pe.dim() != 2 or pe.dtype != torch.float32 or pe.shape[0] != n or pe.shape[1] < 2 or (n > 0 and pe.stride(1) != 1):
+        raise _lib.GnmError("index_degrees: pe must be a float32 [n, >= 2] tensor with unit inner stride, n the index's node count")
+    _call("gnm_index_degrees", n, _ptr(idx["in_ptr"]), _ptr(idx["out_ptr"]), _ptr(nperm), _ptr(pe), pe.stride(0) if n > 0 else pe.shape[1],
+          _stream())
+    return pe
+
+
+# ---------------------------------------------------------------------------------------
 # one GatedGCN layer
 # ---------------------------------------------------------------------------------------
 

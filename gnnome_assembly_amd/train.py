@@ -23,6 +23,10 @@ Differences from the reference, all deliberate:
     logits to a per-label histogram on the device (RankingStats, one launch, no sort, nothing of size [E]); once per epoch the 256 KiB
     record is read and History gains the threshold-free figures the fixed sigmoid(x) = 0.5 counts cannot give: AUROC, average
     precision and the best-F1 threshold.  Loss, schedule, best-model choice and every other History field are the same either way;
+  * with the hyper-parameters "mask_frac_low" / "mask_frac_high" (per cent; default 100 / 100: off) every training step runs on the graph
+    thinned to a random fraction of its READS (cluster.masked_subgraph: a device mask that is a pure function of seed, epoch, graph and
+    read; the thinned graph's own degrees in `pe`), the next step's graph built on a side stream meanwhile (cluster.MaskedGraphLoader);
+    a thinned graph without an edge is a zero-contribution step; validation is never masked; History gains mask_fraction / masked_edges;
   * wandb and the data pipeline are out of scope.
 `calculate_metrics` keeps the reference's naming, in which "precision" and "recall" are swapped
 (utils.py:227-234)."""
@@ -38,7 +42,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import cluster, dp, models
+from . import cluster, dp, engine, models
 
 __all__ = ["get_hyperparameters", "GraphSample", "tfpn_counts", "calculate_metrics", "train", "save_checkpoint", "EpochStats",
            "RankingStats", "RankingMetrics", "BestF1"]
@@ -62,6 +66,10 @@ def get_hyperparameters() -> Dict:
         "clip_grad_norm": 0.0,
         # AUROC, average precision and the best-F1 threshold of every validation epoch from a histogram of the logits (RankingStats)
         "ranking_metrics": os.environ.get("GNM_RANKING_METRICS", "0").strip() == "1",
+        # read-masking coverage augmentation: every TRAINING step keeps a fraction f = randint(low, high) / 100 of the reads (per cent,
+        # 1 <= low <= high <= 100; 100 / 100: off) and runs on the induced sub-graph with its own degrees in `pe`; the 16 PageRank
+        # columns are carried from the parent unless mask_recompute_pe.  Validation is never masked.
+        "mask_frac_low": 100, "mask_frac_high": 100, "mask_recompute_pe": False,
     }
 
 
@@ -249,14 +257,28 @@ def pos_to_neg_ratio(samples: Sequence[GraphSample]) -> float:
     return float(torch.stack(r).mean().item())
 
 
-def _cluster_batches(s: GraphSample, num_parts: int, batch_size: int, method: str):
-    """The sub-graphs of one pass over a graph in mini-batch mode; features ride on ndata / edata exactly
-    as the reference keeps them on the DGLGraph (train.py:298-307)."""
+def _attach_features(s: GraphSample):
+    """The sample's features on its graph's ndata / edata, exactly as the reference keeps them on the DGLGraph (train.py:298-307):
+    what a sub-graph slices."""
     g = s.graph
     g.ndata = dict(g.ndata, pe=s.pe)
     g.edata = dict(g.edata, e=s.e, y=s.y)
+    return g
+
+
+def _cluster_batches(s: GraphSample, num_parts: int, batch_size: int, method: str, read_mask=None):
+    """The sub-graphs of one pass over a graph in mini-batch mode; features ride on ndata / edata (_attach_features).
+    read_mask: None, or (key, epoch, graph_index, recompute_pe, draw) -- every batch is then thinned to the reads its own
+    f = draw() keeps (cluster.ClusterBatchLoader(read_mask=...)); the partition is the parent's cached one either way."""
+    g = _attach_features(s)
     part = cluster.partition_graph(g, num_parts, method)
-    return cluster.ClusterBatchLoader(g, part, batch_size, shuffle=True)
+    if read_mask is None:
+        return cluster.ClusterBatchLoader(g, part, batch_size, shuffle=True)
+    key, epoch, graph_index, recompute_pe, draw = read_mask
+    nb = len(cluster.ClusterBatchLoader(g, part, batch_size, shuffle=False, prefetch=False))
+    return cluster.ClusterBatchLoader(g, part, batch_size, shuffle=True,
+                                      read_mask=dict(key=key, epoch=epoch, graph_index=graph_index, recompute_pe=recompute_pe,
+                                                     fractions=[draw() for _ in range(nb)]))
 
 
 @dataclass
@@ -277,6 +299,9 @@ class History:
     auroc_valid: List[float] = field(default_factory=list)      # "ranking_metrics": per epoch RankingMetrics.auroc of the validation logits,
     ap_valid: List[float] = field(default_factory=list)         # ... .average_precision,
     best_f1_valid: List[tuple] = field(default_factory=list)    # ... and (best_f1.f1, best_f1.logit); all three stay empty when it is off
+    mask_fraction: List[float] = field(default_factory=list)    # "mask_frac_*": the kept read fraction f of every step of this rank on a graph or batch,
+    masked_edges: List[int] = field(default_factory=list)       # ... and the edge count of the thinned graph it ran on (0: a zero-contribution step, which
+                                                                # has no entry in step_losses / step_graph); added once per epoch; both empty when it is off
 
 
 def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSample], out: str = "model",
@@ -303,6 +328,11 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     if hp["clip_grad_norm"] > 0 and not lib_opt:
         raise ValueError("hyper-parameter clip_grad_norm > 0 needs \"optimizer\": \"library\": the torch route does not clip, and "
                          "the value is not silently ignored")
+    mlo, mhi = hp["mask_frac_low"], hp["mask_frac_high"]
+    if not (isinstance(mlo, int) and isinstance(mhi, int) and 1 <= mlo <= mhi <= 100):
+        raise ValueError(f"hyper-parameters mask_frac_low={mlo!r}, mask_frac_high={mhi!r}: expected integers (per cent) with "
+                         "1 <= low <= high <= 100 (100 / 100: no masking)")
+    masking = not (mlo == 100 and mhi == 100)
     seed = hp["seed"]
     random.seed(seed)
     torch.manual_seed(seed)                                                     # utils.set_seed
@@ -341,6 +371,12 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     ranking = bool(hp["ranking_metrics"])
     if ranking:
         rank_stats = RankingStats(dev)                                 # the validation epoch's logit histogram
+    if masking:
+        # a generator of its own: the global `random` decides the shuffle order, which masking must not change
+        mask_rng = random.Random(f"read-mask:{seed}")
+        mask_key = engine.read_mask_key(seed)                          # the rank-mixed dropout key ^ a fixed constant
+        recompute_pe = bool(hp["mask_recompute_pe"])
+        draw_f = lambda: mask_rng.randint(mlo, mhi) / 100.0            # noqa: E731
     hist = History()
     order = list(range(len(train_samples)))
     model_path = os.path.join(workdir, "pretrained", f"model_{out}.pt")
@@ -358,8 +394,22 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         # library route: every step leaves the gradient buffer zeroed (step(zero_grad=True)); only the epoch's first step zeroes it
         # explicitly -- validation and the hooks have run since the last one
         zero_first = True
+        empty_steps = 0                      # masking: graphs whose thinned form had no edge (zero-contribution steps)
+        ep_fracs, ep_edges = [], []
+        if masking and hp["batch_size_train"] <= 1:
+            # the epoch's thinned graphs, one per step, in step order; step k+1's is built on a side stream while step k runs
+            ep_fracs = [draw_f() for _ in order]
+            thinned = iter(cluster.MaskedGraphLoader([(_attach_features(train_samples[g]), f, g) for g, f in zip(order, ep_fracs)],
+                                                     mask_key, epoch, recompute_pe=recompute_pe))
         for it in range(nsteps):
             s = train_samples[order[it]] if it < len(order) else None
+            if masking and hp["batch_size_train"] <= 1 and s is not None:
+                sub = next(thinned)
+                ep_edges.append(sub.num_edges())
+                if sub.num_edges() == 0:     # nothing to train on: a padding step, so that the collectives stay matched
+                    s, empty_steps = None, empty_steps + 1
+                else:
+                    s = GraphSample(sub, sub.edata["e"], sub.ndata["pe"], sub.edata["y"])
             if hp["batch_size_train"] <= 1:                                                     # full graph
                 if zero_first or not lib_opt:
                     flat.zero_()
@@ -388,13 +438,19 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                 nparts = int(torch.randint(lo, hp["num_parts_metis_train"] + 100, (1,)).item())  # train.py:291
                 gl = torch.zeros((), device=dev, dtype=torch.float64)
                 nb = 0
-                loader = _cluster_batches(s, nparts, hp["batch_size_train"], hp["partition_method"]) if s is not None else []
+                rm = (mask_key, epoch, order[it], recompute_pe, draw_f) if masking and s is not None else None
+                loader = _cluster_batches(s, nparts, hp["batch_size_train"], hp["partition_method"], rm) if s is not None else []
                 nbatches = dp.steps_per_epoch(len(loader), dev)          # the ranks' cluster counts differ
                 batches = iter(loader)
                 if fused:
                     graph_stats.zero_()
                 for _ in range(nbatches):
                     sub = next(batches, None)
+                    if rm is not None and sub is not None:
+                        ep_fracs.append(sub.relabel_info["mask_fraction"])
+                        ep_edges.append(sub.num_edges())
+                        if sub.num_edges() == 0:         # a thinned batch without an edge: a zero-contribution step
+                            sub = None
                     if zero_first or not lib_opt:
                         flat.zero_()
                         zero_first = False
@@ -419,10 +475,12 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                     loss_sum += gl / max(nb, 1)                                                 # train.py:330
         if fused and hp["batch_size_train"] <= 1:
             loss_sum, counts = ep_stats.loss_sum.clone(), ep_stats.counts.clone()
-        n_train = torch.tensor(float(len(order)), device=dev, dtype=torch.float64)
+        n_train = torch.tensor(float(len(order) - empty_steps), device=dev, dtype=torch.float64)
+        hist.mask_fraction += ep_fracs
+        hist.masked_edges += ep_edges
         if world > 1:
             dist.all_reduce(loss_sum); dist.all_reduce(n_train); dist.all_reduce(counts)        # noqa: E702
-        train_loss = float(loss_sum / n_train)
+        train_loss = float(loss_sum / n_train.clamp(min=1)) if masking else float(loss_sum / n_train)
         hist.loss_train.append(train_loss)
         if lib_opt:                          # the step kernels' device record, read here with the losses and never per step
             st = optimizer.stats().cpu()
@@ -431,7 +489,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         if ep_losses:
             hist.step_losses += torch.stack(ep_losses).double().cpu().tolist()
         hist.tfpn_train.append(tuple(int(c) for c in counts.tolist()))
-        hist.metrics_train.append(calculate_metrics(*hist.tfpn_train[-1]))
+        # (no counts at all: an epoch whose every thinned graph came out without an edge)
+        hist.metrics_train.append(calculate_metrics(*hist.tfpn_train[-1]) if sum(hist.tfpn_train[-1]) or not masking else None)
         # ---- validation (train.py:385-511): eval mode, no_grad, no activations kept ----
         model.eval()
         vloss = torch.zeros((), device=dev, dtype=torch.float64)

@@ -685,6 +685,36 @@ typedef struct gnm_rank_record { int64_t hist[2][16384]; int64_t tail[4]; /* nan
 size_t gnm_rank_hist_workspace_bytes(int64_t E);
 int gnm_rank_hist(int64_t E, const float* scores, const float* y, void* record, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- read-masking coverage augmentation: which reads a training step keeps, and the degrees of the thinned graph --------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: two new symbols, no existing signature changes.)
+ * A training step may run on the sub-graph induced by a random subset of the READS: to first order a read set thinned to the
+ * fraction f is the same genome sequenced at f times the coverage.  Nodes 2i and 2i+1 are the two strands of read i; a read is
+ * kept or dropped as a whole.  The mask is a pure function of (key, epoch, graph_index, node), never a stored draw:
+ *   gnm_read_mask      mask[v] (uint8 0 / 1, the caller's node order, N entries) for v < N:  r = v >> 1 the read, q = r >> 2;
+ *                      Philox4x32-10 with key (key low word, key high word) and counter (q low, q high, graph_index, epoch);
+ *                      word r & 3 of its output is the draw x, u = (x >> 8) * 2^-24, the read is kept iff u < (float)f, compared
+ *                      in fp32 (f travels as a double and is rounded once).  f = 1 keeps every read, f = 0 none; masks of one
+ *                      (key, epoch, graph_index) are nested in f, and the mask for N is a prefix of the mask for N + k.  An odd N
+ *                      (the last read with one strand only) is legal.  One Philox call serves four reads = eight nodes: one
+ *                      8-byte store where `mask` is 8-byte aligned, byte stores otherwise and in the tail -- same bits.
+ *                      key: the training loop passes (the dropout key of the rank: seed ^ rank * 0x9E3779B97F4A7C15) ^
+ *                      GNM_READ_MASK_KEY_XOR, a fixed odd constant, so that the mask and the dropout stream of one seed never
+ *                      share a (key, counter) pair.
+ *                      It does not depend on the internal node numbering, the grid or gnm_set_occupancy_cap.  0 <= f <= 1 and
+ *                      N >= 0, else -1 before anything is launched; N == 0 returns 0 without a launch (mask may then be NULL).
+ *   gnm_index_degrees  for every internal node i < n of an index (in_ptr, out_ptr [n + 1], internal numbering):
+ *                        pe[nperm[i] * ld + 0] = (float)(in_ptr[i + 1] - in_ptr[i])      the in-degree
+ *                        pe[nperm[i] * ld + 1] = (float)(out_ptr[i + 1] - out_ptr[i])    the out-degree
+ *                      pe: row-major [n, ld] fp32 in the CALLER's node order, ld >= 2; columns 2 .. ld-1 are neither read nor
+ *                      written.  nperm: internal -> caller's node id, NULL: the identity.  A row nperm[i] outside [0, n) is
+ *                      checked before use and never written.  On the sub-graph of a read mask these are the THINNED graph's
+ *                      degrees: the first two columns of the model's `pe` input.  n == 0 returns 0 without a launch.
+ * No atomics, no LDS, no scratch memory, nothing allocated: two runs give the same bits.                                         */
+#define GNM_READ_MASK_KEY_XOR 0xA0761D6478BD642FULL
+int gnm_read_mask(int64_t N, double f, uint64_t key, uint32_t epoch, uint32_t graph_index, uint8_t* mask, void* stream);
+int gnm_index_degrees(int64_t n, const int32_t* in_ptr, const int32_t* out_ptr, const int32_t* nperm, float* pe, int64_t ld,
+                      void* stream);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
