@@ -2,6 +2,6 @@
 models.GraphGatedGCNModel / layers.* forward-backward).  See DESIGN.md."""
 from .graph import AssemblyGraph, from_dgl  # noqa: F401
 from . import layers, models, synth, features, cluster, decode, io  # noqa: F401
-from .models import GraphGatedGCNModel, BCEWithLogitsLoss  # noqa: F401
+from .models import GraphGatedGCNModel, BCEWithLogitsLoss, SymmetryLoss  # noqa: F401
 
 __version__ = "0.1.0"

@@ -133,6 +133,10 @@ SIGNATURES = {
     "gnm_rank_hist": (_i32, [_i64, _p, _p, _p, _p, _sz, _p]),
     "gnm_read_mask": (_i32, [_i64, C.c_double, _u64, _u32, _u32, _p, _p]),
     "gnm_index_degrees": (_i32, [_i64, _p, _p, _p, _p, _i64, _p]),
+    "gnm_sym_bce_workspace_bytes": (_sz, []),
+    "gnm_sym_bce_fwd_bwd": (_i32, [_i64, _p, _p, _p, _f32, _f32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "gnm_mirror_add": (_i32, [_i64, _p, _p, _p, _p]),
+    "gnm_mirror_gather": (_i32, [_i64, _p, _p, _p, _p]),
 }
 
 

@@ -7,6 +7,7 @@
 //   colsum / seg_sum_rows / gather_rows / relu_mask: bias gradients, segmented sums of the
 //                       predictor's [E,64] gradient rows, edge-id -> internal-order gather.
 #include "gnm_common.h"
+#include "gnm_bce.h"
 
 namespace gnm {
 
@@ -162,41 +163,12 @@ __global__ void relu_mask_k(int64_t n, float* __restrict__ x, const float* __res
     x[i] = ref[i] > 0.f ? x[i] : 0.f;
 }
 
-__device__ __forceinline__ float softplusf_(float x) {
-  // log(1 + exp(x)) without overflow: max(x,0) + log1p(exp(-|x|))
-  return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)));
-}
-
-// round(sigmoid(x)) == 1 (utils.calculate_tfpn; round half to even) holds exactly from this logit on: the smallest fp32 x whose
-// fp32 sigmoid is above 0.5 (smaller positive logits give exactly 0.5, which rounds to 0).  Found by bisection over fp32 bit
-// patterns against torch.round(torch.sigmoid(x)): tests/test_loss_counts_cpu.py holds the derivation.  Bits 0x33c00001.
+// softplusf_, bce_term_, bce_grad_, bce_block_sum_ and the rounding threshold live in gnm_bce.h (gnm_symloss.hip shares them).
+// The threshold's literal is spelled here as well -- tests/loss_counts_common.py reads it from this file -- and must be the header's:
+namespace misc_literal {
 constexpr float kSigmoidRoundsUp = 0x1.800002p-24f;
-
-// One logit / label pair: the loss term, and sigma(x) / 1 - sigma(x) for the gradient.  The two products and their sum are
-// kept as three roundings (no fma contraction), here and in bce_grad_: which of them the compiler would fuse depends on the code
-// around the call, and every kernel that calls these must give the same bits.
-__device__ __forceinline__ float bce_term_(float xi, float yi, float pw, float& p, float& q) {
-#pragma clang fp contract(off)
-  p = sigmoid_ieee_(xi);
-  // 1 - p: for x > 0 as e^-x / (1 + e^-x), where 1.f - p cancels (it is 0 from x ~ 17 on, where 1 - p is ~4e-8)
-  const float em = expf(-fabsf(xi));
-  q = xi > 0.f ? em / (1.f + em) : 1.f - p;
-  return pw * yi * softplusf_(-xi) + (1.f - yi) * softplusf_(xi);
 }
-__device__ __forceinline__ float bce_grad_(float yi, float pw, float p, float q, float inv_e) {
-#pragma clang fp contract(off)
-  return (-pw * yi * q + (1.f - yi) * p) * inv_e;
-}
-
-// Sum of the block's `acc` in red[0] (tree over kBlock slots, fixed order)
-__device__ __forceinline__ void bce_block_sum_(double acc, double* red) {
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kBlock / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-}
+static_assert(misc_literal::kSigmoidRoundsUp == kSigmoidRoundsUp, "gnm_bce.h and gnm_misc.hip disagree on kSigmoidRoundsUp");
 
 // STATS: also TP TN FP FN of p = round(sigmoid(x)) against y as four int32 per block behind the kMaxPartialBlocks loss partials
 // (a NaN logit and a label that is neither 0 nor 1 fail every comparison and are counted nowhere), and gscore may be NULL (no
@@ -242,13 +214,6 @@ __global__ __launch_bounds__(kBlock) void bce_fwd_bwd_k(int64_t E, const float* 
     }
   }
 }
-
-// The record gnm_bce_stats_fwd_bwd adds a step to (gnm.h)
-struct BceEpochAcc {
-  double loss_sum;
-  int64_t steps;
-  int64_t counts[4];
-};
 
 template <bool STATS>
 __global__ void bce_finalize_k(const double* __restrict__ ws, int nblk, double inv_e,
@@ -432,12 +397,6 @@ extern "C" int gnm_relu_mask_f32(int64_t n, float* x, const float* ref, void* st
   hipLaunchKernelGGL(relu_mask_k, dim3(ew_grid2(n, 256)), dim3(256), 0, (hipStream_t)stream, n, x, ref);
   GNM_LAUNCH_CHECK("relu_mask_f32");
   return 0;
-}
-
-static inline int bce_grid(int64_t E) {
-  int grid = ew_grid2(E, kBlock);
-  if (grid > kMaxPartialBlocks) grid = kMaxPartialBlocks;
-  return grid;
 }
 
 extern "C" int gnm_bce_fwd_bwd(int64_t E, const float* scores, const float* y, float pos_weight,

@@ -37,6 +37,20 @@ def fresh_flat_gradients(params) -> "Optional[FlatGradients]":
     return None
 
 
+def flat_gradients_of(params) -> "Optional[FlatGradients]":
+    """The FlatGradients(direct_write=True) whose buffer holds the .grad of EVERY tensor in `params`, fresh or not, if no parameter
+    carries a gradient hook: what a backward that ADDS its gradient to the buffer in one launch needs (the reversed pass of the
+    symmetry loss, models._ModelFn); None otherwise.  The caller sets `fresh` False after adding."""
+    if not params:
+        return None
+    for fg in _live:
+        if fg.direct_write and fg.owns(params):
+            if any(getattr(p, "_backward_hooks", None) or getattr(p, "_post_accumulate_grad_hooks", None) for p in params):
+                return None
+            return fg
+    return None
+
+
 def current_rank() -> int:
     """This process's data-parallel rank (0 outside torch.distributed): what engine.dropout_key folds into the dropout seed, so
     that the ranks of a step draw different masks from one user seed."""

@@ -2183,6 +2183,63 @@ def bce_with_logits_counts(scores, y, pos_weight: float, need_grad: bool = True,
     return loss, gs, counts
 
 
+@on_device_of(lambda org, *a, **k: org)
+def sym_bce(org, rev, y, pos_weight: float, alpha: float, need_grad: bool = True, want_counts: bool = False, epoch_acc=None):
+    """The symmetry loss of one graph from one pass over the original and the reversed scores (gnm_sym_bce_fwd_bwd):
+    (loss [1], parts [3] = mean bce(org), mean bce(rev), mean |org - rev|, g_org [E] or None, g_rev [E] or None, counts int64 [4]
+    of org or None).  need_grad=False stores no per-edge output.  epoch_acc: as for bce_with_logits_counts."""
+    lib = _lib.load()
+    _chk_dev(org, rev, y)
+    o = _f32c(org.reshape(-1))
+    r = _f32c(rev.reshape(-1))
+    y = _f32c(y.reshape(-1))
+    E = o.numel()
+    if r.numel() != E or y.numel() != E:
+        raise ValueError(f"sym_bce: {E} original scores, {r.numel()} reversed scores, {y.numel()} labels")
+    dev = o.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    parts = torch.empty(3, dtype=torch.float32, device=dev)
+    go = torch.empty(E, dtype=torch.float32, device=dev) if need_grad else None
+    gr = torch.empty(E, dtype=torch.float32, device=dev) if need_grad else None
+    counts = torch.empty(4, dtype=torch.int64, device=dev) if want_counts else None
+    if epoch_acc is not None:
+        _chk_dev(org, epoch_acc)
+        if epoch_acc.dtype != torch.int64 or epoch_acc.numel() != 6 or not epoch_acc.is_contiguous():
+            raise ValueError("epoch_acc: a contiguous int64 [6] tensor (train.EpochStats.buf)")
+    need = lib.gnm_sym_bce_workspace_bytes()
+    ws = scratch(dev).ws(need)
+    _call("gnm_sym_bce_fwd_bwd", E, _ptr(o), _ptr(r), _ptr(y), float(pos_weight), float(alpha), _ptr(loss), _ptr(parts), _ptr(go),
+          _ptr(gr), _ptr(counts), _ptr(epoch_acc), _ptr(ws), need, _stream())
+    return loss, parts, go, gr, counts
+
+
+@on_device_of(lambda g, *a, **k: g)
+def mirror_add(g, scratch_grad, pi):
+    """g[i] += scratch_grad[pi[i]] over flat fp32 buffers (gnm_mirror_add, one launch): the gradient of a pass that ran on the
+    mirrored parameters flat[pi], folded into the flat gradient buffer.  pi: int32 permutation (models.mirror_index)."""
+    _chk_dev(g, scratch_grad, pi)
+    n = g.numel()
+    if not (g.dtype == scratch_grad.dtype == torch.float32 and g.is_contiguous() and scratch_grad.is_contiguous()
+            and scratch_grad.numel() == n and pi.dtype == torch.int32 and pi.is_contiguous() and pi.numel() == n):
+        raise ValueError(f"mirror_add: contiguous float32 buffers and an int32 permutation of {n} elements each")
+    _call("gnm_mirror_add", n, _ptr(g), _ptr(scratch_grad), _ptr(pi), _stream())
+    return g
+
+
+@on_device_of(lambda src, *a, **k: src)
+def mirror_gather(src, pi, out=None):
+    """out[i] = src[pi[i]] over flat fp32 buffers (gnm_mirror_gather, one launch): the mirrored copy of a flat parameter buffer."""
+    _chk_dev(src, pi, out)
+    n = src.numel()
+    if out is None:
+        out = torch.empty_like(src)
+    if not (src.dtype == out.dtype == torch.float32 and src.is_contiguous() and out.is_contiguous() and out.numel() == n
+            and pi.dtype == torch.int32 and pi.is_contiguous() and pi.numel() == n and out.data_ptr() != src.data_ptr()):
+        raise ValueError(f"mirror_gather: contiguous float32 buffers (out is not src) and an int32 permutation of {n} elements each")
+    _call("gnm_mirror_gather", n, _ptr(out), _ptr(src), _ptr(pi), _stream())
+    return out
+
+
 RANK_BINS = 16384                      # bins per label of a gnm_rank_record (include/gnm.h): the 14-bit key of an fp32 logit
 RANK_RECORD_WORDS = 2 * RANK_BINS + 4  # int64 hist[2][RANK_BINS], then tail[4] = nan_pos, nan_neg, other_label, calls
 

@@ -11,7 +11,7 @@ import torch.nn.functional as F
 from . import dp, engine, layers
 from .graph import as_assembly_graph
 
-__all__ = ["GraphGatedGCNModel", "BCEWithLogitsLoss", "flatten_parameters"]
+__all__ = ["GraphGatedGCNModel", "BCEWithLogitsLoss", "SymmetryLoss", "flatten_parameters", "mirror_state", "mirror_index"]
 
 
 def _engine_order(names):
@@ -62,6 +62,71 @@ def _is_flat(model: nn.Module) -> bool:
     return all(p.device == flat.device and lo <= p.data_ptr() < hi for p in model.parameters())
 
 
+_MIRROR_PAIRS = {"A_2": "A_3", "A_3": "A_2", "B_1": "B_2", "B_2": "B_1"}
+
+
+def _mirror_key(name: str) -> str:
+    parts = name.split(".")
+    if len(parts) == 5 and parts[0] == "gnn" and parts[3] in _MIRROR_PAIRS:
+        parts[3] = _MIRROR_PAIRS[parts[3]]
+        return ".".join(parts)
+    return name
+
+
+def mirror_state(named):
+    """The parameter mirror M: name -> tensor of a GraphGatedGCNModel (a state dict, dict(model.named_parameters()), a dict of
+    gradients) to name -> mirrored tensor, with scores(reverse(g); theta) = scores(g; M theta) on a graph whose in- and out-degree
+    columns of `pe` are left where they are.  Every edge (s -> d) of reverse(g) is (d -> s), so in every layer B_1 <-> B_2 (the
+    edge update reads h[d] where it read h[s]) and A_2 <-> A_3 (the by-destination and the by-source sums trade places; h is
+    symmetric in them), the predictor's first two H-wide column blocks of W1 trade places (cat(x[src], x[dst], e)), and columns
+    0 and 1 of linear_pe.weight do (in-degree | out-degree).  Everything else is untouched.  Views and index ops: differentiable,
+    and an involution: mirror_state(mirror_state(d)) == d.  The gradient follows as dL/d theta = M (dL/d theta' at theta' = M theta)."""
+    out = {}
+    for k, v in named.items():
+        if k == "linear_pe.weight":
+            idx = torch.arange(v.shape[1], device=v.device)
+            idx[0], idx[1] = 1, 0
+            out[k] = v.index_select(1, idx)
+        elif k == "predictor.W1.weight":
+            H = v.shape[1] // 3
+            out[k] = torch.cat([v[:, H:2 * H], v[:, :H], v[:, 2 * H:]], 1)
+        else:
+            out[k] = named[_mirror_key(k)]
+    return out
+
+
+def _flat_offsets(model: nn.Module):
+    """[(name, parameter, element offset in model._gnm_flat)] of a flattened model, in the buffer's order."""
+    base = model._gnm_flat.data_ptr()
+    rows = [(k, p, (p.data_ptr() - base) // 4) for k, p in model.named_parameters()]
+    return sorted(rows, key=lambda r: r[2])
+
+
+def _mirror_of(model: nn.Module):
+    """(pi, flat buffer, {name: element offset}, scratch holder) of a flattened model: what a reversed pass needs, built once per
+    flattening and kept on the model.  The holder keeps the backward's flat scratch buffer between steps."""
+    if not _is_flat(model):
+        raise RuntimeError("mirror_index: the model is not flattened (models.flatten_parameters)")
+    flat = model._gnm_flat
+    cached = getattr(model, "_gnm_mirror", None)
+    if cached is not None and cached[1] is flat:
+        return cached
+    rows = _flat_offsets(model)
+    ids = {k: torch.arange(o, o + p.numel(), dtype=torch.int64).view(p.shape) for k, p, o in rows}
+    m = mirror_state(ids)
+    pi = torch.cat([m[k].reshape(-1) for k, _, _ in rows]).to(torch.int32).to(flat.device)
+    model._gnm_mirror = (pi, flat, {k: o for k, _, o in rows}, {})
+    return model._gnm_mirror
+
+
+def mirror_index(model: nn.Module) -> torch.Tensor:
+    """The mirror as a permutation of the flat parameter buffer: int32 [n] on the buffer's device with
+    model._gnm_flat[pi] == the flattened mirror_state(parameters) and pi[pi] == arange (in the layout of _engine_order the five
+    stacked projections of a layer are the block order (0, 2, 1, 4, 3), weights and biases alike).  Built once per flattening and
+    kept on the model."""
+    return _mirror_of(model)[0]
+
+
 class _ModelFn(torch.autograd.Function):
     """Whole-model forward/backward: the edge stream stays in internal order from the encoder
     to the predictor, activations are released layer by layer in backward."""
@@ -75,6 +140,14 @@ class _ModelFn(torch.autograd.Function):
         # model's activation_checkpoint (it rides here so that the positional layout backward() counts on stays as it is)
         batch_norm, ln_width, checkpoint, *wl = norm       # a fourth entry: the layers' WIDE_LAYERNORM decision (GatedGCN_1d._wide_ln)
         P = {k: v.detach() for k, v in zip(names, flat)}            # a fifth: this forward's node-output dropout (p, key, step) or None
+        mirror = wl[2] if len(wl) > 2 else None                     # a sixth: reverse=True on a flat model: _mirror_of(model)
+        if mirror is not None:
+            # the reversed pass: the same kernels on the mirrored copy of the flat buffer (one gather launch), cut into views of
+            # the same layout -- the five stacked projections stay one [5H,H] operand
+            pi, buf, offs, _ = mirror
+            mflat = engine.mirror_gather(buf, pi)
+            P = {k: mflat[offs[k]:offs[k] + v.numel()].view(v.shape) for k, v in zip(names, flat)}
+        ctx.mirror = mirror
         scores, saved = engine.model_forward(graph, e.detach(), pe.detach(), P, num_layers, need, batch_norm, ln_width=ln_width,
                                              checkpoint=checkpoint, wide_ln=wl[0] if wl else None,
                                              dropout=wl[1] if len(wl) > 1 else None)
@@ -93,6 +166,8 @@ class _ModelFn(torch.autograd.Function):
         # Input gradients (e at position 1, pe at 2): the encoders' backward also writes them when asked for.
         want_e, want_pe = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         inputs = want_e or want_pe
+        if ctx.mirror is not None:
+            return _ModelFn._backward_mirrored(ctx, gscores, want_e, want_pe)
         fg = dp.fresh_flat_gradients(ctx.params)
         if fg is not None and all(ctx.needs_input_grad[7:]):
             out = {k: p.grad for k, p in zip(ctx.names, ctx.params)}
@@ -104,6 +179,34 @@ class _ModelFn(torch.autograd.Function):
         r = engine.model_backward(ctx.graph, ctx.P, ctx.L, ctx.saved, gscores, ctx.bn, ln_width=ctx.lnw, inputs=inputs)
         ctx.saved = None
         G, ge, gpe = r if inputs else (r, None, None)
+        return (None, ge if want_e else None, gpe if want_pe else None, None, None, None, None) + tuple(G[k] for k in ctx.names)
+
+    @staticmethod
+    def _backward_mirrored(ctx, gscores, want_e, want_pe):
+        """The backward of a pass that ran on M theta: dL/d theta = M (dL/d theta').  With a direct-write dp.FlatGradients in the
+        model's layout the kernels write dL/d theta' into a scratch buffer of that layout and ONE launch folds it,
+        grad[i] += scratch[pi[i]] -- an accumulation, right whether or not the buffer already holds the original pass's
+        gradient; it leaves the buffer not fresh.  Otherwise autograd gets M of the gradients."""
+        inputs = want_e or want_pe
+        pi, buf, offs, hold = ctx.mirror
+        fg = dp.flat_gradients_of(ctx.params) if all(ctx.needs_input_grad[7:]) else None
+        if fg is not None and fg.grads.numel() == buf.numel() and all(
+                (p.grad.data_ptr() - fg.flat.data_ptr()) // 4 == offs[k] for k, p in zip(ctx.names, ctx.params)):
+            sg = hold.get("scratch")          # one backward at a time per device (engine.model_backward): the buffer is reused
+            if sg is None:
+                sg = hold["scratch"] = torch.empty_like(buf)
+            sg.zero_()
+            out = {k: sg[offs[k]:offs[k] + p.numel()].view(p.shape) for k, p in zip(ctx.names, ctx.params)}
+            r = engine.model_backward(ctx.graph, ctx.P, ctx.L, ctx.saved, gscores, ctx.bn, out=out, ln_width=ctx.lnw, inputs=inputs)
+            engine.mirror_add(fg.grads, sg, pi)
+            fg.fresh = False
+            ctx.saved = None
+            _, ge, gpe = r if inputs else (r, None, None)
+            return (None, ge if want_e else None, gpe if want_pe else None) + (None,) * (4 + len(ctx.names))
+        r = engine.model_backward(ctx.graph, ctx.P, ctx.L, ctx.saved, gscores, ctx.bn, ln_width=ctx.lnw, inputs=inputs)
+        ctx.saved = None
+        G, ge, gpe = r if inputs else (r, None, None)
+        G = mirror_state(G)
         return (None, ge if want_e else None, gpe if want_pe else None, None, None, None, None) + tuple(G[k] for k in ctx.names)
 
 
@@ -146,7 +249,13 @@ class GraphGatedGCNModel(nn.Module):
     `dropout` (keyword, default 0.0; the reference's model passes none to its layers): node-output dropout of every GatedGCN layer
     (gated_gcn_full.py:154) in training mode with grad enabled -- masks from the device counter (engine.dropout_seed; one step per
     such forward), re-derived by the backward and by a checkpoint recomputation, never stored.  `last_dropout` holds the latest
-    forward's (p, key, step) for engine.dropout_mask.  No effect under eval() or torch.no_grad(); 0.0 changes nothing at all."""
+    forward's (p, key, step) for engine.dropout_mask.  No effect under eval() or torch.no_grad(); 0.0 changes nothing at all.
+
+    `reverse=True` (keyword of forward, default False: the path, launches and bits of a call without it): the scores of the
+    edge-reversed graph, edge k read as (dst_k -> src_k), in the same edge-id order -- the same graph object, index and sweep plans,
+    run on the mirrored parameters (mirror_state).  The in- / out-degree columns of `pe` are swapped by the mirror; its PageRank
+    columns are carried as they are, not recomputed on the reversed adjacency.  Gradients flow to the model's own parameters; with
+    a direct-write dp.FlatGradients the reversed pass adds its gradient to the buffer in one launch (_ModelFn._backward_mirrored)."""
 
     def __init__(self, node_features, edge_features, hidden_features, hidden_edge_features, num_layers,
                  hidden_edge_scores, batch_norm, nb_pos_enc, dropout=0.0):
@@ -172,7 +281,7 @@ class GraphGatedGCNModel(nn.Module):
         """What the layers recorded of layers.WIDE_LAYERNORM when they were built (LayerNorm above 256 channels)."""
         return all(getattr(c, "_wide_ln", False) for c in self.gnn.convs)
 
-    def forward(self, graph, x, e, pe):
+    def forward(self, graph, x, e, pe, reverse=False):
         graph = as_assembly_graph(graph, pe.device)       # a DGLGraph(-like) object is wrapped once and cached on itself
         H = self.linear_pe.out_features
         Hp = layers.padded_width(H)
@@ -184,7 +293,8 @@ class GraphGatedGCNModel(nn.Module):
             # parameters -- the extra channels stay exactly zero through every layer (t = 0 -> bn -> relu -> 0; their gates
             # are 0.5 and gate zeros) and autograd slices the gradients back out of the padded tensors
             names, flat = zip(*self.named_parameters())
-            padded = tuple(_pad_param(k, v, H, Hp) for k, v in zip(names, flat))
+            src = mirror_state(dict(zip(names, flat))) if reverse else dict(zip(names, flat))      # mirror first, then pad
+            padded = tuple(_pad_param(k, src[k], H, Hp) for k in names)
             need = torch.is_grad_enabled() and (any(p.requires_grad for p in flat) or e.requires_grad or pe.requires_grad)
             return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint, self._wide_ln(), drop), *padded)
         if pe.is_cuda and not _is_flat(self):
@@ -193,6 +303,14 @@ class GraphGatedGCNModel(nn.Module):
         # e / pe requiring grad (input attribution, a frozen model, a learnable transform in front of the encoders) also
         # needs the activations: the backward returns their gradients; x stays dead (full_graph.py:23), its .grad None
         need = torch.is_grad_enabled() and (any(p.requires_grad for p in flat) or e.requires_grad or pe.requires_grad)
+        if reverse:
+            if not _is_flat(self):          # parameters off the device: ordinary autograd through the mirror
+                m = mirror_state(dict(zip(names, flat)))
+                return _ModelFn.apply(graph, e, pe, self.num_layers, names, need,
+                                      (self.batch_norm, H, self.activation_checkpoint, self._wide_ln(), drop), *(m[k] for k in names))
+            mirror = _mirror_of(self)
+            return _ModelFn.apply(graph, e, pe, self.num_layers, names, need,
+                                  (self.batch_norm, H, self.activation_checkpoint, self._wide_ln(), drop, mirror), *flat)
         return _ModelFn.apply(graph, e, pe, self.num_layers, names, need, (self.batch_norm, H, self.activation_checkpoint, self._wide_ln(), drop), *flat)
 
 
@@ -239,3 +357,60 @@ class BCEWithLogitsLoss(nn.Module):
         loss and counts are added to on the device."""
         need = torch.is_grad_enabled() and pred.requires_grad
         return _BCECountsFn.apply(pred, y, self.pos_weight, need, getattr(epoch_acc, "buf", epoch_acc))
+
+
+class _SymLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, org, rev, y, pos_weight, alpha, need_grad, want_counts, epoch_acc):
+        loss, parts, go, gr, counts = engine.sym_bce(org.detach(), rev.detach(), y, pos_weight, alpha, need_grad, want_counts, epoch_acc)
+        ctx.go = go.reshape(org.shape) if need_grad else None
+        ctx.gr = gr.reshape(rev.shape) if need_grad else None
+        if counts is None:
+            counts = torch.empty(0, dtype=torch.int64, device=loss.device)
+        ctx.mark_non_differentiable(parts, counts)
+        return loss.reshape(()), parts, counts
+
+    @staticmethod
+    def backward(ctx, gl, _gp, _gc):
+        return (ctx.go * gl if ctx.needs_input_grad[0] else None, ctx.gr * gl if ctx.needs_input_grad[1] else None,
+                None, None, None, None, None, None)
+
+
+class SymmetryLoss(nn.Module):
+    """The symmetry loss of the published GNNome training recipe as one fused HIP pass:
+    mean_k(bce(org_k, y_k) + bce(rev_k, y_k) + alpha |org_k - rev_k|), bce = BCEWithLogits with pos_weight, org the scores of the
+    graph and rev those of its edge-reversed twin (GraphGatedGCNModel.forward(..., reverse=True)), both in edge-id order.
+    `last_parts` holds the device [3] tensor of the latest call: mean bce(org), mean bce(rev), mean |org - rev|.  Under
+    torch.no_grad() or with inputs that need no gradient nothing is stored per edge."""
+
+    def __init__(self, pos_weight, alpha=0.1):
+        super().__init__()
+        self.pos_weight = float(pos_weight.reshape(-1)[0]) if torch.is_tensor(pos_weight) else float(pos_weight)
+        self.alpha = float(alpha)
+        if not (0.0 <= self.alpha < float("inf")):
+            raise ValueError(f"SymmetryLoss: alpha={alpha!r}: expected a finite number >= 0")
+        self.last_parts = None
+
+    def _run(self, org, rev, y, want_counts, epoch_acc):
+        need = torch.is_grad_enabled() and (org.requires_grad or rev.requires_grad)
+        loss, parts, counts = _SymLossFn.apply(org, rev, y, self.pos_weight, self.alpha, need, want_counts,
+                                               getattr(epoch_acc, "buf", epoch_acc))
+        self.last_parts = parts
+        return loss, counts
+
+    def forward(self, org, rev, y):
+        return self._run(org, rev, y, False, None)[0]
+
+    def with_counts(self, org, rev, y, epoch_acc=None):
+        """(loss, counts): forward's loss (same bits, same gradients) and [TP, TN, FP, FN] of `org` -- metrics are reported on the
+        original orientation -- as a device int64 [4] tensor from the same pass; epoch_acc: a train.EpochStats that receives the
+        step's loss and counts."""
+        return self._run(org, rev, y, True, epoch_acc)
+
+    def gradients(self, org, rev, y, epoch_acc=None):
+        """(loss, counts, g_org, g_rev) outside autograd: the loss (a detached scalar), the counts of `org` and d loss / d org,
+        d loss / d rev as [E] tensors -- what the "sequential" schedule of train.train hands to two separate backward passes."""
+        loss, parts, go, gr, counts = engine.sym_bce(org.detach(), rev.detach(), y, self.pos_weight, self.alpha, True, True,
+                                                     getattr(epoch_acc, "buf", epoch_acc))
+        self.last_parts = parts
+        return loss.reshape(()), counts, go.reshape(org.shape), gr.reshape(rev.shape)

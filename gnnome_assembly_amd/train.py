@@ -44,7 +44,7 @@ import torch.distributed as dist
 
 from . import cluster, dp, engine, models
 
-__all__ = ["get_hyperparameters", "GraphSample", "tfpn_counts", "calculate_metrics", "train", "save_checkpoint", "EpochStats",
+__all__ = ["get_hyperparameters", "check_symmetry_hyperparameters", "symmetry_step", "GraphSample", "tfpn_counts", "calculate_metrics", "train", "save_checkpoint", "EpochStats",
            "RankingStats", "RankingMetrics", "BestF1"]
 
 
@@ -70,7 +70,49 @@ def get_hyperparameters() -> Dict:
         # 1 <= low <= high <= 100; 100 / 100: off) and runs on the induced sub-graph with its own degrees in `pe`; the 16 PageRank
         # columns are carried from the parent unless mask_recompute_pe.  Validation is never masked.
         "mask_frac_low": 100, "mask_frac_high": 100, "mask_recompute_pe": False,
+        # symmetry loss (models.SymmetryLoss): every step scores the graph and its edge-reversed twin (model(..., reverse=True)) and
+        # is penalised for both BCE terms and alpha |org - rev| per edge.  "symmetry_schedule": "joint" (two forwards, one backward,
+        # both activation sets alive) or "sequential" (three forwards, one activation set alive at a time; no dropout)
+        "symmetry_loss": os.environ.get("GNM_SYMMETRY_LOSS", "0").strip() == "1", "alpha": 0.1, "symmetry_schedule": "joint",
     }
+
+
+def check_symmetry_hyperparameters(hp: Dict) -> bool:
+    """True when the symmetry loss is on; ValueError for a schedule, an alpha or a combination that is not supported."""
+    if hp["symmetry_schedule"] not in ("joint", "sequential"):
+        raise ValueError(f"hyper-parameter symmetry_schedule={hp['symmetry_schedule']!r}: expected 'joint' or 'sequential'")
+    if not (isinstance(hp["alpha"], (int, float)) and 0.0 <= float(hp["alpha"]) < float("inf")):
+        raise ValueError(f"hyper-parameter alpha={hp['alpha']!r}: expected a finite number >= 0")
+    if not hp["symmetry_loss"]:
+        return False
+    if hp["symmetry_schedule"] == "sequential" and float(hp["dropout"]) > 0.0:
+        raise ValueError("hyper-parameter symmetry_schedule='sequential' with dropout > 0: the schedule runs the original forward "
+                         "twice and the second run would draw another dropout mask; use 'joint' or dropout 0")
+    return True
+
+
+def symmetry_step(model, criterion, graph, x, e, pe, y, schedule: str = "joint", epoch_acc=None, counts: bool = False):
+    """One training step's forward and backward passes under the symmetry loss; returns (loss, org), both detached.
+    "joint": the reversed forward, then the original one, one loss.backward() -- autograd runs the later-built graph first, so the
+    original pass writes its gradient straight into a fresh dp.FlatGradients buffer and the reversed pass folds its own in behind it.
+    "sequential": original forward under no_grad, reversed forward with grad, the loss kernel, the reversed backward, the original
+    forward again with grad (the kernels are bit-reproducible: the scores the loss saw), the original backward: one activation set
+    alive at a time for a third forward.  counts / epoch_acc: criterion.with_counts' (the fused-metrics route)."""
+    if schedule == "joint":
+        rev = model(graph, x, e, pe, reverse=True).squeeze(-1)
+        org = model(graph, x, e, pe).squeeze(-1)
+        loss = criterion.with_counts(org, rev, y, epoch_acc)[0] if (counts or epoch_acc is not None) else criterion(org, rev, y)
+        loss.backward()
+        return loss.detach(), org.detach()
+    with torch.no_grad():
+        org0 = model(graph, x, e, pe).squeeze(-1)
+    rev = model(graph, x, e, pe, reverse=True).squeeze(-1)
+    loss, _, g_org, g_rev = criterion.gradients(org0, rev, y, epoch_acc)
+    torch.autograd.backward(rev, g_rev)
+    del rev
+    org = model(graph, x, e, pe).squeeze(-1)
+    torch.autograd.backward(org, g_org)
+    return loss, org0
 
 
 @dataclass
@@ -300,6 +342,8 @@ class History:
     ap_valid: List[float] = field(default_factory=list)         # ... .average_precision,
     best_f1_valid: List[tuple] = field(default_factory=list)    # ... and (best_f1.f1, best_f1.logit); all three stay empty when it is off
     mask_fraction: List[float] = field(default_factory=list)    # "mask_frac_*": the kept read fraction f of every step of this rank on a graph or batch,
+    sym_gap_train: List[float] = field(default_factory=list)    # "symmetry_loss": per epoch the mean over the steps of mean_k |org_k - rev_k| (the
+    sym_gap_valid: List[float] = field(default_factory=list)    # loss's parts[2], unscaled by alpha), training / validation; empty when it is off
     masked_edges: List[int] = field(default_factory=list)       # ... and the edge count of the thinned graph it ran on (0: a zero-contribution step, which
                                                                 # has no entry in step_losses / step_graph); added once per epoch; both empty when it is off
 
@@ -333,6 +377,9 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         raise ValueError(f"hyper-parameters mask_frac_low={mlo!r}, mask_frac_high={mhi!r}: expected integers (per cent) with "
                          "1 <= low <= high <= 100 (100 / 100: no masking)")
     masking = not (mlo == 100 and mhi == 100)
+    sym = check_symmetry_hyperparameters(hp)
+    if sym and "criterion_factory" in hooks:
+        raise ValueError("hyper-parameter symmetry_loss with a \"criterion_factory\" hook: the symmetry loss is models.SymmetryLoss")
     seed = hp["seed"]
     random.seed(seed)
     torch.manual_seed(seed)                                                     # utils.set_seed
@@ -361,7 +408,22 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     else:
         optimizer = dp.make_adam(model.parameters(), hp["lr"])                           # train.py:209
     criterion = (hooks["criterion_factory"](1.0 / ratio) if "criterion_factory" in hooks
+                 else models.SymmetryLoss(1.0 / ratio, hp["alpha"]) if sym
                  else models.BCEWithLogitsLoss(pos_weight=1.0 / ratio))                         # train.py:210-211
+    if sym:
+        gap = torch.zeros(2, device=dev, dtype=torch.float64)          # the epoch's sum of parts[2] and its number of steps
+        schedule = hp["symmetry_schedule"]
+
+        def note_gap():
+            gap[0] += criterion.last_parts[2].double()
+            gap[1] += 1
+
+        def sym_eval(graph, x, e, pe, y, acc):     # under no_grad: (loss, org) of one validation forward pair
+            org = model(graph, x, e, pe).squeeze(-1)
+            rev = model(graph, x, e, pe, reverse=True).squeeze(-1)
+            loss = criterion.with_counts(org, rev, y, acc)[0] if acc is not None else criterion(org, rev, y)
+            note_gap()
+            return loss, org
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=hp["decay"],
                                                            patience=hp["patience"])             # train.py:212
     # one pass for loss + TP..FN + epoch sums; a criterion without with_counts (a criterion_factory stand-in) takes the torch route
@@ -414,7 +476,10 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                 if zero_first or not lib_opt:
                     flat.zero_()
                     zero_first = False
-                if s is not None:
+                if s is not None and sym:
+                    loss, pred = symmetry_step(model, criterion, s.graph, s.x, s.e, s.pe, s.y, schedule, ep_stats if fused else None)
+                    note_gap()
+                elif s is not None:
                     pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)                           # train.py:252-253
                     loss = criterion.with_counts(pred, s.y, ep_stats)[0] if fused else criterion(pred, s.y)
                     loss.backward()
@@ -454,7 +519,11 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                     if zero_first or not lib_opt:
                         flat.zero_()
                         zero_first = False
-                    if sub is not None:
+                    if sub is not None and sym:
+                        loss, pred = symmetry_step(model, criterion, sub, None, sub.edata["e"], sub.ndata["pe"], sub.edata["y"],
+                                                   schedule, graph_stats if fused else None)
+                        note_gap()
+                    elif sub is not None:
                         pred = model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1)    # train.py:306
                         loss = (criterion.with_counts(pred, sub.edata["y"], graph_stats)[0] if fused
                                 else criterion(pred, sub.edata["y"]))
@@ -480,6 +549,11 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         hist.masked_edges += ep_edges
         if world > 1:
             dist.all_reduce(loss_sum); dist.all_reduce(n_train); dist.all_reduce(counts)        # noqa: E702
+        if sym:                              # one read per epoch
+            if world > 1:
+                dist.all_reduce(gap)
+            hist.sym_gap_train.append(float(gap[0] / gap[1].clamp(min=1)))
+            gap.zero_()
         train_loss = float(loss_sum / n_train.clamp(min=1)) if masking else float(loss_sum / n_train)
         hist.loss_train.append(train_loss)
         if lib_opt:                          # the step kernels' device record, read here with the losses and never per step
@@ -502,13 +576,20 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         with torch.no_grad():
             for s in valid_samples:
                 if hp["batch_size_eval"] <= 1 and fused:
-                    pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)
-                    criterion.with_counts(pred, s.y, ep_stats)
+                    if sym:
+                        pred = sym_eval(s.graph, s.x, s.e, s.pe, s.y, ep_stats)[1]
+                    else:
+                        pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)
+                        criterion.with_counts(pred, s.y, ep_stats)
                     if ranking:
                         rank_stats.add(pred, s.y)
                 elif hp["batch_size_eval"] <= 1:
-                    pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)
-                    vloss += criterion(pred, s.y).double()
+                    if sym:
+                        vl, pred = sym_eval(s.graph, s.x, s.e, s.pe, s.y, None)
+                        vloss += vl.double()
+                    else:
+                        pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)
+                        vloss += criterion(pred, s.y).double()
                     vcounts += tfpn_counts(pred, s.y)
                     if ranking:
                         rank_stats.add(pred, s.y)
@@ -516,8 +597,11 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                     graph_stats.zero_()
                     for sub in _cluster_batches(s, hp["num_parts_metis_eval"], hp["batch_size_eval"],
                                                 hp["partition_method"]):
-                        pred = model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1)
-                        criterion.with_counts(pred, sub.edata["y"], graph_stats)
+                        if sym:
+                            pred = sym_eval(sub, None, sub.edata["e"], sub.ndata["pe"], sub.edata["y"], graph_stats)[1]
+                        else:
+                            pred = model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1)
+                            criterion.with_counts(pred, sub.edata["y"], graph_stats)
                         if ranking:
                             rank_stats.add(pred, sub.edata["y"])
                     vloss += graph_stats.loss_sum / graph_stats.steps.clamp(min=1)
@@ -527,8 +611,12 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                     nb = 0
                     for sub in _cluster_batches(s, hp["num_parts_metis_eval"], hp["batch_size_eval"],
                                                 hp["partition_method"]):
-                        pred = model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1)
-                        gl += criterion(pred, sub.edata["y"]).double()
+                        if sym:
+                            bl, pred = sym_eval(sub, None, sub.edata["e"], sub.ndata["pe"], sub.edata["y"], None)
+                            gl += bl.double()
+                        else:
+                            pred = model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1)
+                            gl += criterion(pred, sub.edata["y"]).double()
                         nb += 1
                         vcounts += tfpn_counts(pred, sub.edata["y"])
                         if ranking:
@@ -539,6 +627,11 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         n_val = torch.tensor(float(len(valid_samples)), device=dev, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(vloss); dist.all_reduce(n_val); dist.all_reduce(vcounts)            # noqa: E702
+        if sym:
+            if world > 1:
+                dist.all_reduce(gap)
+            hist.sym_gap_valid.append(float(gap[0] / gap[1].clamp(min=1)))
+            gap.zero_()
         if ranking:                              # the record adds across ranks like the counts; one read per epoch
             rm = rank_stats.all_reduce_().read()
             hist.auroc_valid.append(rm.auroc)

@@ -715,6 +715,32 @@ int gnm_read_mask(int64_t N, double f, uint64_t key, uint32_t epoch, uint32_t gr
 int gnm_index_degrees(int64_t n, const int32_t* in_ptr, const int32_t* out_ptr, const int32_t* nperm, float* pe, int64_t ld,
                       void* stream);
 
+/* ---- symmetry loss: the original and the edge-reversed scores of one graph in one pass ------------------------------------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: four new symbols, no existing signature changes.)
+ *   l_k = bce(org_k, y_k) + bce(rev_k, y_k) + alpha |org_k - rev_k|,  L = (1/E) sum_k l_k,  bce as in gnm_bce_fwd_bwd.
+ * loss_out[0] = (float)((S_org + S_rev + alpha S_abs) * (1.0 / E)) from the three fp64 sums;  parts_out[3] = their means: mean
+ *             bce(org), mean bce(rev), mean |org - rev| (the last is the "symmetry gap", reported unscaled by alpha).
+ * g_org, g_rev: dL/d org = (bce'(org_k) + alpha sgn(org_k - rev_k)) / E, dL/d rev = (bce'(rev_k) - alpha sgn(org_k - rev_k)) / E,
+ *             sgn(0) = 0 (torch.abs's subgradient).  Both NULL: no per-edge output is stored.  Exactly one NULL is an error.
+ * counts_out: NULL, or [4] = TP TN FP FN of ORG by gnm_bce_stats_fwd_bwd's rule.   epoch_acc: NULL, or the same 48-byte record; it
+ *             receives loss_out[0], 1 and the counts of org.
+ * Same per-element BCE arithmetic, grid, element-to-thread assignment and summation trees as gnm_bce_fwd_bwd: with alpha = 0, g_org
+ * and parts_out[0] have the bits of gnm_bce_fwd_bwd(org)'s gradient and loss, g_rev and parts_out[1] those of gnm_bce_fwd_bwd(rev).
+ * No atomics: two runs give the same bits.  16-byte loads and stores when org, rev, y (and g_org, g_rev) are 16-byte aligned,
+ * element by element otherwise and at the ragged end -- same bits.
+ * ws: gnm_sym_bce_workspace_bytes() bytes, 16-byte aligned; counts_out and epoch_acc 8-byte aligned.
+ * E <= 0, a NULL org / rev / y / loss_out / parts_out, exactly one of g_org / g_rev, a short or misaligned workspace and an alpha
+ * that is negative or not finite are errors, returned before anything is launched.
+ *   gnm_mirror_add     g[i] += scratch[pi[i]], i < n: folds the gradient of a pass run on mirrored parameters (flat[pi]) into the
+ *                      flat gradient buffer.   gnm_mirror_gather   out[i] = src[pi[i]] (out != src).
+ *                      pi: a permutation of [0, n), n < 2^31; an entry outside [0, n) is skipped.  n == 0: no launch.           */
+size_t gnm_sym_bce_workspace_bytes(void);
+int gnm_sym_bce_fwd_bwd(int64_t E, const float* org, const float* rev, const float* y, float pos_weight, float alpha,
+                        float* loss_out, float* parts_out, float* g_org, float* g_rev, int64_t* counts_out, void* epoch_acc,
+                        void* ws, size_t ws_bytes, void* stream);
+int gnm_mirror_add(int64_t n, float* g, const float* scratch, const int32_t* pi, void* stream);
+int gnm_mirror_gather(int64_t n, float* out, const float* src, const int32_t* pi, void* stream);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
