@@ -137,6 +137,7 @@ SIGNATURES = {
     "gnm_sym_bce_fwd_bwd": (_i32, [_i64, _p, _p, _p, _f32, _f32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gnm_mirror_add": (_i32, [_i64, _p, _p, _p, _p]),
     "gnm_mirror_gather": (_i32, [_i64, _p, _p, _p, _p]),
+    "gnm_decision_stats": (_i32, [_i64, _i64] + [_p] * 14),
 }
 
 

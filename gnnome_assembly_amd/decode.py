@@ -31,7 +31,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["DecodeGraph", "sample_edges", "get_contigs", "get_contigs_device", "infer_contigs"]
+__all__ = ["DecodeGraph", "sample_edges", "get_contigs", "get_contigs_device", "infer_contigs", "decision_table"]
 
 
 def _p(a: np.ndarray):
@@ -217,17 +217,43 @@ def get_contigs_device(graph: DecodeGraph, scores, prefix_length, read_length, n
     return contigs
 
 
+def decision_table(graph, scores, y=None):
+    """The choices the greedy walks make on `scores`, for every node at once (gnm_decision_stats, one launch): returns
+    (best_succ, best_pred, DecisionMetrics).  best_succ[v] / best_pred[v] (int32 [N] on the graph's device, the CALLER's node
+    numbering) are the edge ids of the top-scored out-edge / in-edge of node v -- what walk_forwards / walk_backwards take at v
+    while all its neighbours are free (inference.py:45-51) -- with self loops left out, ties to the lowest edge id, NaN below
+    every number, and -1 where v has no candidate.  `graph`: an AssemblyGraph on a HIP device; `scores` [E] in edge-id order;
+    `y` [E] (optional): the edge labels, for the accuracy counters; without it the metrics hold the node counts (dead, forced,
+    branch, branch_nan) alone and every accuracy is NaN.  The walks themselves stay on the host and do not read the tables."""
+    from .graph import as_assembly_graph
+    from .train import DecisionStats
+    g = as_assembly_graph(graph)
+    dev = g.device
+    if dev.type != "cuda":
+        raise _lib.GnmError("decision_table: the graph must be on a HIP device (no CPU fallback)")
+    n = g.num_nodes()
+    best_succ = torch.empty(n, dtype=torch.int32, device=dev)
+    best_pred = torch.empty(n, dtype=torch.int32, device=dev)
+    st = DecisionStats(dev).add(g, scores, y, best_succ, best_pred)
+    return best_succ, best_pred, st.read()
+
+
 def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int = 50, len_threshold: int = 20,
-                  device_sampling: bool = False):
+                  device_sampling: bool = False, decision_report: bool = False):
     """The per-graph body of inference.inference (inference.py:444-490): logits of the whole graph under
     no_grad in eval mode, stored by edge id, then greedy decode.  Returns (scores [E], walks).
     device_sampling=True: the logits stay on the device for `get_contigs_device` (same distribution of start edges,
-    other random numbers); False is `get_contigs` with the reference's seeded draws."""
+    other random numbers); False is `get_contigs` with the reference's seeded draws.
+    decision_report=True: returns (scores, walks, report) with report = decision_table(graph, scores, graph.edata.get('y')) --
+    the per-node best successor / predecessor edges and their counts, taken before the walks, which it does not change."""
     model.eval()
     with torch.no_grad():
         scores = model(graph, None, e, pe).squeeze(-1)                 # inference.py:453-454
+    report = decision_table(graph, scores, getattr(graph, "edata", {}).get("y")) if decision_report else None
     src, dst = graph.edges()
     dg = DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), graph.num_nodes())
     if device_sampling:
-        return scores, get_contigs_device(dg, scores, prefix_length, read_length, nb_paths, len_threshold)
-    return scores, get_contigs(dg, scores, prefix_length, read_length, nb_paths, len_threshold)
+        walks = get_contigs_device(dg, scores, prefix_length, read_length, nb_paths, len_threshold)
+    else:
+        walks = get_contigs(dg, scores, prefix_length, read_length, nb_paths, len_threshold)
+    return (scores, walks, report) if decision_report else (scores, walks)

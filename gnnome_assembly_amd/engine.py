@@ -2262,6 +2262,41 @@ def rank_hist(scores, y, record):
     _call("gnm_rank_hist", E, _ptr(x), _ptr(y), _ptr(record), _ptr(ws), need, _stream())
 
 
+DECISION_COUNTERS = ("dead", "forced", "forced_ok", "branch", "branch_solvable", "branch_ok", "branch_nan")
+DECISION_RECORD_WORDS = 2 * len(DECISION_COUNTERS) + 1   # int64 dir[2][7] (successors, predecessors), then calls (include/gnm.h)
+
+
+@on_device_of(lambda idx, scores, y, record, *a, **k: record)
+def decision_stats(idx, scores, y, record, best_succ=None, best_pred=None):
+    """Add the walk decisions of one graph to `record` (gnm_decision_stats, one launch on the current stream): per node the
+    top-scored out-edge and in-edge, self loops left out, ties to the lowest edge id, NaN below every number.
+    idx: the graph's index (dict of graph.index(device)); scores [E] in edge-id order; y [E] labels or None (then only dead,
+    forced, branch and branch_nan move); record: a contiguous int64 [DECISION_RECORD_WORDS] device tensor
+    (train.DecisionStats.buf), which the caller zeroes once; best_succ / best_pred: None, or contiguous int32 [n] tensors that
+    receive the chosen edge ids in the CALLER's node numbering (-1: no candidate)."""
+    n = int(idx["in_ptr"].numel()) - 1
+    nperm = idx.get("nperm")
+    _chk_dev(scores, y, record, best_succ, best_pred, nperm, *[idx[k] for k in ("perm", "isrc", "idst", "in_ptr", "out_ptr", "out_pos", "out_dst")])
+    x = _f32c(scores.detach().reshape(-1).float())     # .float(): a half or bf16 tensor is compared as its fp32 copy (exact widening)
+    E = x.numel()
+    if E != idx["perm"].numel():
+        raise ValueError(f"decision_stats: {E} scores for an index of {idx['perm'].numel()} edges")
+    if y is not None:
+        y = _f32c(y.reshape(-1).float())
+        if y.numel() != E:
+            raise ValueError(f"decision_stats: {E} scores, {y.numel()} labels")
+    if record.dtype != torch.int64 or record.numel() != DECISION_RECORD_WORDS or not record.is_contiguous():
+        raise ValueError(f"decision_stats: record must be a contiguous int64 [{DECISION_RECORD_WORDS}] tensor (train.DecisionStats.buf)")
+    for name, t in (("best_succ", best_succ), ("best_pred", best_pred)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f"decision_stats: {name} must be a contiguous int32 [{n}] tensor")
+    if any(idx[k].dtype != torch.int32 or not idx[k].is_contiguous() for k in ("perm", "isrc", "idst", "in_ptr", "out_ptr", "out_pos", "out_dst")):
+        raise ValueError("decision_stats: the index arrays must be contiguous int32 tensors (graph.index())")
+    _call("gnm_decision_stats", n, E, _ptr(idx["perm"]), _ptr(idx["isrc"]), _ptr(idx["idst"]), _ptr(idx["in_ptr"]), _ptr(idx["out_ptr"]),
+          _ptr(idx["out_pos"]), _ptr(idx["out_dst"]), _ptr(nperm), _ptr(x), _ptr(y), _ptr(record), _ptr(best_succ), _ptr(best_pred),
+          _stream())
+
+
 def optim_workspace(n: int, device) -> torch.Tensor:
     """The workspace of optim_step for flat buffers of n elements (gnm_optim_workspace_bytes), as int64 words: 8-byte aligned."""
     return torch.empty((_lib.load().gnm_optim_workspace_bytes(int(n)) + 7) // 8, dtype=torch.int64, device=device)

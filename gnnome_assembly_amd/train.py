@@ -23,6 +23,13 @@ Differences from the reference, all deliberate:
     logits to a per-label histogram on the device (RankingStats, one launch, no sort, nothing of size [E]); once per epoch the 256 KiB
     record is read and History gains the threshold-free figures the fixed sigmoid(x) = 0.5 counts cannot give: AUROC, average
     precision and the best-F1 threshold.  Loss, schedule, best-model choice and every other History field are the same either way;
+  * with the hyper-parameter "decision_metrics" (default: GNM_DECISION_METRICS=1, else off) every validation forward also counts the
+    choices the greedy decode would make on its logits (DecisionStats: per node the top-scored out-edge and in-edge, one launch);
+    once per epoch the 15-word record is read and History.decision_valid gains (branch_accuracy, solvable_accuracy, successor-side and
+    predecessor-side branch accuracy): how often, at a node where the walk has a choice, the chosen edge is a correct one.  With
+    batch_size_eval > 1 the decisions are counted on each batch's sub-graph and summed: a node at a cut sees only the candidates
+    inside its batch, so it may count as forced or dead where the whole graph would have made it a branch.  Under the symmetry loss
+    the original scores are counted.  Loss, schedule, best-model choice and every other History field are the same either way;
   * with the hyper-parameters "mask_frac_low" / "mask_frac_high" (per cent; default 100 / 100: off) every training step runs on the graph
     thinned to a random fraction of its READS (cluster.masked_subgraph: a device mask that is a pure function of seed, epoch, graph and
     read; the thinned graph's own degrees in `pe`), the next step's graph built on a side stream meanwhile (cluster.MaskedGraphLoader);
@@ -45,7 +52,7 @@ import torch.distributed as dist
 from . import cluster, dp, engine, models
 
 __all__ = ["get_hyperparameters", "check_symmetry_hyperparameters", "symmetry_step", "GraphSample", "tfpn_counts", "calculate_metrics", "train", "save_checkpoint", "EpochStats",
-           "RankingStats", "RankingMetrics", "BestF1"]
+           "RankingStats", "RankingMetrics", "BestF1", "DecisionStats", "DecisionMetrics", "DecisionCounts"]
 
 
 def get_hyperparameters() -> Dict:
@@ -66,6 +73,8 @@ def get_hyperparameters() -> Dict:
         "clip_grad_norm": 0.0,
         # AUROC, average precision and the best-F1 threshold of every validation epoch from a histogram of the logits (RankingStats)
         "ranking_metrics": os.environ.get("GNM_RANKING_METRICS", "0").strip() == "1",
+        # how often the greedy decode's choice at a node (top-scored out-edge / in-edge) is a correct edge, per validation epoch (DecisionStats)
+        "decision_metrics": os.environ.get("GNM_DECISION_METRICS", "0").strip() == "1",
         # read-masking coverage augmentation: every TRAINING step keeps a fraction f = randint(low, high) / 100 of the reads (per cent,
         # 1 <= low <= high <= 100; 100 / 100: off) and runs on the induced sub-graph with its own degrees in `pe`; the 16 PageRank
         # columns are carried from the parent unless mask_recompute_pe.  Validation is never masked.
@@ -275,6 +284,113 @@ class RankingStats:
         return RankingMetrics.from_counts(b[:2 * RANK_BINS], b[2 * RANK_BINS:])
 
 
+DECISION_COUNTERS = engine.DECISION_COUNTERS                   # the seven counters of gnm_decision_record.dir[d], in order
+DECISION_RECORD_WORDS = engine.DECISION_RECORD_WORDS           # dir[2][7] (successors, predecessors), then calls
+
+
+def _ratio(num: int, den: int) -> float:
+    return float(num) / float(den) if den else float("nan")
+
+
+@dataclass
+class DecisionCounts:
+    """One direction's counters of a gnm_decision_record (or the two directions' sums) and their ratios; a ratio whose denominator
+    is 0 is NaN.  branch_accuracy: of the nodes where the walk has a choice (two or more candidate edges), the fraction whose
+    top-scored candidate is a correct edge (y == 1); solvable_accuracy: the same over the nodes where some candidate IS correct
+    (the others cannot be got right); forced_accuracy: of the nodes with exactly one candidate, the fraction where it is correct."""
+    dead: int = 0
+    forced: int = 0
+    forced_ok: int = 0
+    branch: int = 0
+    branch_solvable: int = 0
+    branch_ok: int = 0
+    branch_nan: int = 0
+
+    @property
+    def branch_accuracy(self) -> float:
+        return _ratio(self.branch_ok, self.branch)
+
+    @property
+    def solvable_accuracy(self) -> float:
+        return _ratio(self.branch_ok, self.branch_solvable)
+
+    @property
+    def forced_accuracy(self) -> float:
+        return _ratio(self.forced_ok, self.forced)
+
+    def __add__(self, other: "DecisionCounts") -> "DecisionCounts":
+        return DecisionCounts(*[getattr(self, k) + getattr(other, k) for k in DECISION_COUNTERS])
+
+
+@dataclass
+class DecisionMetrics:
+    """What a gnm_decision_record says about the choices the greedy decode would make on the scores: `succ` (walk_forwards: the
+    top-scored out-edge of every node), `pred` (walk_backwards: the top-scored in-edge) and `pooled` (their sums), each a
+    DecisionCounts; branch_accuracy / solvable_accuracy / forced_accuracy are the pooled ratios.  Host code on integers."""
+    succ: DecisionCounts
+    pred: DecisionCounts
+    pooled: DecisionCounts
+    calls: int = 0
+
+    @classmethod
+    def from_counts(cls, counts) -> "DecisionMetrics":
+        """counts: the DECISION_RECORD_WORDS int64 words of a record (DecisionStats.buf), or the 14 counters without `calls`."""
+        c = [int(v) for v in np.asarray(counts).reshape(-1).tolist()]
+        k = len(DECISION_COUNTERS)
+        if len(c) not in (2 * k, 2 * k + 1):
+            raise ValueError(f"DecisionMetrics.from_counts: {len(c)} words, expected {2 * k} or {2 * k + 1}")
+        if min(c) < 0:
+            raise ValueError("DecisionMetrics.from_counts: negative count")
+        succ, pred = DecisionCounts(*c[:k]), DecisionCounts(*c[k:2 * k])
+        return cls(succ, pred, succ + pred, c[2 * k] if len(c) > 2 * k else 0)
+
+    @property
+    def branch_accuracy(self) -> float:
+        return self.pooled.branch_accuracy
+
+    @property
+    def solvable_accuracy(self) -> float:
+        return self.pooled.solvable_accuracy
+
+    @property
+    def forced_accuracy(self) -> float:
+        return self.pooled.forced_accuracy
+
+    def summary(self) -> tuple:
+        """The History.decision_valid entry: (branch_accuracy, solvable_accuracy, succ branch_accuracy, pred branch_accuracy)."""
+        return (self.branch_accuracy, self.solvable_accuracy, self.succ.branch_accuracy, self.pred.branch_accuracy)
+
+
+class DecisionStats:
+    """A gnm_decision_record as one int64 tensor `buf` of DECISION_RECORD_WORDS words: dir[2][7] (successors, predecessors; the
+    counters of DECISION_COUNTERS) and calls.  add() is one launch on the current stream and needs a HIP device; the buffer itself
+    may live on the CPU (all_reduce_ under gloo, DecisionMetrics.from_counts).  Records add: across graphs, the sub-graphs of a
+    mini-batch pass and -- all_reduce_ -- ranks."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(DECISION_RECORD_WORDS, dtype=torch.int64, device=device)
+
+    def zero_(self):
+        self.buf.zero_()
+        return self
+
+    def add(self, graph, scores, y=None, best_succ=None, best_pred=None):
+        """Count the decisions of `graph` (an AssemblyGraph on the buffer's device) under `scores` [E] (edge-id order) and the
+        labels `y` [E] (None: only dead / forced / branch / branch_nan move)."""
+        from .graph import as_assembly_graph
+        idx = as_assembly_graph(graph, self.buf.device).index(self.buf.device)
+        engine.decision_stats(idx, scores, y, self.buf, best_succ, best_pred)
+        return self
+
+    def all_reduce_(self):
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.buf)
+        return self
+
+    def read(self) -> DecisionMetrics:
+        return DecisionMetrics.from_counts(self.buf.cpu().numpy())
+
+
 def calculate_metrics(TP, TN, FP, FN):
     """utils.calculate_metrics (utils.py:226-240), including its swapped precision/recall names."""
     recall = TP / (TP + FP) if (TP + FP) else 0
@@ -341,6 +457,8 @@ class History:
     auroc_valid: List[float] = field(default_factory=list)      # "ranking_metrics": per epoch RankingMetrics.auroc of the validation logits,
     ap_valid: List[float] = field(default_factory=list)         # ... .average_precision,
     best_f1_valid: List[tuple] = field(default_factory=list)    # ... and (best_f1.f1, best_f1.logit); all three stay empty when it is off
+    decision_valid: List[tuple] = field(default_factory=list)   # "decision_metrics": per epoch DecisionMetrics.summary() of the validation logits:
+                                                                # (branch_accuracy, solvable_accuracy, succ and pred branch accuracy); empty when it is off
     mask_fraction: List[float] = field(default_factory=list)    # "mask_frac_*": the kept read fraction f of every step of this rank on a graph or batch,
     sym_gap_train: List[float] = field(default_factory=list)    # "symmetry_loss": per epoch the mean over the steps of mean_k |org_k - rev_k| (the
     sym_gap_valid: List[float] = field(default_factory=list)    # loss's parts[2], unscaled by alpha), training / validation; empty when it is off
@@ -377,6 +495,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         raise ValueError(f"hyper-parameters mask_frac_low={mlo!r}, mask_frac_high={mhi!r}: expected integers (per cent) with "
                          "1 <= low <= high <= 100 (100 / 100: no masking)")
     masking = not (mlo == 100 and mhi == 100)
+    if not isinstance(hp["decision_metrics"], (bool, np.bool_)):
+        raise ValueError(f"hyper-parameter decision_metrics={hp['decision_metrics']!r}: expected True or False")
     sym = check_symmetry_hyperparameters(hp)
     if sym and "criterion_factory" in hooks:
         raise ValueError("hyper-parameter symmetry_loss with a \"criterion_factory\" hook: the symmetry loss is models.SymmetryLoss")
@@ -384,6 +504,9 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     random.seed(seed)
     torch.manual_seed(seed)                                                     # utils.set_seed
     dev = train_samples[0].pe.device
+    if hp["decision_metrics"] and dev.type != "cuda":
+        raise ValueError(f"hyper-parameter decision_metrics=True with the samples on {dev}: the decisions are counted by a kernel "
+                         "(gnm_decision_stats) and need a HIP device; there is no CPU route")
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     ratio = pos_to_neg_ratio(train_samples)                                     # train.py:181
@@ -433,6 +556,9 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     ranking = bool(hp["ranking_metrics"])
     if ranking:
         rank_stats = RankingStats(dev)                                 # the validation epoch's logit histogram
+    decision = bool(hp["decision_metrics"])
+    if decision:
+        dec_stats = DecisionStats(dev)                                 # the validation epoch's walk decisions
     if masking:
         # a generator of its own: the global `random` decides the shuffle order, which masking must not change
         mask_rng = random.Random(f"read-mask:{seed}")
@@ -573,6 +699,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
             ep_stats.zero_()
         if ranking:
             rank_stats.zero_()
+        if decision:
+            dec_stats.zero_()
         with torch.no_grad():
             for s in valid_samples:
                 if hp["batch_size_eval"] <= 1 and fused:
@@ -583,6 +711,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                         criterion.with_counts(pred, s.y, ep_stats)
                     if ranking:
                         rank_stats.add(pred, s.y)
+                    if decision:
+                        dec_stats.add(s.graph, pred, s.y)
                 elif hp["batch_size_eval"] <= 1:
                     if sym:
                         vl, pred = sym_eval(s.graph, s.x, s.e, s.pe, s.y, None)
@@ -593,6 +723,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                     vcounts += tfpn_counts(pred, s.y)
                     if ranking:
                         rank_stats.add(pred, s.y)
+                    if decision:
+                        dec_stats.add(s.graph, pred, s.y)
                 elif fused:
                     graph_stats.zero_()
                     for sub in _cluster_batches(s, hp["num_parts_metis_eval"], hp["batch_size_eval"],
@@ -604,6 +736,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                             criterion.with_counts(pred, sub.edata["y"], graph_stats)
                         if ranking:
                             rank_stats.add(pred, sub.edata["y"])
+                        if decision:
+                            dec_stats.add(sub, pred, sub.edata["y"])
                     vloss += graph_stats.loss_sum / graph_stats.steps.clamp(min=1)
                     vcounts += graph_stats.counts
                 else:                                                                           # train.py:428-486
@@ -621,6 +755,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                         vcounts += tfpn_counts(pred, sub.edata["y"])
                         if ranking:
                             rank_stats.add(pred, sub.edata["y"])
+                        if decision:
+                            dec_stats.add(sub, pred, sub.edata["y"])
                     vloss += gl / max(nb, 1)
         if fused and hp["batch_size_eval"] <= 1:
             vloss, vcounts = ep_stats.loss_sum.clone(), ep_stats.counts.clone()
@@ -637,6 +773,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
             hist.auroc_valid.append(rm.auroc)
             hist.ap_valid.append(rm.average_precision)
             hist.best_f1_valid.append((rm.best_f1.f1, rm.best_f1.logit) if rm.best_f1 is not None else None)
+        if decision:                             # 15 integers; they add across ranks like the counts; one read per epoch
+            hist.decision_valid.append(dec_stats.all_reduce_().read().summary())
         val_loss = float(vloss / n_val.clamp(min=1))
         hist.loss_valid.append(val_loss)
         hist.tfpn_valid.append(tuple(int(c) for c in vcounts.tolist()))

@@ -741,6 +741,42 @@ int gnm_sym_bce_fwd_bwd(int64_t E, const float* org, const float* rev, const flo
 int gnm_mirror_add(int64_t n, float* g, const float* scratch, const int32_t* pi, void* stream);
 int gnm_mirror_gather(int64_t n, float* out, const float* src, const int32_t* pi, void* stream);
 
+/* ---- walk decisions: per node the best-scored out- and in-edge, and how often that choice is a correct edge, in one pass --------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: one new symbol, no existing signature changes.)
+ * The greedy decode follows, at a node with several free successors, the out-edge with the top score (inference.py:45-51) and on
+ * the way back the top-scored in-edge; a contig breaks or goes chimeric when that one choice is wrong, which no edge-wise figure
+ * (loss, TP..FN, AUROC) shows.  DEVICE pointers; perm .. out_dst: the graph's index (gnm_graph_build_index), nperm: internal ->
+ * caller's node id, NULL: the identity.  scores, y [E]: fp32 in EDGE-ID order (y may be NULL).
+ * Candidates of internal node i.  Successors: p in [out_ptr[i], out_ptr[i+1]) -> internal position out_pos[p] -> edge id
+ *   perm[out_pos[p]], other end out_dst[p].  Predecessors: j in [in_ptr[i], in_ptr[i+1]) -> edge id perm[j], other end isrc[j].
+ *   A self loop is no candidate (the decode drops self loops from its candidates); duplicate edges are separate candidates.
+ *   idst is not read (in-edge j of node i ends in i) and may be NULL.
+ * Choice: the candidate with the largest score, the lowest edge id among equal scores.  -0 equals +0; denormals are not flushed;
+ *   a NaN orders below every number, -inf included, and NaNs tie (lowest edge id).  Compared on the full 32-bit form of the key
+ *   above: k(x) = 0 for a NaN, else u ^ ((u >> 31) ? 0xFFFFFFFF : 0x80000000) with u = bits(x == -0 ? +0 : x); (k, -eid) under
+ *   a plain integer maximum.
+ * best_succ / best_pred [n] (int32, either may be NULL): the chosen edge id of node v in the CALLER's numbering, -1 when v has no
+ *   candidate.  A row nperm[i] outside [0, n) is checked before use and never written.
+ * record: ADDS, per direction d (0: successors, 1: predecessors), to
+ *   dir[d][0] dead             nodes with no candidate
+ *   dir[d][1] forced           nodes with exactly one candidate         dir[d][2] forced_ok        ... whose label y == 1
+ *   dir[d][3] branch           nodes with two or more candidates        dir[d][4] branch_solvable  ... some candidate has y == 1
+ *   dir[d][5] branch_ok        ... the chosen edge has y == 1           dir[d][6] branch_nan       ... the chosen score is NaN
+ *   and calls += 1.  A label other than 1 (0.5, NaN) counts as not 1.  y == NULL: only dead, forced, branch and branch_nan move.
+ *   n == 0 or E == 0 is a valid call (E == 0: every node is dead).  The caller zeroes the record; records add across calls,
+ *   graphs and ranks.  8-byte aligned.
+ * One launch: eight lanes per node stride over its candidates and reduce by shuffles; counters go through registers and LDS to one
+ * 64-bit integer atomic per counter and workgroup.  All fields are integer sums, which commute, and a table entry depends on its
+ * node alone: neither depends on the grid, gnm_set_occupancy_cap or the order in which the atomics land, and two runs give the
+ * same bits.  No float atomics, no workspace, nothing allocated.  Every position and edge id read from the index is range-checked
+ * before it addresses anything (an entry outside [0, E) drops that candidate).
+ * n or E negative or >= 2^31 - 1, a NULL or misaligned record, NULL row pointers with n > 0 and NULL perm / isrc / out_pos /
+ * out_dst / scores with E > 0 are errors, returned before anything is launched.                                                 */
+typedef struct gnm_decision_record { int64_t dir[2][7]; int64_t calls; } gnm_decision_record;
+int gnm_decision_stats(int64_t n, int64_t E, const int32_t* perm, const int32_t* isrc, const int32_t* idst, const int32_t* in_ptr,
+                       const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, const int32_t* nperm,
+                       const float* scores, const float* y, void* record, int32_t* best_succ, int32_t* best_pred, void* stream);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
