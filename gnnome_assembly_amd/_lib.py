@@ -138,6 +138,8 @@ SIGNATURES = {
     "gnm_mirror_add": (_i32, [_i64, _p, _p, _p, _p]),
     "gnm_mirror_gather": (_i32, [_i64, _p, _p, _p, _p]),
     "gnm_decision_stats": (_i32, [_i64, _i64] + [_p] * 14),
+    "gnm_bog_workspace_bytes": (_sz, [_i64]),
+    "gnm_bog_contigs": (_i32, [_i64, _i64] + [_p] * 8 + [_f32] + [_p] * 7 + [_sz, _p]),
 }
 
 

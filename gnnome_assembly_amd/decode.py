@@ -19,11 +19,17 @@ Differences from the reference, both deliberate:
 `get_contigs_device` is the opt-in form whose O(E) work per iteration -- the candidate list of the not-yet-visited
 sub-graph, the sigmoid, the normalisation and the draw -- runs on the device where the logits already are
 (gnm_decode_candidate_sums / gnm_decode_pick, inverse-CDF sampling), and whose candidate walks run side by side on host
-threads (gnm_decode_iteration_mt).  It draws from the same distribution as `sample_edges`, not the same random numbers."""
+threads (gnm_decode_iteration_mt).  It draws from the same distribution as `sample_edges`, not the same random numbers.
+
+`best_overlap_contigs` is a second, deterministic decoder that runs on the device as a whole (gnm_bog_contigs): the mutual-best
+edges of the scores form disjoint paths, which list ranking turns into contigs; `resolve_strands` then keeps one strand per read.
+A different algorithm from the greedy walk, not a faster form of it: the walk follows a forced single successor even when that
+edge is not the successor's best predecessor, the cover does not."""
 from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 from typing import Callable, List, Optional
 
 import numpy as np
@@ -31,7 +37,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["DecodeGraph", "sample_edges", "get_contigs", "get_contigs_device", "infer_contigs", "decision_table"]
+__all__ = ["DecodeGraph", "sample_edges", "get_contigs", "get_contigs_device", "infer_contigs", "decision_table",
+           "best_overlap_contigs", "BogContigs", "BogStats", "resolve_strands", "ResolvedContigs", "n50"]
 
 
 def _p(a: np.ndarray):
@@ -238,18 +245,190 @@ def decision_table(graph, scores, y=None):
     return best_succ, best_pred, st.read()
 
 
+def n50(lengths) -> int:
+    """The N50 of a set of lengths: the largest L such that the lengths >= L sum to at least half of the total; 0 for none."""
+    a = np.sort(np.asarray(lengths, dtype=np.int64).reshape(-1))[::-1]
+    if a.size == 0:
+        return 0
+    cum = np.cumsum(a)
+    return int(a[int(np.searchsorted(cum, (int(cum[-1]) + 1) // 2))])
+
+
+@dataclass
+class BogStats:
+    """A gnm_bog_record (include/gnm.h): contigs, links (kept, after the cycle cuts), cycles_cut, dropped (mutual-best edges
+    refused for a NaN score or min_logit), wrong_links (links whose label is not 1), multi_nodes / multi_contigs (nodes on and
+    number of paths of two or more nodes), calls."""
+    contigs: int = 0
+    links: int = 0
+    cycles_cut: int = 0
+    dropped: int = 0
+    wrong_links: int = 0
+    multi_nodes: int = 0
+    multi_contigs: int = 0
+    calls: int = 0
+
+    @property
+    def wrong_link_fraction(self) -> float:
+        return float(self.wrong_links) / float(self.links) if self.links else float("nan")
+
+    def words(self) -> List[int]:
+        return [self.contigs, self.links, self.cycles_cut, self.dropped, self.wrong_links, self.multi_nodes, self.multi_contigs,
+                self.calls]
+
+
+class BogContigs:
+    """The best-overlap contigs of one graph, on the graph's device: contig c holds the nodes
+    walk_nodes[contig_ptr[c] : contig_ptr[c+1]] in walk order, joined by the edges walk_edges[...] (-1 at a contig's first node);
+    bases[c] is its length in bases (get_contig_length), wrong[c] the number of its links whose label is not 1 (0 without labels).
+    Contigs are numbered by ascending id of their first node.  `stats`: BogStats.  The host views are copied once, on first use."""
+
+    def __init__(self, contig_ptr, walk_nodes, walk_edges, bases, wrong, stats: BogStats, prefix_length, read_length):
+        self.contig_ptr, self.walk_nodes, self.walk_edges, self.bases, self.wrong = contig_ptr, walk_nodes, walk_edges, bases, wrong
+        self.stats = stats
+        self.prefix_length, self.read_length = prefix_length, read_length
+        self._host = None
+
+    def __len__(self):
+        return int(self.bases.numel())
+
+    def host(self):
+        """dict of numpy arrays: contig_ptr, walk_nodes, walk_edges, bases, wrong, prefix_length, read_length."""
+        if self._host is None:
+            self._host = {k: getattr(self, k).cpu().numpy() for k in
+                          ("contig_ptr", "walk_nodes", "walk_edges", "bases", "wrong", "prefix_length", "read_length")}
+        return self._host
+
+    def num_nodes(self) -> torch.Tensor:
+        """int32 [C] on the device: the number of nodes of every contig."""
+        return self.contig_ptr[1:] - self.contig_ptr[:-1]
+
+    def walks(self, min_nodes: int = 1) -> List[List[int]]:
+        """The contigs of at least `min_nodes` nodes as lists of node ids, in the format get_contigs returns."""
+        h = self.host()
+        ptr, nodes = h["contig_ptr"], h["walk_nodes"]
+        return [nodes[ptr[c]:ptr[c + 1]].tolist() for c in range(ptr.size - 1) if ptr[c + 1] - ptr[c] >= min_nodes]
+
+    def _bases(self, min_nodes: int) -> np.ndarray:
+        h = self.host()
+        return h["bases"][np.diff(h["contig_ptr"]) >= min_nodes]
+
+    def n50(self, min_nodes: int = 1) -> int:
+        return n50(self._bases(min_nodes))
+
+    def longest(self, min_nodes: int = 1) -> int:
+        b = self._bases(min_nodes)
+        return int(b.max()) if b.size else 0
+
+
+def best_overlap_contigs(graph, scores, prefix_length, read_length, y=None, min_logit: float = float("-inf")) -> BogContigs:
+    """Contigs of the best-overlap graph of `scores`, computed on the device: an edge is kept only when it is the top-scored
+    out-edge of its source AND the top-scored in-edge of its destination (the tables of gnm_decision_stats; self loops out, ties
+    to the lowest edge id, NaN lowest), not NaN and >= min_logit.  Every node then has at most one successor and one predecessor;
+    a cycle is cut at its smallest node id; the paths are the contigs (gnm_bog_contigs: list ranking by pointer jumping).
+    Deterministic: no sampling, no host walk, the same bits on every run.  `graph`: an AssemblyGraph on a HIP device; `scores`
+    [E] in edge-id order; prefix_length [E], read_length [N] (g.edata['prefix_length'], g.ndata['read_length']); `y` [E]
+    (optional): the labels, for the wrong-link counts.  One host synchronisation: the read of the 8-word record, for the contig
+    count.  The two strands of a read may both be covered: see resolve_strands."""
+    from . import engine
+    from .graph import as_assembly_graph
+    from .train import DecisionStats
+    g = as_assembly_graph(graph)
+    dev = g.device
+    if dev.type != "cuda":
+        raise _lib.GnmError("best_overlap_contigs: the graph must be on a HIP device (no CPU fallback)")
+    n, E = g.num_nodes(), g.num_edges()
+    pl = torch.as_tensor(prefix_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    rl = torch.as_tensor(read_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    if pl.numel() != E or rl.numel() != n or scores.numel() != E:
+        raise ValueError("scores / prefix_length need one entry per edge, read_length one per node")
+    with torch.cuda.device(dev):
+        i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
+        best_succ, best_pred = i32(n), i32(n)
+        DecisionStats(dev).add(g, scores, y, best_succ, best_pred)
+        src, dst = g.edges()
+        rec = torch.zeros(engine.BOG_RECORD_WORDS, dtype=torch.int64, device=dev)
+        contig_ptr, walk_nodes, walk_edges, wrong = i32(n + 1), i32(n), i32(n), i32(n)
+        bases = torch.empty(n, dtype=torch.int64, device=dev)
+        engine.bog_contigs(src, dst, best_succ, best_pred, scores, y, pl, rl, rec, contig_ptr, walk_nodes, walk_edges, bases, wrong,
+                           min_logit)
+        stats = BogStats(*[int(v) for v in rec.cpu().tolist()])        # the one synchronisation
+    C = stats.contigs
+    return BogContigs(contig_ptr[:C + 1], walk_nodes, walk_edges, bases[:C], wrong[:C], stats, pl, rl)
+
+
+@dataclass
+class ResolvedContigs:
+    """resolve_strands' result: the kept pieces as lists of node ids and their lengths in bases, in the order they were kept."""
+    walks: List[List[int]]
+    bases: List[int]
+
+
+def resolve_strands(contigs: BogContigs, len_threshold: int = 20) -> ResolvedContigs:
+    """One strand per read.  Nodes 2i and 2i+1 are the two strands of read i, and the best-overlap cover may hold a read on two
+    different paths (typically a contig and its reverse complement).  Host side, plain numpy and Python:
+      * the contigs are taken by bases descending, among equals by ascending id of their first node;
+      * a contig's nodes are walked in order; a node whose read is already taken ends the current piece and belongs to none;
+      * a piece of at least `len_threshold` nodes is kept and its reads are marked taken; a shorter piece is dropped and its reads
+        are NOT marked;
+      * a read that is already in the current piece (both strands on one path) ends the piece too; when the piece is dropped the
+        node starts the next one, when it is kept the node is skipped like any taken one.
+    A piece's length in bases is the sum of prefix_length over its inner links plus the read_length of its last node."""
+    h = contigs.host()
+    ptr, nodes, edges, pl, rl = h["contig_ptr"], h["walk_nodes"], h["walk_edges"], h["prefix_length"], h["read_length"]
+    thr = max(1, int(len_threshold))
+    C = ptr.size - 1
+    order = sorted(range(C), key=lambda c: (-int(h["bases"][c]), c))
+    taken = np.zeros(int(rl.size // 2 + 1), np.bool_)
+    walks, bases = [], []
+
+    def close(lo, hi):                       # the piece of positions [lo, hi): kept or dropped; True when kept
+        if hi - lo < thr:
+            return False
+        piece = nodes[lo:hi]
+        taken[piece >> 1] = True
+        walks.append(piece.tolist())
+        bases.append(int(pl[edges[lo + 1:hi]].sum()) + int(rl[piece[-1]]))
+        return True
+
+    for c in order:
+        if ptr[c + 1] - ptr[c] < thr:        # no piece of it can reach the threshold
+            continue
+        lo, inside = int(ptr[c]), set()
+        for pos in range(int(ptr[c]), int(ptr[c + 1])):
+            r = int(nodes[pos]) >> 1
+            if taken[r]:
+                close(lo, pos)
+                lo, inside = pos + 1, set()
+            elif r in inside:
+                kept = close(lo, pos)
+                lo, inside = (pos + 1, set()) if kept else (pos, {r})
+            else:
+                inside.add(r)
+        close(lo, int(ptr[c + 1]))
+    return ResolvedContigs(walks, bases)
+
+
 def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int = 50, len_threshold: int = 20,
-                  device_sampling: bool = False, decision_report: bool = False):
+                  device_sampling: bool = False, decision_report: bool = False, decoder: str = "greedy"):
     """The per-graph body of inference.inference (inference.py:444-490): logits of the whole graph under
     no_grad in eval mode, stored by edge id, then greedy decode.  Returns (scores [E], walks).
     device_sampling=True: the logits stay on the device for `get_contigs_device` (same distribution of start edges,
     other random numbers); False is `get_contigs` with the reference's seeded draws.
     decision_report=True: returns (scores, walks, report) with report = decision_table(graph, scores, graph.edata.get('y')) --
-    the per-node best successor / predecessor edges and their counts, taken before the walks, which it does not change."""
+    the per-node best successor / predecessor edges and their counts, taken before the walks, which it does not change.
+    decoder="best_overlap": the walks are resolve_strands(best_overlap_contigs(graph, scores, ...), len_threshold).walks --
+    deterministic, computed on the device, no sampling (nb_paths and device_sampling are not used)."""
+    if decoder not in ("greedy", "best_overlap"):
+        raise ValueError(f"decoder {decoder!r}: expected 'greedy' or 'best_overlap'")
     model.eval()
     with torch.no_grad():
         scores = model(graph, None, e, pe).squeeze(-1)                 # inference.py:453-454
     report = decision_table(graph, scores, getattr(graph, "edata", {}).get("y")) if decision_report else None
+    if decoder == "best_overlap":
+        walks = resolve_strands(best_overlap_contigs(graph, scores, prefix_length, read_length,
+                                                     getattr(graph, "edata", {}).get("y")), len_threshold).walks
+        return (scores, walks, report) if decision_report else (scores, walks)
     src, dst = graph.edges()
     dg = DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), graph.num_nodes())
     if device_sampling:

@@ -2297,6 +2297,47 @@ def decision_stats(idx, scores, y, record, best_succ=None, best_pred=None):
           _stream())
 
 
+BOG_COUNTERS = ("contigs", "links", "cycles_cut", "dropped", "wrong_links", "multi_nodes", "multi_contigs", "calls")
+BOG_RECORD_WORDS = len(BOG_COUNTERS)       # the int64 words of a gnm_bog_record (include/gnm.h), in order
+
+
+@on_device_of(lambda src, dst, best_succ, best_pred, scores, y, prefix_length, read_length, record, *a, **k: record)
+def bog_contigs(src, dst, best_succ, best_pred, scores, y, prefix_length, read_length, record, contig_ptr, walk_nodes, walk_edges,
+                contig_bases, contig_wrong, min_logit: float = float("-inf")):
+    """The best-overlap contigs of one graph (gnm_bog_contigs: 2 ceil(log2 n) + 6 launches on the current stream, no host
+    synchronisation): the edges that are the best successor of their source and the best predecessor of their destination, cycles
+    cut at their smallest node, the resulting paths ranked and laid out.  Caller's node numbering, edge-id order.
+    src, dst [E] int32; best_succ, best_pred [n] int32 (decision_stats); scores [E]; y [E] labels or None; prefix_length [E] and
+    read_length [n] int64; record: a contiguous int64 [BOG_RECORD_WORDS] device tensor the call ADDS to (the caller zeroes it and
+    reads the contig count C from it); contig_ptr int32 [n+1]; walk_nodes, walk_edges, contig_wrong int32 [n]; contig_bases int64
+    [n] -- of contig_ptr / contig_bases / contig_wrong only the first C+1 / C / C entries are defined."""
+    lib = _lib.load()
+    _chk_dev(src, dst, best_succ, best_pred, scores, y, prefix_length, read_length, record, contig_ptr, walk_nodes, walk_edges,
+             contig_bases, contig_wrong)
+    n, E = int(best_succ.numel()), int(src.numel())
+    x = _f32c(scores.detach().reshape(-1).float())     # .float(): a half or bf16 tensor is compared as its fp32 copy (exact widening)
+    if x.numel() != E or dst.numel() != E:
+        raise ValueError(f"bog_contigs: {E} src entries, {dst.numel()} dst entries, {x.numel()} scores")
+    if y is not None:
+        y = _f32c(y.reshape(-1).float())
+        if y.numel() != E:
+            raise ValueError(f"bog_contigs: {E} scores, {y.numel()} labels")
+    if record.dtype != torch.int64 or record.numel() != BOG_RECORD_WORDS or not record.is_contiguous():
+        raise ValueError(f"bog_contigs: record must be a contiguous int64 [{BOG_RECORD_WORDS}] tensor")
+    for name, t, dt, m in (("src", src, torch.int32, E), ("dst", dst, torch.int32, E), ("best_succ", best_succ, torch.int32, n),
+                           ("best_pred", best_pred, torch.int32, n), ("prefix_length", prefix_length, torch.int64, E),
+                           ("read_length", read_length, torch.int64, n), ("contig_ptr", contig_ptr, torch.int32, n + 1),
+                           ("walk_nodes", walk_nodes, torch.int32, n), ("walk_edges", walk_edges, torch.int32, n),
+                           ("contig_bases", contig_bases, torch.int64, n), ("contig_wrong", contig_wrong, torch.int32, n)):
+        if t.dtype != dt or t.numel() != m or not t.is_contiguous():
+            raise ValueError(f"bog_contigs: {name} must be a contiguous {str(dt).replace('torch.', '')} [{m}] tensor")
+    need = lib.gnm_bog_workspace_bytes(n)
+    ws = scratch(record.device).ws(need) if need else None
+    _call("gnm_bog_contigs", n, E, _ptr(src), _ptr(dst), _ptr(best_succ), _ptr(best_pred), _ptr(x), _ptr(y), _ptr(prefix_length),
+          _ptr(read_length), float(min_logit), _ptr(record), _ptr(contig_ptr), _ptr(walk_nodes), _ptr(walk_edges), _ptr(contig_bases),
+          _ptr(contig_wrong), _ptr(ws), need, _stream())
+
+
 def optim_workspace(n: int, device) -> torch.Tensor:
     """The workspace of optim_step for flat buffers of n elements (gnm_optim_workspace_bytes), as int64 words: 8-byte aligned."""
     return torch.empty((_lib.load().gnm_optim_workspace_bytes(int(n)) + 7) // 8, dtype=torch.int64, device=device)

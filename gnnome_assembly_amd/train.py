@@ -30,6 +30,13 @@ Differences from the reference, all deliberate:
     batch_size_eval > 1 the decisions are counted on each batch's sub-graph and summed: a node at a cut sees only the candidates
     inside its batch, so it may count as forced or dead where the whole graph would have made it a branch.  Under the symmetry loss
     the original scores are counted.  Loss, schedule, best-model choice and every other History field are the same either way;
+  * with the hyper-parameter "assembly_metrics" (default: GNM_ASSEMBLY_METRICS=1, else off) every full-graph validation forward also
+    decodes its logits into the contigs of the best-overlap graph on the device (decode.best_overlap_contigs: mutual-best edges, list
+    ranking; the graph's edata["prefix_length"] / ndata["read_length"]) and keeps the bases and wrong-link counts of the contigs with at
+    least 20 nodes; once per epoch History.assembly_valid gains (contigs, N50 in bases, longest contig in bases, wrong links / links)
+    over the pooled contigs of the epoch's validation graphs.  Refused with batch_size_eval > 1 (a cover across cluster cuts means
+    nothing).  Under the symmetry loss the original scores are decoded.  Loss, schedule, best-model choice and every other History
+    field are the same either way;
   * with the hyper-parameters "mask_frac_low" / "mask_frac_high" (per cent; default 100 / 100: off) every training step runs on the graph
     thinned to a random fraction of its READS (cluster.masked_subgraph: a device mask that is a pure function of seed, epoch, graph and
     read; the thinned graph's own degrees in `pe`), the next step's graph built on a side stream meanwhile (cluster.MaskedGraphLoader);
@@ -52,7 +59,7 @@ import torch.distributed as dist
 from . import cluster, dp, engine, models
 
 __all__ = ["get_hyperparameters", "check_symmetry_hyperparameters", "symmetry_step", "GraphSample", "tfpn_counts", "calculate_metrics", "train", "save_checkpoint", "EpochStats",
-           "RankingStats", "RankingMetrics", "BestF1", "DecisionStats", "DecisionMetrics", "DecisionCounts"]
+           "RankingStats", "RankingMetrics", "BestF1", "DecisionStats", "DecisionMetrics", "DecisionCounts", "AssemblyStats"]
 
 
 def get_hyperparameters() -> Dict:
@@ -75,6 +82,8 @@ def get_hyperparameters() -> Dict:
         "ranking_metrics": os.environ.get("GNM_RANKING_METRICS", "0").strip() == "1",
         # how often the greedy decode's choice at a node (top-scored out-edge / in-edge) is a correct edge, per validation epoch (DecisionStats)
         "decision_metrics": os.environ.get("GNM_DECISION_METRICS", "0").strip() == "1",
+        # contig count, N50, longest contig and wrong-link share of the best-overlap contigs of every validation epoch (AssemblyStats)
+        "assembly_metrics": os.environ.get("GNM_ASSEMBLY_METRICS", "0").strip() == "1",
         # read-masking coverage augmentation: every TRAINING step keeps a fraction f = randint(low, high) / 100 of the reads (per cent,
         # 1 <= low <= high <= 100; 100 / 100: off) and runs on the induced sub-graph with its own degrees in `pe`; the 16 PageRank
         # columns are carried from the parent unless mask_recompute_pe.  Validation is never masked.
@@ -391,6 +400,54 @@ class DecisionStats:
         return DecisionMetrics.from_counts(self.buf.cpu().numpy())
 
 
+ASSEMBLY_MIN_NODES = 20      # History.assembly_valid pools the contigs of at least this many nodes (the decode's len_threshold)
+
+
+class AssemblyStats:
+    """The best-overlap contigs of an epoch's validation graphs: `rec`, the sum of their gnm_bog_records (int64 [8], host), and the
+    bases of the contigs of at least `min_nodes` nodes, pooled.  add() decodes one graph on the device (decode.best_overlap_contigs:
+    one host synchronisation) and needs a HIP device.  Under torch.distributed all_reduce_() sums the records and gathers the pooled
+    lengths (all_gather_object), once per epoch."""
+
+    def __init__(self, device, min_nodes: int = ASSEMBLY_MIN_NODES):
+        self.device = torch.device(device)
+        self.min_nodes = int(min_nodes)
+        self.zero_()
+
+    def zero_(self):
+        self.rec = np.zeros(engine.BOG_RECORD_WORDS, np.int64)
+        self.bases: List[int] = []
+        self.wrong: List[int] = []
+        return self
+
+    def add(self, graph, scores, y=None):
+        from . import decode
+        c = decode.best_overlap_contigs(graph, scores.detach(), graph.edata["prefix_length"], graph.ndata["read_length"], y)
+        self.rec += np.asarray(c.stats.words(), np.int64)
+        keep = c.num_nodes() >= self.min_nodes
+        self.bases += c.bases[keep].cpu().tolist()
+        self.wrong += c.wrong[keep].cpu().tolist()
+        return self
+
+    def all_reduce_(self):
+        if dist.is_available() and dist.is_initialized():
+            t = torch.from_numpy(self.rec).to(self.device)
+            dist.all_reduce(t)
+            self.rec = t.cpu().numpy()
+            parts = [None] * dist.get_world_size()
+            dist.all_gather_object(parts, (self.bases, self.wrong))
+            self.bases = [b for p in parts for b in p[0]]
+            self.wrong = [w for p in parts for w in p[1]]
+        return self
+
+    def summary(self) -> tuple:
+        """The History.assembly_valid entry: (contigs, n50_bases, longest_bases, wrong_link_fraction) -- the first three over the
+        pooled contigs, the last = wrong_links / links of the summed records (NaN without a link)."""
+        from .decode import n50
+        links, wrong = int(self.rec[1]), int(self.rec[4])
+        return (len(self.bases), n50(self.bases), max(self.bases, default=0), _ratio(wrong, links))
+
+
 def calculate_metrics(TP, TN, FP, FN):
     """utils.calculate_metrics (utils.py:226-240), including its swapped precision/recall names."""
     recall = TP / (TP + FP) if (TP + FP) else 0
@@ -459,6 +516,8 @@ class History:
     best_f1_valid: List[tuple] = field(default_factory=list)    # ... and (best_f1.f1, best_f1.logit); all three stay empty when it is off
     decision_valid: List[tuple] = field(default_factory=list)   # "decision_metrics": per epoch DecisionMetrics.summary() of the validation logits:
                                                                 # (branch_accuracy, solvable_accuracy, succ and pred branch accuracy); empty when it is off
+    assembly_valid: List[tuple] = field(default_factory=list)   # "assembly_metrics": per epoch AssemblyStats.summary() of the validation logits:
+                                                                # (contigs, n50_bases, longest_bases, wrong_link_fraction); empty when it is off
     mask_fraction: List[float] = field(default_factory=list)    # "mask_frac_*": the kept read fraction f of every step of this rank on a graph or batch,
     sym_gap_train: List[float] = field(default_factory=list)    # "symmetry_loss": per epoch the mean over the steps of mean_k |org_k - rev_k| (the
     sym_gap_valid: List[float] = field(default_factory=list)    # loss's parts[2], unscaled by alpha), training / validation; empty when it is off
@@ -497,6 +556,16 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     masking = not (mlo == 100 and mhi == 100)
     if not isinstance(hp["decision_metrics"], (bool, np.bool_)):
         raise ValueError(f"hyper-parameter decision_metrics={hp['decision_metrics']!r}: expected True or False")
+    if not isinstance(hp["assembly_metrics"], (bool, np.bool_)):
+        raise ValueError(f"hyper-parameter assembly_metrics={hp['assembly_metrics']!r}: expected True or False")
+    if hp["assembly_metrics"]:
+        if hp["batch_size_eval"] > 1:
+            raise ValueError("hyper-parameter assembly_metrics=True with batch_size_eval > 1: the contigs are decoded on the whole "
+                             "validation graph; a cover across cluster cuts means nothing")
+        for i, s in enumerate(valid_samples):
+            for where, key in (("edata", "prefix_length"), ("ndata", "read_length")):
+                if key not in getattr(s.graph, where, {}):
+                    raise ValueError(f"hyper-parameter assembly_metrics=True: validation sample {i} has no graph.{where}[{key!r}]")
     sym = check_symmetry_hyperparameters(hp)
     if sym and "criterion_factory" in hooks:
         raise ValueError("hyper-parameter symmetry_loss with a \"criterion_factory\" hook: the symmetry loss is models.SymmetryLoss")
@@ -507,6 +576,9 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     if hp["decision_metrics"] and dev.type != "cuda":
         raise ValueError(f"hyper-parameter decision_metrics=True with the samples on {dev}: the decisions are counted by a kernel "
                          "(gnm_decision_stats) and need a HIP device; there is no CPU route")
+    if hp["assembly_metrics"] and dev.type != "cuda":
+        raise ValueError(f"hyper-parameter assembly_metrics=True with the samples on {dev}: the contigs are decoded by kernels "
+                         "(gnm_decision_stats, gnm_bog_contigs) and need a HIP device; there is no CPU route")
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     ratio = pos_to_neg_ratio(train_samples)                                     # train.py:181
@@ -559,6 +631,9 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     decision = bool(hp["decision_metrics"])
     if decision:
         dec_stats = DecisionStats(dev)                                 # the validation epoch's walk decisions
+    assembly = bool(hp["assembly_metrics"])
+    if assembly:
+        asm_stats = AssemblyStats(dev)                                 # the validation epoch's best-overlap contigs
     if masking:
         # a generator of its own: the global `random` decides the shuffle order, which masking must not change
         mask_rng = random.Random(f"read-mask:{seed}")
@@ -701,6 +776,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
             rank_stats.zero_()
         if decision:
             dec_stats.zero_()
+        if assembly:
+            asm_stats.zero_()
         with torch.no_grad():
             for s in valid_samples:
                 if hp["batch_size_eval"] <= 1 and fused:
@@ -713,6 +790,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                         rank_stats.add(pred, s.y)
                     if decision:
                         dec_stats.add(s.graph, pred, s.y)
+                    if assembly:
+                        asm_stats.add(s.graph, pred, s.y)
                 elif hp["batch_size_eval"] <= 1:
                     if sym:
                         vl, pred = sym_eval(s.graph, s.x, s.e, s.pe, s.y, None)
@@ -725,6 +804,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                         rank_stats.add(pred, s.y)
                     if decision:
                         dec_stats.add(s.graph, pred, s.y)
+                    if assembly:
+                        asm_stats.add(s.graph, pred, s.y)
                 elif fused:
                     graph_stats.zero_()
                     for sub in _cluster_batches(s, hp["num_parts_metis_eval"], hp["batch_size_eval"],
@@ -775,6 +856,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
             hist.best_f1_valid.append((rm.best_f1.f1, rm.best_f1.logit) if rm.best_f1 is not None else None)
         if decision:                             # 15 integers; they add across ranks like the counts; one read per epoch
             hist.decision_valid.append(dec_stats.all_reduce_().read().summary())
+        if assembly:                             # eight integers summed, the pooled lengths gathered; once per epoch
+            hist.assembly_valid.append(asm_stats.all_reduce_().summary())
         val_loss = float(vloss / n_val.clamp(min=1))
         hist.loss_valid.append(val_loss)
         hist.tfpn_valid.append(tuple(int(c) for c in vcounts.tolist()))

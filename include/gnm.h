@@ -777,6 +777,48 @@ int gnm_decision_stats(int64_t n, int64_t E, const int32_t* perm, const int32_t*
                        const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, const int32_t* nperm,
                        const float* scores, const float* y, void* record, int32_t* best_succ, int32_t* best_pred, void* stream);
 
+/* ---- best-overlap contigs: mutual-best links, cycles cut, list ranking by pointer jumping, contig layout -- all on the device ------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: two new symbols, no existing signature changes.)
+ * The best-overlap graph of overlap-layout assemblers on the tables gnm_decision_stats writes: a deterministic decoder that needs
+ * no sampling and no host walk.  DEVICE pointers; everything in the CALLER's node numbering and edge-id order.
+ * Inputs: src, dst [E] int32; best_succ, best_pred [n] int32 (gnm_decision_stats); scores [E] fp32; y [E] fp32 or NULL;
+ *   prefix_length [E] int64; read_length [n] int64; min_logit (-inf: no cut).
+ * Links.  Edge k = (u -> v) is a link iff u != v, best_succ[u] == k, best_pred[v] == k, scores[k] is not NaN and
+ *   scores[k] >= min_logit.  A table entry outside [-1, E) or a src / dst entry outside [0, n) drops that candidate; each is
+ *   checked before it addresses anything.  Then next[u] = v, prev[v] = u, pedge[v] = k; else -1.
+ * Cycles.  A component in which every node has a prev is a cycle; it is cut at its smallest node id m: prev[m] = pedge[m] = -1
+ *   and next[old prev of m] = -1.  (Two mutual-best edges u -> v, v -> u are the smallest case.)
+ * Ranking.  Every node now lies on exactly one path (a node with no link is a path of one).  head(v): the path's first node;
+ *   rank(v): hops from the head; off(v): the int64 sum of prefix_length[pedge[w]] over the path from the head (excluded) to v
+ *   (included); wrong(v): the same sum over [y[pedge[w]] != 1], 0 everywhere when y == NULL.
+ * Contigs.  The heads in ascending node id are contigs 0 .. C-1.  Outputs (contig_ptr [n+1], the others [n]; of contig_ptr,
+ *   contig_bases and contig_wrong only the first C+1 / C / C entries are defined):
+ *   contig_ptr [C+1] int32; walk_nodes [n] int32 with walk_nodes[contig_ptr[c] + rank(v)] = v; walk_edges [n] int32 = pedge in
+ *   the same layout (-1 at a contig's first node); contig_bases [C] int64 = off(tail) + read_length[tail] (get_contig_length,
+ *   inference.py:20-28); contig_wrong [C] int32 = wrong(tail).
+ * record: ADDS to  contigs (C), links (kept links, after the cuts: n - C), cycles_cut, dropped (mutual-best edges refused for a
+ *   NaN score or min_logit), wrong_links (the sum of contig_wrong), multi_nodes (nodes on paths of >= 2 nodes), multi_contigs,
+ *   calls (+1).  The caller zeroes it; the host reads C from it -- the call's one synchronisation, and the caller's.  8-byte aligned.
+ * gnm_bog_contigs issues every launch on `stream`: 2 K + 6 of them, K = ceil(log2(max(n, 2))).  Pointer jumping runs as K fixed
+ * rounds per pass, one launch per round, reading one generation of the per-node state and writing the other: pass one carries the
+ * minimum id (a node whose pointer is still live after K rounds is on a cycle), pass two carries head, rank, off and wrong.  Head
+ * numbers and contig offsets are exclusive prefix sums over node-ordered flags / lengths in fixed blocks (block sums, one workgroup
+ * over the block sums, in-block scan).  No workgroup waits for another inside a kernel, nothing is read back between launches, no
+ * float arithmetic (the score enters through the one comparison), integer atomics on the eight record words only (one per counter
+ * and workgroup): the results depend on the inputs alone, not on the grid, gnm_set_occupancy_cap or timing.
+ * ws: gnm_bog_workspace_bytes(n) bytes (72 n and two block-sum arrays; 0 for n == 0 and for an n that is refused), 16-byte aligned.
+ * n == 0 and E == 0 are valid (E == 0: n contigs of one node).  n or E negative or >= 2^31 - 1, a NULL or misaligned record, NULL
+ * tables / read_length / outputs with n > 0, NULL src / dst / scores / prefix_length with E > 0 and a workspace that is NULL, short
+ * or misaligned are errors, returned before anything is launched.                                                                 */
+typedef struct gnm_bog_record {
+  int64_t contigs, links, cycles_cut, dropped, wrong_links, multi_nodes, multi_contigs, calls;
+} gnm_bog_record;
+size_t gnm_bog_workspace_bytes(int64_t n);
+int gnm_bog_contigs(int64_t n, int64_t E, const int32_t* src, const int32_t* dst, const int32_t* best_succ, const int32_t* best_pred,
+                    const float* scores, const float* y, const int64_t* prefix_length, const int64_t* read_length, float min_logit,
+                    void* record, int32_t* contig_ptr, int32_t* walk_nodes, int32_t* walk_edges, int64_t* contig_bases,
+                    int32_t* contig_wrong, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
