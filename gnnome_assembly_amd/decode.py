@@ -233,7 +233,7 @@ def decision_table(graph, scores, y=None):
     `y` [E] (optional): the edge labels, for the accuracy counters; without it the metrics hold the node counts (dead, forced,
     branch, branch_nan) alone and every accuracy is NaN.  The walks themselves stay on the host and do not read the tables."""
     from .graph import as_assembly_graph
-    from .train import DecisionStats
+    from .metrics import DecisionStats
     g = as_assembly_graph(graph)
     dev = g.device
     if dev.type != "cuda":
@@ -332,7 +332,7 @@ def best_overlap_contigs(graph, scores, prefix_length, read_length, y=None, min_
     count.  The two strands of a read may both be covered: see resolve_strands."""
     from . import engine
     from .graph import as_assembly_graph
-    from .train import DecisionStats
+    from .metrics import DecisionStats
     g = as_assembly_graph(graph)
     dev = g.device
     if dev.type != "cuda":

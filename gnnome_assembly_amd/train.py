@@ -19,31 +19,20 @@ Differences from the reference, all deliberate:
   * with the hyper-parameter "optimizer": "library" (default: GNM_OPTIM=library, else "torch") the step is dp.LibAdam's: two
     launches over the flat buffers that also leave the gradient zeroed for the next backward, clip the gradient's norm to
     "clip_grad_norm" (0: off) and skip a step whose gradient is not finite, counted in History.skipped_steps;
-  * with the hyper-parameter "ranking_metrics" (default: GNM_RANKING_METRICS=1, else off) every validation forward also adds its
-    logits to a per-label histogram on the device (RankingStats, one launch, no sort, nothing of size [E]); once per epoch the 256 KiB
-    record is read and History gains the threshold-free figures the fixed sigmoid(x) = 0.5 counts cannot give: AUROC, average
-    precision and the best-F1 threshold.  Loss, schedule, best-model choice and every other History field are the same either way;
-  * with the hyper-parameter "decision_metrics" (default: GNM_DECISION_METRICS=1, else off) every validation forward also counts the
-    choices the greedy decode would make on its logits (DecisionStats: per node the top-scored out-edge and in-edge, one launch);
-    once per epoch the 15-word record is read and History.decision_valid gains (branch_accuracy, solvable_accuracy, successor-side and
-    predecessor-side branch accuracy): how often, at a node where the walk has a choice, the chosen edge is a correct one.  With
-    batch_size_eval > 1 the decisions are counted on each batch's sub-graph and summed: a node at a cut sees only the candidates
-    inside its batch, so it may count as forced or dead where the whole graph would have made it a branch.  Under the symmetry loss
-    the original scores are counted.  Loss, schedule, best-model choice and every other History field are the same either way;
-  * with the hyper-parameter "assembly_metrics" (default: GNM_ASSEMBLY_METRICS=1, else off) every full-graph validation forward also
-    decodes its logits into the contigs of the best-overlap graph on the device (decode.best_overlap_contigs: mutual-best edges, list
-    ranking; the graph's edata["prefix_length"] / ndata["read_length"]) and keeps the bases and wrong-link counts of the contigs with at
-    least 20 nodes; once per epoch History.assembly_valid gains (contigs, N50 in bases, longest contig in bases, wrong links / links)
-    over the pooled contigs of the epoch's validation graphs.  Refused with batch_size_eval > 1 (a cover across cluster cuts means
-    nothing).  Under the symmetry loss the original scores are decoded.  Loss, schedule, best-model choice and every other History
-    field are the same either way;
+  * with the hyper-parameters "ranking_metrics", "decision_metrics" and "assembly_metrics" (defaults: GNM_RANKING_METRICS=1,
+    GNM_DECISION_METRICS=1, GNM_ASSEMBLY_METRICS=1, else off) every validation forward also feeds its logits to an observer on the
+    device (metrics.py: RankingStats, DecisionStats, AssemblyStats), read once per epoch: History gains AUROC, average precision and
+    the best-F1 threshold / the greedy decode's branch accuracies / contig count, N50, longest contig and wrong-link share of the
+    best-overlap contigs.  With batch_size_eval > 1 the decisions are counted on each batch's sub-graph and summed (a node at a cut
+    sees only the candidates inside its batch) and "assembly_metrics" is refused (a cover across cluster cuts means nothing).  Under
+    the symmetry loss the observers see the original scores.  Loss, schedule, best-model choice and every other History field are
+    the same either way;
   * with the hyper-parameters "mask_frac_low" / "mask_frac_high" (per cent; default 100 / 100: off) every training step runs on the graph
     thinned to a random fraction of its READS (cluster.masked_subgraph: a device mask that is a pure function of seed, epoch, graph and
     read; the thinned graph's own degrees in `pe`), the next step's graph built on a side stream meanwhile (cluster.MaskedGraphLoader);
     a thinned graph without an edge is a zero-contribution step; validation is never masked; History gains mask_fraction / masked_edges;
   * wandb and the data pipeline are out of scope.
-`calculate_metrics` keeps the reference's naming, in which "precision" and "recall" are swapped
-(utils.py:227-234)."""
+The counts, records and metric classes the loop uses live in metrics.py and are re-exported here."""
 from __future__ import annotations
 
 import copy
@@ -57,6 +46,9 @@ import torch
 import torch.distributed as dist
 
 from . import cluster, dp, engine, models
+from .metrics import (ASSEMBLY_MIN_NODES, DECISION_COUNTERS, DECISION_RECORD_WORDS, RANK_BINS, AssemblyStats, BestF1,  # noqa: F401
+                      DecisionCounts, DecisionMetrics, DecisionStats, EpochStats, RankingMetrics, RankingStats, _ratio,
+                      calculate_metrics, rank_bin_lower_edge, tfpn_counts)
 
 __all__ = ["get_hyperparameters", "check_symmetry_hyperparameters", "symmetry_step", "GraphSample", "tfpn_counts", "calculate_metrics", "train", "save_checkpoint", "EpochStats",
            "RankingStats", "RankingMetrics", "BestF1", "DecisionStats", "DecisionMetrics", "DecisionCounts", "AssemblyStats"]
@@ -109,6 +101,43 @@ def check_symmetry_hyperparameters(hp: Dict) -> bool:
     return True
 
 
+def _check_hyperparameters(hp: Dict, hooks: Dict, train_samples, valid_samples) -> None:
+    """ValueError for what train() refuses, before it seeds or builds anything: the optimizer and its clipping, the mask fractions, the
+    decision / assembly metrics and what the latter needs on the validation graphs, the symmetry loss (check_symmetry_hyperparameters),
+    and last -- only these look at a sample -- the metrics that have no CPU route."""
+    if hp["optimizer"] not in ("torch", "library"):
+        raise ValueError(f"hyper-parameter optimizer={hp['optimizer']!r}: expected 'torch' or 'library'")
+    if not float(hp["clip_grad_norm"]) >= 0.0:
+        raise ValueError(f"hyper-parameter clip_grad_norm={hp['clip_grad_norm']!r}: expected a number >= 0 (0: off)")
+    if hp["clip_grad_norm"] > 0 and hp["optimizer"] != "library":
+        raise ValueError("hyper-parameter clip_grad_norm > 0 needs \"optimizer\": \"library\": the torch route does not clip, and "
+                         "the value is not silently ignored")
+    mlo, mhi = hp["mask_frac_low"], hp["mask_frac_high"]
+    if not (isinstance(mlo, int) and isinstance(mhi, int) and 1 <= mlo <= mhi <= 100):
+        raise ValueError(f"hyper-parameters mask_frac_low={mlo!r}, mask_frac_high={mhi!r}: expected integers (per cent) with "
+                         "1 <= low <= high <= 100 (100 / 100: no masking)")
+    if not isinstance(hp["decision_metrics"], (bool, np.bool_)):
+        raise ValueError(f"hyper-parameter decision_metrics={hp['decision_metrics']!r}: expected True or False")
+    if not isinstance(hp["assembly_metrics"], (bool, np.bool_)):
+        raise ValueError(f"hyper-parameter assembly_metrics={hp['assembly_metrics']!r}: expected True or False")
+    if hp["assembly_metrics"]:
+        if hp["batch_size_eval"] > 1:
+            raise ValueError("hyper-parameter assembly_metrics=True with batch_size_eval > 1: the contigs are decoded on the whole "
+                             "validation graph; a cover across cluster cuts means nothing")
+        for i, s in enumerate(valid_samples):
+            for where, key in (("edata", "prefix_length"), ("ndata", "read_length")):
+                if key not in getattr(s.graph, where, {}):
+                    raise ValueError(f"hyper-parameter assembly_metrics=True: validation sample {i} has no graph.{where}[{key!r}]")
+    if check_symmetry_hyperparameters(hp) and "criterion_factory" in hooks:
+        raise ValueError("hyper-parameter symmetry_loss with a \"criterion_factory\" hook: the symmetry loss is models.SymmetryLoss")
+    if hp["decision_metrics"] and train_samples[0].pe.device.type != "cuda":
+        raise ValueError(f"hyper-parameter decision_metrics=True with the samples on {train_samples[0].pe.device}: the decisions are "
+                         "counted by a kernel (gnm_decision_stats) and need a HIP device; there is no CPU route")
+    if hp["assembly_metrics"] and train_samples[0].pe.device.type != "cuda":
+        raise ValueError(f"hyper-parameter assembly_metrics=True with the samples on {train_samples[0].pe.device}: the contigs are "
+                         "decoded by kernels (gnm_decision_stats, gnm_bog_contigs) and need a HIP device; there is no CPU route")
+
+
 def symmetry_step(model, criterion, graph, x, e, pe, y, schedule: str = "joint", epoch_acc=None, counts: bool = False):
     """One training step's forward and backward passes under the symmetry loss; returns (loss, org), both detached.
     "joint": the reversed forward, then the original one, one loss.backward() -- autograd runs the later-built graph first, so the
@@ -141,320 +170,6 @@ class GraphSample:
     pe: torch.Tensor              # [N, nb_pos_enc+2] = in_deg | out_deg | pe
     y: torch.Tensor               # [E] float labels
     x: Optional[torch.Tensor] = None
-
-
-def tfpn_counts(edge_predictions: torch.Tensor, edge_labels: torch.Tensor) -> torch.Tensor:
-    """[TP, TN, FP, FN] as a device int64 tensor (utils.calculate_tfpn without the .item() syncs)."""
-    p = torch.round(torch.sigmoid(edge_predictions))
-    return torch.stack([((p == 1) & (edge_labels == 1)).sum(), ((p == 0) & (edge_labels == 0)).sum(),
-                        ((p == 1) & (edge_labels == 0)).sum(), ((p == 0) & (edge_labels == 1)).sum()])
-
-
-class EpochStats:
-    """The running sums of an epoch (or of one graph's batches) on the device, in the 48-byte record that
-    BCEWithLogitsLoss.with_counts(..., epoch_acc=self) adds every step to: {double loss_sum; int64 steps; int64 counts[4]}.
-    loss_sum is the fp64 sum of the steps' fp32 losses in call order.  `loss_sum`, `steps` and `counts` are views of `buf`."""
-
-    def __init__(self, device):
-        self.buf = torch.zeros(6, dtype=torch.int64, device=device)
-        self.loss_sum = self.buf[0:1].view(torch.float64)[0]
-        self.steps = self.buf[1]
-        self.counts = self.buf[2:6]
-
-    def zero_(self):
-        self.buf.zero_()
-        return self
-
-    def read(self):
-        """(loss_sum, steps, (TP, TN, FP, FN)) with one device-to-host copy."""
-        b = self.buf.cpu()
-        return float(b[0:1].view(torch.float64)[0]), int(b[1]), tuple(int(c) for c in b[2:6].tolist())
-
-
-RANK_BINS = 16384            # bins per label: the 14-bit key of an fp32 logit (include/gnm.h, gnm_rank_record)
-
-
-def rank_bin_lower_edge(k) -> np.ndarray:
-    """The smallest fp32 value whose key is k (fp64 array): the logit threshold "predict positive from bin k upwards".  Invert
-    key = u >> 18 with u = bits ^ (sign ? 0xFFFFFFFF : 0x80000000): a bin of positive values starts at its smallest bit pattern, a
-    bin of negative values at its largest.  Bin 31 holds -inf alone among the values that are not NaN: its edge is -inf."""
-    u = np.asarray(k, dtype=np.uint64) << np.uint64(18)
-    bits = np.where(u >> np.uint64(31) != 0, u ^ np.uint64(0x80000000), ~u & np.uint64(0xFFFFFFFF))
-    with np.errstate(invalid="ignore"):              # the edges of the bins that only NaN patterns fall into
-        x = bits.astype(np.uint32).view(np.float32).astype(np.float64)
-    return np.where(np.isnan(x), np.where(u >> np.uint64(31) != 0, np.inf, -np.inf), x)
-
-
-@dataclass
-class BestF1:
-    """The threshold "positive iff logit >= logit" (the lower edge of bin `bin`) with the largest F1 = 2TP / (2TP + FP + FN) among
-    the occupied bins; of equal F1 values the highest bin.  prob = sigmoid(logit)."""
-    f1: float
-    logit: float
-    prob: float
-    bin: int
-    TP: int
-    TN: int
-    FP: int
-    FN: int
-
-
-@dataclass
-class RankingMetrics:
-    """What a gnm_rank_record says about how the logits order positives and negatives (host code, fp64 numpy on integers).
-    auroc counts a (positive, negative) pair in one bin as 1/2, auroc_lo as 0 and auroc_hi as 1: the exact Mann-Whitney AUROC of the
-    raw logits (ties 1/2) lies in [auroc_lo, auroc_hi], because two edges in different bins are ordered as their bins are."""
-    auroc: float
-    auroc_lo: float
-    auroc_hi: float
-    average_precision: float
-    best_f1: Optional[BestF1]
-    n_pos: int               # binned positives and negatives (NaN logits and other labels are in n_nan / n_other)
-    n_neg: int
-    n_nan: int
-    n_other: int
-    calls: int
-    hist: np.ndarray = field(repr=False, compare=False, default=None)       # int64 [2, RANK_BINS]: negatives, positives
-
-    @classmethod
-    def from_counts(cls, hist, tail) -> "RankingMetrics":
-        hist = np.asarray(hist, dtype=np.int64).reshape(2, RANK_BINS)
-        tail = np.asarray(tail, dtype=np.int64).reshape(4)
-        neg, pos = hist[0].astype(np.float64), hist[1].astype(np.float64)
-        P, N = float(pos.sum()), float(neg.sum())
-        nan = float("nan")
-        if P > 0 and N > 0:
-            above = P - np.cumsum(pos)                                        # positives in the bins above k
-            lo = float((neg * above).sum())
-            tie = float((neg * pos).sum())
-            auroc, auroc_lo, auroc_hi = (lo + 0.5 * tie) / (P * N), lo / (P * N), (lo + tie) / (P * N)
-        else:
-            auroc = auroc_lo = auroc_hi = nan
-        occ = np.flatnonzero(hist[0] + hist[1])[::-1]                         # occupied bins, from the top
-        best, ap = None, nan
-        if occ.size:
-            tp, fp = np.cumsum(pos[occ]), np.cumsum(neg[occ])                 # predicted positive from bin occ[i] upwards
-            if P > 0 and N > 0:
-                ap = float((pos[occ] / P * (tp / (tp + fp))).sum())           # sum over bins of (R_k - R_{k-1}) Prec_k
-            den = 2.0 * tp + fp + (P - tp)
-            f1 = np.where(den > 0, 2.0 * tp / np.where(den > 0, den, 1.0), 0.0)
-            i = int(np.argmax(f1))                                            # first maximum from the top: the highest bin
-            edge = float(rank_bin_lower_edge(occ[i]))
-            with np.errstate(over="ignore"):
-                prob = float(1.0 / (1.0 + np.exp(-edge)))
-            best = BestF1(float(f1[i]), edge, prob, int(occ[i]), int(tp[i]), int(N - fp[i]), int(fp[i]), int(P - tp[i]))
-        return cls(auroc, auroc_lo, auroc_hi, ap, best, int(P), int(N), int(tail[0] + tail[1]), int(tail[2]), int(tail[3]), hist)
-
-    def _curve(self):
-        occ = np.flatnonzero(self.hist[0] + self.hist[1])[::-1]
-        tp, fp = np.cumsum(self.hist[1][occ]).astype(np.float64), np.cumsum(self.hist[0][occ]).astype(np.float64)
-        return occ, tp, fp
-
-    def roc(self):
-        """(fpr, tpr, logit thresholds) over the occupied bins from the top; NaN where a class is empty."""
-        occ, tp, fp = self._curve()
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return fp / float(self.n_neg), tp / float(self.n_pos), rank_bin_lower_edge(occ)
-
-    def pr(self):
-        """(precision, recall, logit thresholds) over the occupied bins from the top."""
-        occ, tp, fp = self._curve()
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return tp / (tp + fp), tp / float(self.n_pos), rank_bin_lower_edge(occ)
-
-
-class RankingStats:
-    """A gnm_rank_record as one int64 tensor `buf` of 2 * RANK_BINS + 4 words: hist[2][RANK_BINS] (negatives, positives) and
-    tail[4] = nan_pos, nan_neg, other_label, calls (`hist` and `tail` are views).  add() is one launch on the current stream and
-    needs a HIP device; the buffer itself may live on the CPU (all_reduce_ under gloo, RankingMetrics.from_counts).  Records add:
-    across steps, graphs and -- all_reduce_ -- ranks."""
-
-    def __init__(self, device):
-        self.buf = torch.zeros(2 * RANK_BINS + 4, dtype=torch.int64, device=device)
-        self.hist = self.buf[:2 * RANK_BINS].view(2, RANK_BINS)
-        self.tail = self.buf[2 * RANK_BINS:]
-
-    def zero_(self):
-        self.buf.zero_()
-        return self
-
-    def add(self, scores, y):
-        from . import engine
-        engine.rank_hist(scores.detach(), y, self.buf)
-        return self
-
-    def all_reduce_(self):
-        if dist.is_available() and dist.is_initialized():
-            dist.all_reduce(self.buf)
-        return self
-
-    def read(self) -> RankingMetrics:
-        b = self.buf.cpu().numpy()
-        return RankingMetrics.from_counts(b[:2 * RANK_BINS], b[2 * RANK_BINS:])
-
-
-DECISION_COUNTERS = engine.DECISION_COUNTERS                   # the seven counters of gnm_decision_record.dir[d], in order
-DECISION_RECORD_WORDS = engine.DECISION_RECORD_WORDS           # dir[2][7] (successors, predecessors), then calls
-
-
-def _ratio(num: int, den: int) -> float:
-    return float(num) / float(den) if den else float("nan")
-
-
-@dataclass
-class DecisionCounts:
-    """One direction's counters of a gnm_decision_record (or the two directions' sums) and their ratios; a ratio whose denominator
-    is 0 is NaN.  branch_accuracy: of the nodes where the walk has a choice (two or more candidate edges), the fraction whose
-    top-scored candidate is a correct edge (y == 1); solvable_accuracy: the same over the nodes where some candidate IS correct
-    (the others cannot be got right); forced_accuracy: of the nodes with exactly one candidate, the fraction where it is correct."""
-    dead: int = 0
-    forced: int = 0
-    forced_ok: int = 0
-    branch: int = 0
-    branch_solvable: int = 0
-    branch_ok: int = 0
-    branch_nan: int = 0
-
-    @property
-    def branch_accuracy(self) -> float:
-        return _ratio(self.branch_ok, self.branch)
-
-    @property
-    def solvable_accuracy(self) -> float:
-        return _ratio(self.branch_ok, self.branch_solvable)
-
-    @property
-    def forced_accuracy(self) -> float:
-        return _ratio(self.forced_ok, self.forced)
-
-    def __add__(self, other: "DecisionCounts") -> "DecisionCounts":
-        return DecisionCounts(*[getattr(self, k) + getattr(other, k) for k in DECISION_COUNTERS])
-
-
-@dataclass
-class DecisionMetrics:
-    """What a gnm_decision_record says about the choices the greedy decode would make on the scores: `succ` (walk_forwards: the
-    top-scored out-edge of every node), `pred` (walk_backwards: the top-scored in-edge) and `pooled` (their sums), each a
-    DecisionCounts; branch_accuracy / solvable_accuracy / forced_accuracy are the pooled ratios.  Host code on integers."""
-    succ: DecisionCounts
-    pred: DecisionCounts
-    pooled: DecisionCounts
-    calls: int = 0
-
-    @classmethod
-    def from_counts(cls, counts) -> "DecisionMetrics":
-        """counts: the DECISION_RECORD_WORDS int64 words of a record (DecisionStats.buf), or the 14 counters without `calls`."""
-        c = [int(v) for v in np.asarray(counts).reshape(-1).tolist()]
-        k = len(DECISION_COUNTERS)
-        if len(c) not in (2 * k, 2 * k + 1):
-            raise ValueError(f"DecisionMetrics.from_counts: {len(c)} words, expected {2 * k} or {2 * k + 1}")
-        if min(c) < 0:
-            raise ValueError("DecisionMetrics.from_counts: negative count")
-        succ, pred = DecisionCounts(*c[:k]), DecisionCounts(*c[k:2 * k])
-        return cls(succ, pred, succ + pred, c[2 * k] if len(c) > 2 * k else 0)
-
-    @property
-    def branch_accuracy(self) -> float:
-        return self.pooled.branch_accuracy
-
-    @property
-    def solvable_accuracy(self) -> float:
-        return self.pooled.solvable_accuracy
-
-    @property
-    def forced_accuracy(self) -> float:
-        return self.pooled.forced_accuracy
-
-    def summary(self) -> tuple:
-        """The History.decision_valid entry: (branch_accuracy, solvable_accuracy, succ branch_accuracy, pred branch_accuracy)."""
-        return (self.branch_accuracy, self.solvable_accuracy, self.succ.branch_accuracy, self.pred.branch_accuracy)
-
-
-class DecisionStats:
-    """A gnm_decision_record as one int64 tensor `buf` of DECISION_RECORD_WORDS words: dir[2][7] (successors, predecessors; the
-    counters of DECISION_COUNTERS) and calls.  add() is one launch on the current stream and needs a HIP device; the buffer itself
-    may live on the CPU (all_reduce_ under gloo, DecisionMetrics.from_counts).  Records add: across graphs, the sub-graphs of a
-    mini-batch pass and -- all_reduce_ -- ranks."""
-
-    def __init__(self, device):
-        self.buf = torch.zeros(DECISION_RECORD_WORDS, dtype=torch.int64, device=device)
-
-    def zero_(self):
-        self.buf.zero_()
-        return self
-
-    def add(self, graph, scores, y=None, best_succ=None, best_pred=None):
-        """Count the decisions of `graph` (an AssemblyGraph on the buffer's device) under `scores` [E] (edge-id order) and the
-        labels `y` [E] (None: only dead / forced / branch / branch_nan move)."""
-        from .graph import as_assembly_graph
-        idx = as_assembly_graph(graph, self.buf.device).index(self.buf.device)
-        engine.decision_stats(idx, scores, y, self.buf, best_succ, best_pred)
-        return self
-
-    def all_reduce_(self):
-        if dist.is_available() and dist.is_initialized():
-            dist.all_reduce(self.buf)
-        return self
-
-    def read(self) -> DecisionMetrics:
-        return DecisionMetrics.from_counts(self.buf.cpu().numpy())
-
-
-ASSEMBLY_MIN_NODES = 20      # History.assembly_valid pools the contigs of at least this many nodes (the decode's len_threshold)
-
-
-class AssemblyStats:
-    """The best-overlap contigs of an epoch's validation graphs: `rec`, the sum of their gnm_bog_records (int64 [8], host), and the
-    bases of the contigs of at least `min_nodes` nodes, pooled.  add() decodes one graph on the device (decode.best_overlap_contigs:
-    one host synchronisation) and needs a HIP device.  Under torch.distributed all_reduce_() sums the records and gathers the pooled
-    lengths (all_gather_object), once per epoch."""
-
-    def __init__(self, device, min_nodes: int = ASSEMBLY_MIN_NODES):
-        self.device = torch.device(device)
-        self.min_nodes = int(min_nodes)
-        self.zero_()
-
-    def zero_(self):
-        self.rec = np.zeros(engine.BOG_RECORD_WORDS, np.int64)
-        self.bases: List[int] = []
-        self.wrong: List[int] = []
-        return self
-
-    def add(self, graph, scores, y=None):
-        from . import decode
-        c = decode.best_overlap_contigs(graph, scores.detach(), graph.edata["prefix_length"], graph.ndata["read_length"], y)
-        self.rec += np.asarray(c.stats.words(), np.int64)
-        keep = c.num_nodes() >= self.min_nodes
-        self.bases += c.bases[keep].cpu().tolist()
-        self.wrong += c.wrong[keep].cpu().tolist()
-        return self
-
-    def all_reduce_(self):
-        if dist.is_available() and dist.is_initialized():
-            t = torch.from_numpy(self.rec).to(self.device)
-            dist.all_reduce(t)
-            self.rec = t.cpu().numpy()
-            parts = [None] * dist.get_world_size()
-            dist.all_gather_object(parts, (self.bases, self.wrong))
-            self.bases = [b for p in parts for b in p[0]]
-            self.wrong = [w for p in parts for w in p[1]]
-        return self
-
-    def summary(self) -> tuple:
-        """The History.assembly_valid entry: (contigs, n50_bases, longest_bases, wrong_link_fraction) -- the first three over the
-        pooled contigs, the last = wrong_links / links of the summed records (NaN without a link)."""
-        from .decode import n50
-        links, wrong = int(self.rec[1]), int(self.rec[4])
-        return (len(self.bases), n50(self.bases), max(self.bases, default=0), _ratio(wrong, links))
-
-
-def calculate_metrics(TP, TN, FP, FN):
-    """utils.calculate_metrics (utils.py:226-240), including its swapped precision/recall names."""
-    recall = TP / (TP + FP) if (TP + FP) else 0
-    precision = TP / (TP + FN) if (TP + FN) else 0
-    f1 = TP / (TP + 0.5 * (FP + FN)) if (TP + 0.5 * (FP + FN)) else 0
-    accuracy = (TP + TN) / (TP + TN + FP + FN)
-    return accuracy, precision, recall, f1
 
 
 def save_checkpoint(epoch, model, optimizer, loss_train, loss_valid, out, directory="checkpoints"):
@@ -518,11 +233,45 @@ class History:
                                                                 # (branch_accuracy, solvable_accuracy, succ and pred branch accuracy); empty when it is off
     assembly_valid: List[tuple] = field(default_factory=list)   # "assembly_metrics": per epoch AssemblyStats.summary() of the validation logits:
                                                                 # (contigs, n50_bases, longest_bases, wrong_link_fraction); empty when it is off
-    mask_fraction: List[float] = field(default_factory=list)    # "mask_frac_*": the kept read fraction f of every step of this rank on a graph or batch,
+    mask_fraction: List[float] = field(default_factory=list)    # "mask_frac_*": the kept read fraction f of every step of this rank on a graph or batch;
+                                                                # added once per epoch; empty when it is off
     sym_gap_train: List[float] = field(default_factory=list)    # "symmetry_loss": per epoch the mean over the steps of mean_k |org_k - rev_k| (the
     sym_gap_valid: List[float] = field(default_factory=list)    # loss's parts[2], unscaled by alpha), training / validation; empty when it is off
-    masked_edges: List[int] = field(default_factory=list)       # ... and the edge count of the thinned graph it ran on (0: a zero-contribution step, which
-                                                                # has no entry in step_losses / step_graph); added once per epoch; both empty when it is off
+    masked_edges: List[int] = field(default_factory=list)       # "mask_frac_*": beside every entry of mask_fraction, the edge count of the thinned graph the
+                                                                # step ran on (0: a zero-contribution step, which has no entry in step_losses / step_graph)
+
+
+def _whole(s: GraphSample):
+    """What a forward pass on the sample's whole graph takes: (graph, x, e, pe, y)."""
+    return s.graph, s.x, s.e, s.pe, s.y
+
+
+def _batch(sub):
+    """... and on a sub-graph that carries its features (a cluster batch, a thinned graph)."""
+    return sub, None, sub.edata["e"], sub.ndata["pe"], sub.edata["y"]
+
+
+def _add_graph_mean(ep: EpochStats, graph: EpochStats):
+    """Mini-batch mode, once per graph and on the device: the mean loss of the graph's batches and their counts join the epoch's
+    (train.py:330)."""
+    ep.loss_sum += graph.loss_sum / graph.steps.clamp(min=1)
+    ep.counts += graph.counts
+
+
+def _ranking_entries(stats: RankingStats) -> Dict:
+    rm = stats.read()
+    return {"auroc_valid": rm.auroc, "ap_valid": rm.average_precision,
+            "best_f1_valid": (rm.best_f1.f1, rm.best_f1.logit) if rm.best_f1 is not None else None}
+
+
+# The validation observers: the hyper-parameter that switches one on, its record (zero_() before an epoch's validation, all_reduce_()
+# after it: the records add across ranks like the counts), how the record takes the scores of a (sub-)graph, and the History entries
+# of an epoch, read from the reduced record.  Assembly is full-graph only (_check_hyperparameters).
+_OBSERVERS = (
+    ("ranking_metrics", RankingStats, lambda st, graph, pred, y: st.add(pred, y), _ranking_entries),
+    ("decision_metrics", DecisionStats, lambda st, graph, pred, y: st.add(graph, pred, y), lambda st: {"decision_valid": st.read().summary()}),
+    ("assembly_metrics", AssemblyStats, lambda st, graph, pred, y: st.add(graph, pred, y), lambda st: {"assembly_valid": st.summary()}),
+)
 
 
 def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSample], out: str = "model",
@@ -541,44 +290,16 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     hooks = hooks or {}
     hp = dict(get_hyperparameters())
     hp.update(hyperparameters or {})
-    if hp["optimizer"] not in ("torch", "library"):
-        raise ValueError(f"hyper-parameter optimizer={hp['optimizer']!r}: expected 'torch' or 'library'")
+    _check_hyperparameters(hp, hooks, train_samples, valid_samples)
     lib_opt = hp["optimizer"] == "library"
-    if not float(hp["clip_grad_norm"]) >= 0.0:
-        raise ValueError(f"hyper-parameter clip_grad_norm={hp['clip_grad_norm']!r}: expected a number >= 0 (0: off)")
-    if hp["clip_grad_norm"] > 0 and not lib_opt:
-        raise ValueError("hyper-parameter clip_grad_norm > 0 needs \"optimizer\": \"library\": the torch route does not clip, and "
-                         "the value is not silently ignored")
     mlo, mhi = hp["mask_frac_low"], hp["mask_frac_high"]
-    if not (isinstance(mlo, int) and isinstance(mhi, int) and 1 <= mlo <= mhi <= 100):
-        raise ValueError(f"hyper-parameters mask_frac_low={mlo!r}, mask_frac_high={mhi!r}: expected integers (per cent) with "
-                         "1 <= low <= high <= 100 (100 / 100: no masking)")
     masking = not (mlo == 100 and mhi == 100)
-    if not isinstance(hp["decision_metrics"], (bool, np.bool_)):
-        raise ValueError(f"hyper-parameter decision_metrics={hp['decision_metrics']!r}: expected True or False")
-    if not isinstance(hp["assembly_metrics"], (bool, np.bool_)):
-        raise ValueError(f"hyper-parameter assembly_metrics={hp['assembly_metrics']!r}: expected True or False")
-    if hp["assembly_metrics"]:
-        if hp["batch_size_eval"] > 1:
-            raise ValueError("hyper-parameter assembly_metrics=True with batch_size_eval > 1: the contigs are decoded on the whole "
-                             "validation graph; a cover across cluster cuts means nothing")
-        for i, s in enumerate(valid_samples):
-            for where, key in (("edata", "prefix_length"), ("ndata", "read_length")):
-                if key not in getattr(s.graph, where, {}):
-                    raise ValueError(f"hyper-parameter assembly_metrics=True: validation sample {i} has no graph.{where}[{key!r}]")
-    sym = check_symmetry_hyperparameters(hp)
-    if sym and "criterion_factory" in hooks:
-        raise ValueError("hyper-parameter symmetry_loss with a \"criterion_factory\" hook: the symmetry loss is models.SymmetryLoss")
+    sym = bool(hp["symmetry_loss"])
+    full_train, full_eval = hp["batch_size_train"] <= 1, hp["batch_size_eval"] <= 1
     seed = hp["seed"]
     random.seed(seed)
     torch.manual_seed(seed)                                                     # utils.set_seed
     dev = train_samples[0].pe.device
-    if hp["decision_metrics"] and dev.type != "cuda":
-        raise ValueError(f"hyper-parameter decision_metrics=True with the samples on {dev}: the decisions are counted by a kernel "
-                         "(gnm_decision_stats) and need a HIP device; there is no CPU route")
-    if hp["assembly_metrics"] and dev.type != "cuda":
-        raise ValueError(f"hyper-parameter assembly_metrics=True with the samples on {dev}: the contigs are decoded by kernels "
-                         "(gnm_decision_stats, gnm_bog_contigs) and need a HIP device; there is no CPU route")
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     ratio = pos_to_neg_ratio(train_samples)                                     # train.py:181
@@ -597,7 +318,7 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
             dist.broadcast(p.data, 0)
     best_state = copy.deepcopy(model.state_dict())                                              # train.py:203
     models.flatten_parameters(model)
-    flat = dp.FlatGradients(model.parameters(), direct_write=True)       # the loop below zero_()s before every backward
+    flat = dp.FlatGradients(model.parameters(), direct_write=True)       # zeroed before every backward (step() below)
     if lib_opt:
         optimizer = dp.LibAdam(model.parameters(), hp["lr"], max_norm=float(hp["clip_grad_norm"]), flat=flat)
     else:
@@ -609,107 +330,120 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         gap = torch.zeros(2, device=dev, dtype=torch.float64)          # the epoch's sum of parts[2] and its number of steps
         schedule = hp["symmetry_schedule"]
 
-        def note_gap():
+        def note_gap():                      # after every symmetry step or evaluation that really ran
             gap[0] += criterion.last_parts[2].double()
             gap[1] += 1
 
-        def sym_eval(graph, x, e, pe, y, acc):     # under no_grad: (loss, org) of one validation forward pair
-            org = model(graph, x, e, pe).squeeze(-1)
-            rev = model(graph, x, e, pe, reverse=True).squeeze(-1)
-            loss = criterion.with_counts(org, rev, y, acc)[0] if acc is not None else criterion(org, rev, y)
-            note_gap()
-            return loss, org
+        def read_gap():                      # one read per pass (training, validation), then zeroed for the next
+            if world > 1:
+                dist.all_reduce(gap)
+            mean = float(gap[0] / gap[1].clamp(min=1))
+            gap.zero_()
+            return mean
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", factor=hp["decay"],
                                                            patience=hp["patience"])             # train.py:212
     # one pass for loss + TP..FN + epoch sums; a criterion without with_counts (a criterion_factory stand-in) takes the torch route
     fused = bool(hp["fused_metrics"]) and hasattr(criterion, "with_counts")
-    if fused:
-        ep_stats, graph_stats = EpochStats(dev), EpochStats(dev)       # the epoch's sums; one graph's batches (mini-batch mode)
-    ranking = bool(hp["ranking_metrics"])
-    if ranking:
-        rank_stats = RankingStats(dev)                                 # the validation epoch's logit histogram
-    decision = bool(hp["decision_metrics"])
-    if decision:
-        dec_stats = DecisionStats(dev)                                 # the validation epoch's walk decisions
-    assembly = bool(hp["assembly_metrics"])
-    if assembly:
-        asm_stats = AssemblyStats(dev)                                 # the validation epoch's best-overlap contigs
+    # {fp64 loss sum, steps, TP..FN} of the pass under way (training, then validation) and of one graph's batches (mini-batch mode):
+    # filled by the loss kernel (fused), or by record() below
+    ep_stats, graph_stats = EpochStats(dev), EpochStats(dev)
+    observers = [(cls(dev), add, entries) for key, cls, add, entries in _OBSERVERS if hp[key]]
     if masking:
         # a generator of its own: the global `random` decides the shuffle order, which masking must not change
         mask_rng = random.Random(f"read-mask:{seed}")
         mask_key = engine.read_mask_key(seed)                          # the rank-mixed dropout key ^ a fixed constant
         recompute_pe = bool(hp["mask_recompute_pe"])
         draw_f = lambda: mask_rng.randint(mlo, mhi) / 100.0            # noqa: E731
+
+    def record(rec, loss, pred, y):
+        """The torch-metrics route: add to `rec` what the loss kernel adds on the fused route."""
+        rec.loss_sum += loss.detach().double()
+        rec.steps += 1
+        rec.counts += tfpn_counts(pred.detach(), y)
+
+    def step(sample, rec, epoch, it=None):
+        """One optimizer step on sample = (graph, x, e, pe, y), or on None: a zero-contribution step, so that the collectives stay
+        matched.  `rec` collects the step's loss and counts; it: the number of a full-graph step (the "after_exchange" hook is
+        full-graph only).  Returns the detached loss, or None."""
+        if not lib_opt:                      # the library's step leaves the gradient buffer zeroed itself
+            flat.zero_()
+        if sample is not None:
+            graph, x, e, pe, y = sample
+            if sym:
+                loss, pred = symmetry_step(model, criterion, graph, x, e, pe, y, schedule, rec if fused else None)
+                note_gap()
+            else:
+                pred = model(graph, x, e, pe).squeeze(-1)                                       # train.py:252-253
+                loss = criterion.with_counts(pred, y, rec)[0] if fused else criterion(pred, y)
+                loss.backward()
+        flat.all_reduce_mean(contributed=sample is not None)
+        if it is not None and "after_exchange" in hooks:
+            hooks["after_exchange"](epoch, it, flat)
+        if lib_opt:
+            optimizer.step(zero_grad=True)
+        else:
+            optimizer.step()                                                                    # train.py:256-258
+        if sample is None:
+            return None
+        if not fused:
+            record(rec, loss, pred, y)
+        return loss.detach()
+
+    def evaluate(sample, rec):
+        """Under no_grad: the forward and the loss of one (sub-)graph, added to `rec` -- under the symmetry loss the forward pair,
+        and its gap is noted -- then the observers take the (original) scores."""
+        graph, x, e, pe, y = sample
+        pred = model(graph, x, e, pe).squeeze(-1)
+        args = (pred, model(graph, x, e, pe, reverse=True).squeeze(-1), y) if sym else (pred, y)
+        loss = criterion.with_counts(*args, rec)[0] if fused else criterion(*args)
+        if sym:
+            note_gap()
+        if not fused:
+            record(rec, loss, pred, y)
+        for stats, add, _ in observers:
+            add(stats, graph, pred, y)
+
     hist = History()
     order = list(range(len(train_samples)))
     model_path = os.path.join(workdir, "pretrained", f"model_{out}.pt")
     for epoch in range(hp["num_epochs"]):
         random.shuffle(order)                                                                   # train.py:238
         model.train()
-        loss_sum = torch.zeros((), device=dev, dtype=torch.float64)
-        counts = torch.zeros(4, device=dev, dtype=torch.int64)
+        ep_stats.zero_()
         ep_losses = []                       # device scalars; read back once per epoch
-        if fused:
-            ep_stats.zero_()
         # every rank takes the same number of optimizer steps: shards may be uneven (dp.shard_graphs), the
         # shorter ranks pad with zero-contribution steps so that the gradient collectives stay matched
         nsteps = dp.steps_per_epoch(len(order), dev)
-        # library route: every step leaves the gradient buffer zeroed (step(zero_grad=True)); only the epoch's first step zeroes it
-        # explicitly -- validation and the hooks have run since the last one
-        zero_first = True
+        if lib_opt:                          # validation and the hooks have run since the last step left the gradient buffer zeroed
+            flat.zero_()
         empty_steps = 0                      # masking: graphs whose thinned form had no edge (zero-contribution steps)
         ep_fracs, ep_edges = [], []
-        if masking and hp["batch_size_train"] <= 1:
+        if masking and full_train:
             # the epoch's thinned graphs, one per step, in step order; step k+1's is built on a side stream while step k runs
             ep_fracs = [draw_f() for _ in order]
             thinned = iter(cluster.MaskedGraphLoader([(_attach_features(train_samples[g]), f, g) for g, f in zip(order, ep_fracs)],
                                                      mask_key, epoch, recompute_pe=recompute_pe))
         for it in range(nsteps):
             s = train_samples[order[it]] if it < len(order) else None
-            if masking and hp["batch_size_train"] <= 1 and s is not None:
-                sub = next(thinned)
-                ep_edges.append(sub.num_edges())
-                if sub.num_edges() == 0:     # nothing to train on: a padding step, so that the collectives stay matched
-                    s, empty_steps = None, empty_steps + 1
-                else:
-                    s = GraphSample(sub, sub.edata["e"], sub.ndata["pe"], sub.edata["y"])
-            if hp["batch_size_train"] <= 1:                                                     # full graph
-                if zero_first or not lib_opt:
-                    flat.zero_()
-                    zero_first = False
-                if s is not None and sym:
-                    loss, pred = symmetry_step(model, criterion, s.graph, s.x, s.e, s.pe, s.y, schedule, ep_stats if fused else None)
-                    note_gap()
-                elif s is not None:
-                    pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)                           # train.py:252-253
-                    loss = criterion.with_counts(pred, s.y, ep_stats)[0] if fused else criterion(pred, s.y)
-                    loss.backward()
-                flat.all_reduce_mean(contributed=s is not None)
-                if "after_exchange" in hooks:
-                    hooks["after_exchange"](epoch, it, flat)
-                if lib_opt:
-                    optimizer.step(zero_grad=True)
-                else:
-                    optimizer.step()                                                            # train.py:256-258
-                if s is not None and fused:              # the loss kernel has added the step to ep_stats
-                    ep_losses.append(loss.detach())
+            if full_train:
+                sample = _whole(s) if s is not None else None
+                if masking and s is not None:
+                    sub = next(thinned)
+                    ep_edges.append(sub.num_edges())
+                    sample = _batch(sub) if sub.num_edges() else None        # no edge, nothing to train on: a padding step
+                    empty_steps += sample is None
+                loss = step(sample, ep_stats, epoch, it)
+                if sample is not None:
+                    ep_losses.append(loss)
                     hist.step_graph.append(order[it])
-                elif s is not None:
-                    loss_sum += loss.detach().double()
-                    ep_losses.append(loss.detach())
-                    hist.step_graph.append(order[it])
-                    counts += tfpn_counts(pred.detach(), s.y)
             else:                                                                               # train.py:282-343
                 lo = max(1, hp["num_parts_metis_train"] - 100)
-                nparts = int(torch.randint(lo, hp["num_parts_metis_train"] + 100, (1,)).item())  # train.py:291
-                gl = torch.zeros((), device=dev, dtype=torch.float64)
-                nb = 0
+                nparts = int(torch.randint(lo, hp["num_parts_metis_train"] + 100, (1,)).item())  # train.py:291; on padding steps too
                 rm = (mask_key, epoch, order[it], recompute_pe, draw_f) if masking and s is not None else None
                 loader = _cluster_batches(s, nparts, hp["batch_size_train"], hp["partition_method"], rm) if s is not None else []
                 nbatches = dp.steps_per_epoch(len(loader), dev)          # the ranks' cluster counts differ
                 batches = iter(loader)
-                if fused:
-                    graph_stats.zero_()
+                graph_stats.zero_()
                 for _ in range(nbatches):
                     sub = next(batches, None)
                     if rm is not None and sub is not None:
@@ -717,44 +451,17 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
                         ep_edges.append(sub.num_edges())
                         if sub.num_edges() == 0:         # a thinned batch without an edge: a zero-contribution step
                             sub = None
-                    if zero_first or not lib_opt:
-                        flat.zero_()
-                        zero_first = False
-                    if sub is not None and sym:
-                        loss, pred = symmetry_step(model, criterion, sub, None, sub.edata["e"], sub.ndata["pe"], sub.edata["y"],
-                                                   schedule, graph_stats if fused else None)
-                        note_gap()
-                    elif sub is not None:
-                        pred = model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1)    # train.py:306
-                        loss = (criterion.with_counts(pred, sub.edata["y"], graph_stats)[0] if fused
-                                else criterion(pred, sub.edata["y"]))
-                        loss.backward()
-                    flat.all_reduce_mean(contributed=sub is not None)
-                    if lib_opt:
-                        optimizer.step(zero_grad=True)
-                    else:
-                        optimizer.step()
-                    if sub is not None and not fused:
-                        gl += loss.detach().double()
-                        nb += 1
-                        counts += tfpn_counts(pred.detach(), sub.edata["y"])
-                if s is not None and fused:              # once per graph, on the device: the mean of its batches, its counts
-                    loss_sum += graph_stats.loss_sum / graph_stats.steps.clamp(min=1)
-                    counts += graph_stats.counts
-                elif s is not None:
-                    loss_sum += gl / max(nb, 1)                                                 # train.py:330
-        if fused and hp["batch_size_train"] <= 1:
-            loss_sum, counts = ep_stats.loss_sum.clone(), ep_stats.counts.clone()
+                    step(_batch(sub) if sub is not None else None, graph_stats, epoch)
+                if s is not None:
+                    _add_graph_mean(ep_stats, graph_stats)
+        loss_sum, counts = ep_stats.loss_sum.clone(), ep_stats.counts.clone()
         n_train = torch.tensor(float(len(order) - empty_steps), device=dev, dtype=torch.float64)
         hist.mask_fraction += ep_fracs
         hist.masked_edges += ep_edges
         if world > 1:
             dist.all_reduce(loss_sum); dist.all_reduce(n_train); dist.all_reduce(counts)        # noqa: E702
-        if sym:                              # one read per epoch
-            if world > 1:
-                dist.all_reduce(gap)
-            hist.sym_gap_train.append(float(gap[0] / gap[1].clamp(min=1)))
-            gap.zero_()
+        if sym:
+            hist.sym_gap_train.append(read_gap())
         train_loss = float(loss_sum / n_train.clamp(min=1)) if masking else float(loss_sum / n_train)
         hist.loss_train.append(train_loss)
         if lib_opt:                          # the step kernels' device record, read here with the losses and never per step
@@ -768,96 +475,27 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
         hist.metrics_train.append(calculate_metrics(*hist.tfpn_train[-1]) if sum(hist.tfpn_train[-1]) or not masking else None)
         # ---- validation (train.py:385-511): eval mode, no_grad, no activations kept ----
         model.eval()
-        vloss = torch.zeros((), device=dev, dtype=torch.float64)
-        vcounts = torch.zeros(4, device=dev, dtype=torch.int64)
-        if fused:
-            ep_stats.zero_()
-        if ranking:
-            rank_stats.zero_()
-        if decision:
-            dec_stats.zero_()
-        if assembly:
-            asm_stats.zero_()
+        ep_stats.zero_()
+        for stats, _, _ in observers:
+            stats.zero_()
         with torch.no_grad():
             for s in valid_samples:
-                if hp["batch_size_eval"] <= 1 and fused:
-                    if sym:
-                        pred = sym_eval(s.graph, s.x, s.e, s.pe, s.y, ep_stats)[1]
-                    else:
-                        pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)
-                        criterion.with_counts(pred, s.y, ep_stats)
-                    if ranking:
-                        rank_stats.add(pred, s.y)
-                    if decision:
-                        dec_stats.add(s.graph, pred, s.y)
-                    if assembly:
-                        asm_stats.add(s.graph, pred, s.y)
-                elif hp["batch_size_eval"] <= 1:
-                    if sym:
-                        vl, pred = sym_eval(s.graph, s.x, s.e, s.pe, s.y, None)
-                        vloss += vl.double()
-                    else:
-                        pred = model(s.graph, s.x, s.e, s.pe).squeeze(-1)
-                        vloss += criterion(pred, s.y).double()
-                    vcounts += tfpn_counts(pred, s.y)
-                    if ranking:
-                        rank_stats.add(pred, s.y)
-                    if decision:
-                        dec_stats.add(s.graph, pred, s.y)
-                    if assembly:
-                        asm_stats.add(s.graph, pred, s.y)
-                elif fused:
-                    graph_stats.zero_()
-                    for sub in _cluster_batches(s, hp["num_parts_metis_eval"], hp["batch_size_eval"],
-                                                hp["partition_method"]):
-                        if sym:
-                            pred = sym_eval(sub, None, sub.edata["e"], sub.ndata["pe"], sub.edata["y"], graph_stats)[1]
-                        else:
-                            pred = model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1)
-                            criterion.with_counts(pred, sub.edata["y"], graph_stats)
-                        if ranking:
-                            rank_stats.add(pred, sub.edata["y"])
-                        if decision:
-                            dec_stats.add(sub, pred, sub.edata["y"])
-                    vloss += graph_stats.loss_sum / graph_stats.steps.clamp(min=1)
-                    vcounts += graph_stats.counts
+                if full_eval:
+                    evaluate(_whole(s), ep_stats)
                 else:                                                                           # train.py:428-486
-                    gl = torch.zeros((), device=dev, dtype=torch.float64)
-                    nb = 0
-                    for sub in _cluster_batches(s, hp["num_parts_metis_eval"], hp["batch_size_eval"],
-                                                hp["partition_method"]):
-                        if sym:
-                            bl, pred = sym_eval(sub, None, sub.edata["e"], sub.ndata["pe"], sub.edata["y"], None)
-                            gl += bl.double()
-                        else:
-                            pred = model(sub, None, sub.edata["e"], sub.ndata["pe"]).squeeze(-1)
-                            gl += criterion(pred, sub.edata["y"]).double()
-                        nb += 1
-                        vcounts += tfpn_counts(pred, sub.edata["y"])
-                        if ranking:
-                            rank_stats.add(pred, sub.edata["y"])
-                        if decision:
-                            dec_stats.add(sub, pred, sub.edata["y"])
-                    vloss += gl / max(nb, 1)
-        if fused and hp["batch_size_eval"] <= 1:
-            vloss, vcounts = ep_stats.loss_sum.clone(), ep_stats.counts.clone()
+                    graph_stats.zero_()
+                    for sub in _cluster_batches(s, hp["num_parts_metis_eval"], hp["batch_size_eval"], hp["partition_method"]):
+                        evaluate(_batch(sub), graph_stats)
+                    _add_graph_mean(ep_stats, graph_stats)
+        vloss, vcounts = ep_stats.loss_sum.clone(), ep_stats.counts.clone()
         n_val = torch.tensor(float(len(valid_samples)), device=dev, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(vloss); dist.all_reduce(n_val); dist.all_reduce(vcounts)            # noqa: E702
         if sym:
-            if world > 1:
-                dist.all_reduce(gap)
-            hist.sym_gap_valid.append(float(gap[0] / gap[1].clamp(min=1)))
-            gap.zero_()
-        if ranking:                              # the record adds across ranks like the counts; one read per epoch
-            rm = rank_stats.all_reduce_().read()
-            hist.auroc_valid.append(rm.auroc)
-            hist.ap_valid.append(rm.average_precision)
-            hist.best_f1_valid.append((rm.best_f1.f1, rm.best_f1.logit) if rm.best_f1 is not None else None)
-        if decision:                             # 15 integers; they add across ranks like the counts; one read per epoch
-            hist.decision_valid.append(dec_stats.all_reduce_().read().summary())
-        if assembly:                             # eight integers summed, the pooled lengths gathered; once per epoch
-            hist.assembly_valid.append(asm_stats.all_reduce_().summary())
+            hist.sym_gap_valid.append(read_gap())
+        for stats, _, entries in observers:      # one reduction and one read per observer and epoch
+            for name, value in entries(stats.all_reduce_()).items():
+                getattr(hist, name).append(value)
         val_loss = float(vloss / n_val.clamp(min=1))
         hist.loss_valid.append(val_loss)
         hist.tfpn_valid.append(tuple(int(c) for c in vcounts.tolist()))

@@ -157,15 +157,15 @@ def test_hyperparameter_default_and_environment(monkeypatch):
 
 @pytest.fixture(scope="module")
 def samples():
-    from test_dp_gloo import _mix_sample
+    from loop_common import mix_sample
     torch.set_num_threads(1)
-    return [_mix_sample(60, 0), _mix_sample(50, 1)], [_mix_sample(40, 100)]
+    return [mix_sample(60, 0), mix_sample(50, 1)], [mix_sample(40, 100)]
 
 
 def _train(samples, tmp_path, name, **hp):
     from gnnome_assembly_amd import train as T
-    from test_dp_gloo import _oracle_model_factory
-    hooks = {"model_factory": _oracle_model_factory,
+    from loop_common import oracle_model_factory
+    hooks = {"model_factory": oracle_model_factory,
              "criterion_factory": lambda pw: torch.nn.BCEWithLogitsLoss(pos_weight=torch.tensor([pw]))}
     wd = tmp_path / name
     wd.mkdir()

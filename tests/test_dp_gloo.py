@@ -12,6 +12,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from loop_common import mix_sample, oracle_model_factory
+
 
 def _free_port():
     s = socket.socket()
@@ -161,26 +163,6 @@ def _mix24(base_reads=240):
     return [(reads[i], int(i)) for i in order]
 
 
-def _mix_sample(reads, seed):
-    from gnnome_assembly_amd import synth, AssemblyGraph
-    from gnnome_assembly_amd.train import GraphSample
-    src, dst, n = synth.make_graph(reads, seed=seed)
-    inp = synth.make_inputs(src, dst, n, seed=seed)
-    return GraphSample(AssemblyGraph(src, dst, n), torch.from_numpy(inp["e"]), torch.from_numpy(inp["pe"]), torch.from_numpy(inp["y"]))
-
-
-def _oracle_model_factory(hp):
-    import gnnome_assembly_amd as G
-    from oracle import gatedgcn_oracle as orc
-
-    class OracleModel(G.GraphGatedGCNModel):
-        def forward(self, graph, x, e, pe):
-            s, d = graph.edges()
-            return orc.model_forward(dict(self.named_parameters()), s.long(), d.long(), graph.num_nodes(), e, pe)
-    return OracleModel(hp["node_features"], hp["edge_features"], hp["dim_latent"], hp["hidden_edge_features"], hp["num_gnn_layers"],
-                       hp["hidden_edge_scores"], hp["batch_norm"], hp["nb_pos_enc"])
-
-
 def _world8_worker(rank, world, port, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     torch.set_num_threads(1)
@@ -190,8 +172,8 @@ def _world8_worker(rank, world, port, out_dir):
     data = _mix24()
     sizes = [r for r, _ in data]
     mine = dp.shard_graphs(len(data), rank, world, sizes=sizes)
-    tr = [_mix_sample(*data[i]) for i in mine]
-    va = [_mix_sample(40, 100)] if rank == 0 else []
+    tr = [mix_sample(*data[i]) for i in mine]
+    va = [mix_sample(40, 100)] if rank == 0 else []
     first = {}
 
     def after_exchange(epoch, it, flat):
@@ -202,7 +184,7 @@ def _world8_worker(rank, world, port, out_dir):
     workdir = os.path.join(out_dir, f"rank{rank}")
     os.makedirs(workdir, exist_ok=True)
     model, best, hist = T.train(tr, va, out="w8", hyperparameters=hp, workdir=workdir, verbose=False,
-                                hooks={"after_exchange": after_exchange, "model_factory": _oracle_model_factory,
+                                hooks={"after_exchange": after_exchange, "model_factory": oracle_model_factory,
                                        "criterion_factory": lambda pw: torch.nn.BCEWithLogitsLoss(pos_weight=torch.tensor([pw]))})
     flat_order = sorted(model.parameters(), key=lambda p: p._gnm_slot)
     np.savez(os.path.join(out_dir, f"w8_{rank}.npz"), grad0=first["grad"],
@@ -248,12 +230,12 @@ def test_train_loop_under_eight_ranks_on_the_mixed_chromosome_set(tmp_path):
     import gnnome_assembly_amd as G
     from gnnome_assembly_amd import models, train as T
     torch.manual_seed(0)
-    ref = _oracle_model_factory(dict(T.get_hyperparameters(), dim_latent=32, num_gnn_layers=1))
+    ref = oracle_model_factory(dict(T.get_hyperparameters(), dim_latent=32, num_gnn_layers=1))
     models.flatten_parameters(ref)
     order = sorted(ref.parameters(), key=lambda p: p._gnm_slot)
     ratios, samples = [], []
     for r in range(world):
-        ss = [_mix_sample(*data[i]) for i in meta[r]["shard"]]
+        ss = [mix_sample(*data[i]) for i in meta[r]["shard"]]
         ratios.append((float(np.mean([float((s.y == 1).sum() / (s.y == 0).sum()) for s in ss])), len(ss)))
         samples.append(ss[meta[r]["step_graph"][0]])
     ratio = sum(a * n for a, n in ratios) / sum(n for _, n in ratios)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from loop_common import CountingBCE, mix_sample, oracle_model_factory
 from loss_counts_common import (REPO, WINDOW, X_STAR, bits_to_f32, boundary_logits, f32_bits, rule_counts, source_constant,
                                 steps_from_zero, torch_counts)
 
@@ -104,26 +105,6 @@ def test_invalid_arguments_return_error_without_a_device(lib):
     assert (counts == -7).all() and loss[0] == 0
 
 
-def _sample(reads, seed):
-    from gnnome_assembly_amd import AssemblyGraph, synth
-    from gnnome_assembly_amd.train import GraphSample
-    src, dst, n = synth.make_graph(reads, seed=seed)
-    inp = synth.make_inputs(src, dst, n, seed=seed)
-    return GraphSample(AssemblyGraph(src, dst, n), torch.from_numpy(inp["e"]), torch.from_numpy(inp["pe"]), torch.from_numpy(inp["y"]))
-
-
-def _oracle_model_factory(hp):
-    import gnnome_assembly_amd as G
-    from oracle import gatedgcn_oracle as orc
-
-    class OracleModel(G.GraphGatedGCNModel):
-        def forward(self, graph, x, e, pe):
-            s, d = graph.edges()
-            return orc.model_forward(dict(self.named_parameters()), s.long(), d.long(), graph.num_nodes(), e, pe)
-    return OracleModel(hp["node_features"], hp["edge_features"], hp["dim_latent"], hp["hidden_edge_features"], hp["num_gnn_layers"],
-                       hp["hidden_edge_scores"], hp["batch_norm"], hp["nb_pos_enc"])
-
-
 def test_train_falls_back_for_a_criterion_without_with_counts(lib, tmp_path, monkeypatch):
     """fused_metrics=True with a criterion_factory stand-in (torch's loss: no with_counts) takes the torch route and gives the
     History of the off run; GNM_FUSED_METRICS=1 sets the hyper-parameter's default."""
@@ -133,12 +114,12 @@ def test_train_falls_back_for_a_criterion_without_with_counts(lib, tmp_path, mon
     monkeypatch.setenv("GNM_FUSED_METRICS", "1")
     assert T.get_hyperparameters()["fused_metrics"] is True
     monkeypatch.delenv("GNM_FUSED_METRICS")
-    hooks = {"model_factory": _oracle_model_factory,
+    hooks = {"model_factory": oracle_model_factory,
              "criterion_factory": lambda pw: torch.nn.BCEWithLogitsLoss(pos_weight=torch.tensor([pw]))}
     assert not hasattr(hooks["criterion_factory"](1.0), "with_counts")
     runs = []
     for fused in (False, True):
-        tr, va = [_sample(60, 1), _sample(50, 2)], [_sample(40, 3)]
+        tr, va = [mix_sample(60, 1), mix_sample(50, 2)], [mix_sample(40, 3)]
         hp = dict(num_epochs=2, dim_latent=32, num_gnn_layers=1, lr=1e-3, seed=0, fused_metrics=fused)
         model, best, hist = T.train(tr, va, out="fb", hyperparameters=hp, workdir=str(tmp_path / str(fused)), verbose=False,
                                     hooks=hooks)
@@ -147,3 +128,34 @@ def test_train_falls_back_for_a_criterion_without_with_counts(lib, tmp_path, mon
     assert len(h0.step_losses) == 4 and len(h0.tfpn_train) == 2 and sum(h0.tfpn_train[0]) > 0
     assert h0 == h1                                                         # dataclass equality: every field
     assert all(torch.equal(s0[k], s1[k]) for k in s0)
+
+
+@pytest.mark.parametrize("masking", [False, True])
+@pytest.mark.parametrize("batch_size_eval", [1, 3])
+@pytest.mark.parametrize("batch_size_train", [1, 20])
+def test_train_fused_route_with_a_counting_stand_in_equals_the_torch_route(lib, tmp_path, monkeypatch, batch_size_train, batch_size_eval,
+                                                                           masking):
+    """The loop's fused-metrics route on the CPU: a criterion_factory stand-in WITH with_counts (loop_common.CountingBCE, which
+    fills the EpochStats it is handed as the loss kernel does) against torch's loss, which takes the torch route -- full graph
+    and mini-batch, training and validation, with and without read masking: the same History (every field) and the same final
+    parameters, bit for bit."""
+    from gnnome_assembly_amd import train as T
+    torch.set_num_threads(1)
+    hp = dict(num_epochs=2, dim_latent=32, num_gnn_layers=1, lr=1e-3, seed=0, fused_metrics=True,
+              batch_size_train=batch_size_train, num_parts_metis_train=101, batch_size_eval=batch_size_eval, num_parts_metis_eval=8)
+    if masking:
+        hp.update(mask_frac_low=80, mask_frac_high=100)
+    runs, calls, orig = [], [], CountingBCE.with_counts
+    monkeypatch.setattr(CountingBCE, "with_counts", lambda self, *a, **k: (calls.append(1), orig(self, *a, **k))[1])
+    for cls in (torch.nn.BCEWithLogitsLoss, CountingBCE):
+        tr = [mix_sample(r, s) for r, s in ((120, 0), (90, 1), (100, 2))]
+        va = [mix_sample(60, 100), mix_sample(40, 101)]
+        hooks = {"model_factory": oracle_model_factory, "criterion_factory": lambda pw: cls(pos_weight=torch.tensor([pw]))}
+        model, _, hist = T.train(tr, va, out="m", hyperparameters=hp, workdir=str(tmp_path / cls.__name__), verbose=False, hooks=hooks)
+        runs.append((hist, torch.cat([p.detach().reshape(-1) for p in sorted(model.parameters(), key=lambda p: p._gnm_slot)])))
+    (h0, f0), (h1, f1) = runs
+    assert len(calls) >= 2 * (3 + 2)                                        # the stand-in run took the fused route: every step and evaluation
+    assert len(h0.loss_train) == len(h0.loss_valid) == 2 and sum(h0.tfpn_train[0]) > 0 and sum(h0.tfpn_valid[0]) > 0
+    assert (len(h0.step_losses) == 6) == (batch_size_train == 1) and (len(h0.mask_fraction) > 0) == masking
+    assert h0 == h1                                                         # dataclass equality: every field
+    assert torch.equal(f0, f1)

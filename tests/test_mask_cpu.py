@@ -1,7 +1,7 @@
 """Read-masking coverage augmentation, the tier without a GPU: the numpy restatement of the mask (tests/mask_reference.py) and its
 properties, the library's plumbing (symbols, header, argument checks -- all refused on the host before any launch), the package's
 host route against the restatement, the degrees' tensor restatement against bincount on the cases of tests/induce_cases.py, and
-the training loop (train.train) with the CPU stand-in model of tests/test_dp_gloo.py."""
+the training loop (train.train) with the CPU stand-in model of tests/loop_common.py."""
 import os
 import random
 import re
@@ -12,7 +12,7 @@ import torch
 
 import induce_cases as ic
 import mask_reference as ref
-from test_dp_gloo import _mix_sample, _oracle_model_factory
+from loop_common import mix_sample, oracle_model_factory
 
 KEY = ref.mask_key(0x5EEDC0DE12345678)
 
@@ -149,7 +149,7 @@ def test_index_degrees_restatement_equals_bincount(node_order, shuffle):
 
 
 # ---- 5. the training loop -------------------------------------------------------------------------------------------------------
-_HOOKS = {"model_factory": _oracle_model_factory,
+_HOOKS = {"model_factory": oracle_model_factory,
           "criterion_factory": lambda pw: torch.nn.BCEWithLogitsLoss(pos_weight=torch.tensor([pw]))}
 _HP = dict(num_epochs=2, dim_latent=32, num_gnn_layers=1, lr=1e-3, seed=0)
 
@@ -157,7 +157,7 @@ _HP = dict(num_epochs=2, dim_latent=32, num_gnn_layers=1, lr=1e-3, seed=0)
 @pytest.fixture(scope="module")
 def samples():
     torch.set_num_threads(1)
-    return [_mix_sample(r, s) for r, s in ((120, 0), (90, 1), (100, 2))], [_mix_sample(40, 100)]
+    return [mix_sample(r, s) for r, s in ((120, 0), (90, 1), (100, 2))], [mix_sample(40, 100)]
 
 
 def _run(samples, tmp_path, name, **hp):
