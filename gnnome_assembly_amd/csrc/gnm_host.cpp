@@ -659,3 +659,43 @@ extern "C" int64_t gnm_decode_iteration_mt(int64_t N, const float* scores, const
   }
   return len;
 }
+
+// walk_edges of walks given as node lists (include/gnm.h, "contig sequences").  gnm_decode_build_adjacency's succ_eid answers a
+// duplicated (src, dst) pair with its LAST id; here the lowest one is wanted, so the edge ids are laid out once more by source,
+// in ascending id, and the first match wins.
+extern "C" int gnm_decode_walk_edges(const int32_t* src, const int32_t* dst, int64_t N, int64_t E, const int32_t* succ_ptr,
+                                     int64_t C, const int32_t* contig_ptr, const int32_t* walk_nodes, int32_t* walk_edges,
+                                     int64_t* bad) {
+  GNM_CHECK_ARG(N >= 0 && E >= 0 && C >= 0 && N < INT32_MAX && E < INT32_MAX, "decode_walk_edges: N/E/C out of range");
+  GNM_CHECK_ARG(succ_ptr && contig_ptr && (E == 0 || (src && dst)), "decode_walk_edges: null argument");
+  GNM_CHECK_ARG(contig_ptr[0] == 0, "decode_walk_edges: contig_ptr[0] = %d, expected 0", contig_ptr[0]);
+  for (int64_t c = 0; c < C; ++c)
+    GNM_CHECK_ARG(contig_ptr[c] <= contig_ptr[c + 1], "decode_walk_edges: contig_ptr decreases at contig %lld", (long long)c);
+  GNM_CHECK_ARG(contig_ptr[C] == 0 || (walk_nodes && walk_edges), "decode_walk_edges: null walk arrays");
+  std::vector<int32_t> fill(succ_ptr, succ_ptr + N), by_src((size_t)E);
+  for (int64_t k = 0; k < E; ++k) {
+    GNM_CHECK_ARG(src[k] >= 0 && src[k] < N && fill[(size_t)src[k]] < succ_ptr[src[k] + 1],
+                  "decode_walk_edges: edge %lld does not fit succ_ptr", (long long)k);
+    by_src[(size_t)fill[(size_t)src[k]]++] = (int32_t)k;
+  }
+  for (int64_t c = 0; c < C; ++c)
+    for (int64_t p = contig_ptr[c]; p < contig_ptr[c + 1]; ++p) {
+      const int64_t u = p > contig_ptr[c] ? walk_nodes[p - 1] : -1, v = walk_nodes[p];
+      int32_t found = -1;
+      if (v >= 0 && v < N && p > contig_ptr[c])
+        for (int32_t q = succ_ptr[u]; q < succ_ptr[u + 1] && found < 0; ++q)      // (u was checked as the previous v)
+          if (dst[by_src[(size_t)q]] == v) found = by_src[(size_t)q];
+      if (v < 0 || v >= N || (p > contig_ptr[c] && found < 0)) {
+        if (bad) { bad[0] = c; bad[1] = p - contig_ptr[c]; bad[2] = u; bad[3] = v; }
+        if (v < 0 || v >= N)
+          gnm::set_error("decode_walk_edges: contig %lld position %lld: node %lld outside [0, %lld)", (long long)c,
+                         (long long)(p - contig_ptr[c]), (long long)v, (long long)N);
+        else
+          gnm::set_error("decode_walk_edges: contig %lld step %lld: %lld -> %lld is not an edge of the graph", (long long)c,
+                         (long long)(p - contig_ptr[c]), (long long)u, (long long)v);
+        return -2;
+      }
+      walk_edges[p] = found;
+    }
+  return 0;
+}

@@ -1,0 +1,242 @@
+// Contig sequences on the device (include/gnm.h, "contig sequences"): walks in CSR form + a packed read store -> the contigs'
+// bases as ASCII, back to back in one buffer.  The per-position and per-lane arithmetic is csrc/gnm_seq.h.
+//
+// gnm_seq_layout, four launches on one stream:
+//   seq_len_k     piece_len[p] of every walk position (the position's contig by binary search in contig_ptr, the node, read and
+//                 edge checked before they address anything), the sum of every block of kBlock positions, the counters.
+//   seq_scan_k    ONE workgroup: the block sums -> their exclusive prefix, in place (gnm_induce.hip's ind_scan_k, in int64);
+//                 piece_off[P] = the total; record: contigs, pieces, bases, calls.
+//   seq_apply_k   piece_off[p] = block prefix + in-block exclusive scan of piece_len.
+//   seq_cptr_k    contig_base_ptr[c] = piece_off[contig_ptr[c]].
+// gnm_seq_emit, one launch: a workgroup owns a run of consecutive chunks of kSeqChunkBases output bases.  Per chunk its first
+// thread finds the pieces of the chunk's first and last base in piece_off (binary search for the run's first chunk, a few steps
+// forward from the previous chunk's last piece after that) and leaves the range in LDS; every lane then finds the piece of its
+// first base inside that range and writes its 16 bases with one aligned 16-byte store.
+// No workgroup waits for another, nothing is read back between the launches, no float arithmetic; integer atomics on the record
+// words only (one per counter and workgroup): bytes and record depend on the inputs alone, not on the grid or on timing.
+#include "gnm_common.h"
+#include "gnm_seq.h"
+
+namespace gnm {
+
+enum { kSeqContigs = 0, kSeqPieces, kSeqBases, kSeqClamped, kSeqEmpty, kSeqReverse, kSeqInvalid, kSeqCalls };
+
+struct SeqArgs {
+  SeqStore s;
+  int64_t C, P, E, nb;                   // nb: scan blocks of kBlock positions
+  const int32_t *contig_ptr, *walk_nodes, *walk_edges;
+  const int64_t* prefix_length;
+  int64_t *piece_len, *piece_off, *contig_base_ptr, *bsum;
+  unsigned long long* rec;
+  int64_t total;                         // emit: the bases the caller read from the record
+  uint8_t* out;
+};
+
+// The workgroup's sum of v, added to *word by one atomic (none when it is 0).  Every thread of the workgroup calls it.
+__device__ __forceinline__ void seq_count_(unsigned v, unsigned* lds, unsigned long long* word) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = lds[0] + lds[1] + lds[2] + lds[3];
+    if (t) atomicAdd(word, (unsigned long long)t);
+  }
+  __syncthreads();
+}
+
+// Exclusive scan of one int64 per thread over the workgroup, in thread order; `total` = the workgroup's sum.
+__device__ __forceinline__ int64_t seq_block_scan_(int64_t v, int64_t* lds, int64_t& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  long long x = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const long long o = __shfl_up(x, off, 64);
+    if (lane >= off) x += o;
+  }
+  if (lane == 63) lds[wave] = x;
+  __syncthreads();
+  int64_t before = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < kWavesPerBlock; ++w) {
+    const int64_t t = lds[w];
+    before += w < wave ? t : 0;
+    total += t;
+  }
+  __syncthreads();
+  return before + x - v;
+}
+
+__global__ __launch_bounds__(kBlock) void seq_len_k(SeqArgs a) {
+  __shared__ int64_t lds64[kWavesPerBlock];
+  __shared__ unsigned lds[kWavesPerBlock];
+  unsigned clamped = 0u, empty = 0u, reverse = 0u, invalid = 0u;
+  for (int64_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
+    const int64_t p = b * kBlock + threadIdx.x;
+    int64_t k = 0;
+    if (p < a.P) {
+      unsigned f;
+      k = seq_piece_len_(a.s, a.C, a.P, a.E, a.contig_ptr, a.walk_nodes, a.walk_edges, a.prefix_length, p, f);
+      a.piece_len[p] = k;
+      clamped += f & 1u;
+      reverse += (f >> 1) & 1u;
+      invalid += (f >> 2) & 1u;
+      empty += (k == 0 && !(f & 4u)) ? 1u : 0u;
+    }
+    int64_t total;
+    seq_block_scan_(k, lds64, total);
+    if (threadIdx.x == 0) a.bsum[b] = total;
+  }
+  seq_count_(clamped, lds, a.rec + kSeqClamped);
+  seq_count_(empty, lds, a.rec + kSeqEmpty);
+  seq_count_(reverse, lds, a.rec + kSeqReverse);
+  seq_count_(invalid, lds, a.rec + kSeqInvalid);
+}
+
+__global__ __launch_bounds__(kBlock) void seq_scan_k(SeqArgs a) {
+  __shared__ int64_t lds64[kWavesPerBlock];
+  const int64_t chunk = (a.nb + kBlock - 1) / kBlock;
+  const int64_t b0 = (int64_t)threadIdx.x * chunk < a.nb ? (int64_t)threadIdx.x * chunk : a.nb;
+  const int64_t b1 = b0 + chunk < a.nb ? b0 + chunk : a.nb;
+  int64_t t = 0;
+  for (int64_t b = b0; b < b1; ++b) t += a.bsum[b];
+  int64_t total;
+  int64_t run = seq_block_scan_(t, lds64, total);
+  for (int64_t b = b0; b < b1; ++b) {
+    const int64_t v = a.bsum[b];
+    a.bsum[b] = run;
+    run += v;
+  }
+  if (threadIdx.x == 0) {
+    a.piece_off[a.P] = total;
+    if (a.C > 0) atomicAdd(a.rec + kSeqContigs, (unsigned long long)a.C);
+    if (a.P > 0) atomicAdd(a.rec + kSeqPieces, (unsigned long long)a.P);
+    if (total > 0) atomicAdd(a.rec + kSeqBases, (unsigned long long)total);
+    atomicAdd(a.rec + kSeqCalls, 1ull);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void seq_apply_k(SeqArgs a) {
+  __shared__ int64_t lds64[kWavesPerBlock];
+  for (int64_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
+    const int64_t p = b * kBlock + threadIdx.x;
+    int64_t total;
+    const int64_t x = a.bsum[b] + seq_block_scan_(p < a.P ? a.piece_len[p] : 0, lds64, total);
+    if (p < a.P) a.piece_off[p] = x;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void seq_cptr_k(SeqArgs a) {
+  for (int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x; c <= a.C; c += (int64_t)gridDim.x * kBlock) {
+    int64_t i = a.contig_ptr[c];
+    i = i < 0 ? 0 : (i > a.P ? a.P : i);
+    a.contig_base_ptr[c] = a.piece_off[i];
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void seq_emit_k(SeqArgs a) {
+  __shared__ int64_t range[2];
+  const int64_t all = a.piece_off[a.P];
+  const int64_t total = a.total < all ? a.total : all;   // never past what the layout pass laid out
+  const int64_t nchunks = (total + kSeqChunkBases - 1) / kSeqChunkBases;
+  // A workgroup takes a run of consecutive chunks: the piece that ends one chunk is where the search for the next one starts,
+  // so only the first chunk of a workgroup pays a binary search over all P offsets.
+  const int64_t per = (nchunks + gridDim.x - 1) / gridDim.x;
+  const int64_t ch0 = (int64_t)blockIdx.x * per, ch1 = ch0 + per < nchunks ? ch0 + per : nchunks;
+  int64_t prev = -1;                                     // thread 0: the piece of the previous chunk's last base
+  for (int64_t ch = ch0; ch < ch1; ++ch) {
+    const int64_t c0 = ch * kSeqChunkBases;
+    if (threadIdx.x == 0) {
+      const int64_t end = c0 + kSeqChunkBases < total ? c0 + kSeqChunkBases : total;
+      const int64_t lo = prev < 0 ? seq_find_(a.piece_off, 0, a.P - 1, c0) : seq_gallop_(a.piece_off, prev, a.P - 1, c0);
+      prev = seq_gallop_(a.piece_off, lo, a.P - 1, end - 1);
+      range[0] = lo;
+      range[1] = prev;
+    }
+    __syncthreads();
+    const int64_t lo = range[0], hi = range[1];
+    const int64_t g0 = c0 + (int64_t)threadIdx.x * kSeqLaneBases;
+    if (g0 < total) {
+      uint64_t o[2];
+      seq_lane_(a.s, a.walk_nodes, a.piece_off, lo, hi, g0, total, o);
+      *reinterpret_cast<uint4*>(a.out + g0) =
+          make_uint4((uint32_t)o[0], (uint32_t)(o[0] >> 32), (uint32_t)o[1], (uint32_t)(o[1] >> 32));
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace gnm
+
+using namespace gnm;
+
+static inline size_t seq_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
+
+static_assert(kSeqChunkBases == GNM_SEQ_CHUNK_BASES, "include/gnm.h states the chunk size");
+
+extern "C" size_t gnm_seq_workspace_bytes(int64_t P) {
+  if (P < 0 || P >= INT32_MAX) return 0;
+  return seq_pad((size_t)((P + kBlock - 1) / kBlock) * 8);
+}
+
+static int seq_store_check(const char* what, int64_t n, int64_t R, const int64_t* base_off, const int64_t* length, int64_t packed_bytes) {
+  GNM_CHECK_ARG(n >= 0 && R >= 0 && n < INT32_MAX && R < INT32_MAX, "%s: n = %lld, R = %lld: expected 0 <= n, R < 2^31 - 1", what,
+                (long long)n, (long long)R);
+  GNM_CHECK_ARG(packed_bytes >= 0 && packed_bytes % 16 == 0 && packed_bytes <= (INT64_MAX >> 2),
+                "%s: packed_bytes = %lld: the store is whole 16-byte groups", what, (long long)packed_bytes);
+  GNM_CHECK_ARG(R == 0 || (base_off && length), "%s: base_off and length must not be null when R > 0", what);
+  return 0;
+}
+
+extern "C" int gnm_seq_layout(int64_t C, int64_t P, int64_t E, int64_t n, int64_t R, const int32_t* contig_ptr,
+                              const int32_t* walk_nodes, const int32_t* walk_edges, const int64_t* prefix_length,
+                              const int64_t* base_off, const int64_t* length, int64_t packed_bytes, void* record, int64_t* piece_len,
+                              int64_t* piece_off, int64_t* contig_base_ptr, void* ws, size_t ws_bytes, void* stream) {
+  GNM_CHECK_ARG(C >= 0 && P >= 0 && E >= 0 && C < INT32_MAX && P < INT32_MAX && E < INT32_MAX,
+                "seq_layout: C = %lld, P = %lld, E = %lld: expected 0 <= C, P, E < 2^31 - 1", (long long)C, (long long)P, (long long)E);
+  if (seq_store_check("seq_layout", n, R, base_off, length, packed_bytes)) return -1;
+  GNM_CHECK_ARG(record && ((uintptr_t)record & 7) == 0, "seq_layout: record must be a non-null, 8-byte aligned gnm_seq_record");
+  GNM_CHECK_ARG(contig_ptr && piece_off && contig_base_ptr, "seq_layout: contig_ptr, piece_off and contig_base_ptr must not be null");
+  GNM_CHECK_ARG(P == 0 || (walk_nodes && walk_edges && piece_len), "seq_layout: walk_nodes, walk_edges and piece_len must not be null when P > 0");
+  GNM_CHECK_ARG(E == 0 || prefix_length, "seq_layout: prefix_length must not be null when E > 0");
+  const size_t need = gnm_seq_workspace_bytes(P);
+  GNM_CHECK_ARG(need == 0 || (ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0),
+                "seq_layout: workspace of %zu bytes too small (gnm_seq_workspace_bytes: %zu), null or not 16-byte aligned", ws_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  SeqArgs a = {};
+  a.s.packed = nullptr; a.s.base_off = base_off; a.s.length = length; a.s.nibbles = packed_bytes * 2; a.s.R = R; a.s.n = n;
+  a.C = C; a.P = P; a.E = E; a.nb = (P + kBlock - 1) / kBlock;
+  a.contig_ptr = contig_ptr; a.walk_nodes = walk_nodes; a.walk_edges = walk_edges; a.prefix_length = prefix_length;
+  a.piece_len = piece_len; a.piece_off = piece_off; a.contig_base_ptr = contig_base_ptr; a.bsum = (int64_t*)ws;
+  a.rec = (unsigned long long*)record;
+  const dim3 blk(kBlock);
+  if (P > 0) hipLaunchKernelGGL(seq_len_k, dim3(persistent_grid(a.nb, 1, 8)), blk, 0, st, a);
+  hipLaunchKernelGGL(seq_scan_k, dim3(1), blk, 0, st, a);                     // P == 0: piece_off[0] = 0, calls += 1
+  if (P > 0) hipLaunchKernelGGL(seq_apply_k, dim3(persistent_grid(a.nb, 1, 8)), blk, 0, st, a);
+  hipLaunchKernelGGL(seq_cptr_k, dim3(persistent_grid(C + 1, kBlock, 8)), blk, 0, st, a);
+  GNM_LAUNCH_CHECK("seq_layout");
+  return 0;
+}
+
+extern "C" int gnm_seq_emit(int64_t P, int64_t n, int64_t R, const int32_t* walk_nodes, const int64_t* piece_off,
+                            const int64_t* base_off, const int64_t* length, const uint8_t* packed, int64_t packed_bytes,
+                            int64_t total, uint8_t* out, int64_t out_bytes, void* stream) {
+  GNM_CHECK_ARG(P >= 0 && P < INT32_MAX && total >= 0, "seq_emit: P = %lld, total = %lld: expected 0 <= P < 2^31 - 1, 0 <= total",
+                (long long)P, (long long)total);
+  if (seq_store_check("seq_emit", n, R, base_off, length, packed_bytes)) return -1;
+  GNM_CHECK_ARG(out_bytes >= 0 && out_bytes % 16 == 0 && total <= out_bytes,
+                "seq_emit: out_bytes = %lld for %lld bases: expected a multiple of 16 that holds them", (long long)out_bytes,
+                (long long)total);
+  if (total == 0 || P == 0) return 0;                                          // nothing to write: nothing is launched
+  GNM_CHECK_ARG(walk_nodes && piece_off && out && ((uintptr_t)out & 15) == 0,
+                "seq_emit: walk_nodes, piece_off and a 16-byte aligned out must not be null when there are bases to write");
+  GNM_CHECK_ARG(packed_bytes == 0 || (packed && ((uintptr_t)packed & 3) == 0), "seq_emit: packed must be non-null and 4-byte aligned");
+  SeqArgs a = {};
+  a.s.packed = packed; a.s.base_off = base_off; a.s.length = length; a.s.nibbles = packed_bytes * 2; a.s.R = R; a.s.n = n;
+  a.P = P; a.walk_nodes = walk_nodes; a.piece_off = const_cast<int64_t*>(piece_off); a.total = total; a.out = out;
+  const int64_t nchunks = (total + kSeqChunkBases - 1) / kSeqChunkBases;
+  hipLaunchKernelGGL(seq_emit_k, dim3(persistent_grid(nchunks, 1, 8)), dim3(kBlock), 0, (hipStream_t)stream, a);
+  GNM_LAUNCH_CHECK("seq_emit");
+  return 0;
+}

@@ -24,7 +24,10 @@ threads (gnm_decode_iteration_mt).  It draws from the same distribution as `samp
 `best_overlap_contigs` is a second, deterministic decoder that runs on the device as a whole (gnm_bog_contigs): the mutual-best
 edges of the scores form disjoint paths, which list ranking turns into contigs; `resolve_strands` then keeps one strand per read.
 A different algorithm from the greedy walk, not a faster form of it: the walk follows a forced single successor even when that
-edge is not the successor's best predecessor, the cover does not."""
+edge is not the successor's best predecessor, the cover does not.
+
+`contig_sequences` turns the walks of any of the decoders into bases on the device over a packed `reads.ReadStore`
+(gnm_seq_layout / gnm_seq_emit), `ContigSequences.write_fasta`, `ng50` and `quick_evaluation` are evaluate.py's FASTA and report."""
 from __future__ import annotations
 
 import ctypes as C
@@ -38,7 +41,8 @@ import torch
 from . import _lib
 
 __all__ = ["DecodeGraph", "sample_edges", "get_contigs", "get_contigs_device", "infer_contigs", "decision_table",
-           "best_overlap_contigs", "BogContigs", "BogStats", "resolve_strands", "ResolvedContigs", "n50"]
+           "best_overlap_contigs", "BogContigs", "BogStats", "resolve_strands", "ResolvedContigs", "n50",
+           "contig_sequences", "ContigSequences", "SeqStats", "walk_edge_ids", "ng50", "quick_evaluation", "CHR_LENGTHS"]
 
 
 def _p(a: np.ndarray):
@@ -409,8 +413,215 @@ def resolve_strands(contigs: BogContigs, len_threshold: int = 20) -> ResolvedCon
     return ResolvedContigs(walks, bases)
 
 
+# ---- contig sequences: walks + a packed read store -> bases, FASTA, N50 / NG50 (evaluate.py) ------------------------------------------
+# evaluate.py:9-33, retyped: the chromosome lengths quick_evaluation divides by
+CHR_LENGTHS = {
+    "chr1": 248387328, "chr2": 242696752, "chr3": 201105948, "chr4": 193574945, "chr5": 182045439, "chr6": 172126628,
+    "chr7": 160567428, "chr8": 146259331, "chr9": 150617247, "chr10": 134758134, "chr11": 135127769, "chr12": 133324548,
+    "chr13": 113566686, "chr14": 101161492, "chr15": 99753195, "chr16": 96330374, "chr17": 84276897, "chr18": 80542538,
+    "chr19": 61707364, "chr20": 66210255, "chr21": 45090682, "chr22": 51324926, "chrX": 154259566,
+}
+
+
+def _ref_length(ref_length) -> int:
+    return int(CHR_LENGTHS[ref_length]) if isinstance(ref_length, str) else int(ref_length)
+
+
+def _nx(lengths, target) -> int:
+    """The length at which the running sum of the lengths, longest first, reaches `target`; -1 when it never does."""
+    run = 0
+    for v in sorted((int(v) for v in np.asarray(lengths).reshape(-1)), reverse=True):
+        run += v
+        if run >= target:
+            return v
+    return -1
+
+
+def ng50(lengths, ref_length) -> int:
+    """calculate_NG50 (evaluate.py:76-92): the contig length at which the lengths, longest first, sum to half of `ref_length` (a
+    number of bases or a key of CHR_LENGTHS); -1 when they never do or ref_length <= 0."""
+    ref = _ref_length(ref_length)
+    return _nx(lengths, ref / 2) if ref > 0 else -1
+
+
+def quick_evaluation(lengths, ref_length):
+    """quick_evaluation (evaluate.py:95-104) on contig lengths: (contigs, longest, reconstructed, N50, NG50); reconstructed is the
+    fraction sum(lengths) / ref_length, N50 / NG50 are -1 where the reference's loops fall through (no contig; less than half of
+    the reference covered).  Unlike the reference, no contig at all gives longest = 0 instead of raising."""
+    a = [int(v) for v in np.asarray(lengths).reshape(-1)]
+    ref = _ref_length(ref_length)
+    return len(a), max(a, default=0), sum(a) / ref, _nx(a, sum(a) / 2), ng50(a, ref)
+
+
+@dataclass
+class SeqStats:
+    """A gnm_seq_record (include/gnm.h): contigs, pieces (walk positions), bases, clamped (pieces whose prefix_length was below 0
+    or above the read's length), empty (valid pieces of 0 bases), reverse (valid pieces of odd nodes), invalid (positions whose
+    node, read or edge is out of range: 0 bases, nothing read), calls."""
+    contigs: int = 0
+    pieces: int = 0
+    bases: int = 0
+    clamped: int = 0
+    empty: int = 0
+    reverse: int = 0
+    invalid: int = 0
+    calls: int = 0
+
+    def words(self) -> List[int]:
+        return [self.contigs, self.pieces, self.bases, self.clamped, self.empty, self.reverse, self.invalid, self.calls]
+
+
+class ContigSequences:
+    """The bases of a set of contigs, back to back: contig c is bases[contig_ptr[c] : contig_ptr[c+1]], ASCII letters of
+    "=ACMGRSVTWYHKDBN" (uint8; on the device when contig_sequences made it), contig_ptr int64 [C+1].  `record`: SeqStats.
+    `lengths` (numpy int64 [C]) and the host copy of the bases are made once, on first use."""
+
+    def __init__(self, bases, contig_ptr, record: Optional[SeqStats] = None):
+        as_t = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dt)  # noqa: E731
+        self.bases, self.contig_ptr = as_t(bases, torch.uint8), as_t(contig_ptr, torch.int64)
+        self.record = record if record is not None else SeqStats()
+        self._ptr = self._host = None
+
+    def __len__(self):
+        return int(self.contig_ptr.numel()) - 1
+
+    def _hptr(self) -> np.ndarray:
+        if self._ptr is None:
+            self._ptr = self.contig_ptr.cpu().numpy()
+        return self._ptr
+
+    def _hbases(self) -> np.ndarray:
+        if self._host is None:
+            self._host = self.bases.cpu().numpy()
+        return self._host
+
+    @property
+    def lengths(self) -> np.ndarray:
+        return np.diff(self._hptr())
+
+    def sequence(self, c: int) -> str:
+        p = self._hptr()
+        return self._hbases()[p[c]:p[c + 1]].tobytes().decode("ascii")
+
+    def write_fasta(self, path, line_width: int = 60) -> None:
+        """`>contig_{c+1} length={n}` and the bases in lines of `line_width`: the records walk_to_sequence builds (evaluate.py:43-45)
+        as Biopython's SeqIO.write(..., 'fasta') lays them out.  A contig of no bases is its header line alone."""
+        w = int(line_width)
+        if w < 1:
+            raise ValueError("write_fasta: line_width must be at least 1")
+        p, b = self._hptr(), self._hbases()
+        with open(path, "wb") as fh:
+            for c in range(len(self)):
+                seq = b[p[c]:p[c + 1]]
+                fh.write(f">contig_{c + 1} length={seq.size}\n".encode())
+                full = seq.size // w
+                if full:
+                    rows = np.empty((full, w + 1), np.uint8)
+                    rows[:, :w] = seq[:full * w].reshape(full, w)
+                    rows[:, w] = 10
+                    fh.write(rows.tobytes())
+                if seq.size > full * w:
+                    fh.write(seq[full * w:].tobytes() + b"\n")
+
+
+def walk_edge_ids(graph: DecodeGraph, walks):
+    """(contig_ptr [C+1], walk_nodes [P], walk_edges [P]) int32 numpy arrays for walks given as lists of node ids
+    (gnm_decode_walk_edges): walk_edges[p] is the id of the edge from position p-1 to p -- the lowest id among parallel edges --
+    and -1 at a contig's first node.  A step that is not an edge of `graph` raises ValueError naming it."""
+    lib = _lib.load()
+    ptr = np.zeros(len(walks) + 1, np.int64)
+    np.cumsum([len(w) for w in walks], out=ptr[1:])
+    if ptr[-1] >= 2 ** 31 - 1:
+        raise ValueError("walk_edge_ids: the walks hold 2^31 - 1 positions or more")
+    contig_ptr = ptr.astype(np.int32)
+    nodes = np.ascontiguousarray(np.concatenate([np.asarray(w, np.int64).reshape(-1) for w in walks] + [np.zeros(0, np.int64)]))
+    if nodes.size and (nodes.min() < 0 or nodes.max() >= graph.n):
+        bad = int(nodes[(nodes < 0) | (nodes >= graph.n)][0])
+        raise ValueError(f"walk_edge_ids: node {bad} outside [0, {graph.n})")
+    walk_nodes = nodes.astype(np.int32)
+    edges = np.full(walk_nodes.size, -1, np.int32)
+    bad = np.zeros(4, np.int64)
+    rc = lib.gnm_decode_walk_edges(_p(graph.src), _p(graph.dst), graph.n, graph.src.size, _p(graph.succ[0]), len(walks),
+                                   _p(contig_ptr), _p(walk_nodes), _p(edges), _p(bad))
+    if rc == -2:
+        raise ValueError(lib.gnm_last_error().decode(errors="replace"))
+    _lib.check(rc, "gnm_decode_walk_edges")
+    return contig_ptr, walk_nodes, edges
+
+
+def contig_sequences(walks, graph, reads, prefix_length=None, read_length=None) -> ContigSequences:
+    """The sequences of `walks` on the device: evaluate.walk_to_sequence (evaluate.py:36-47) over a packed ReadStore.
+
+    walks: a BogContigs -- its device CSR is used as it is, no host round trip -- or a list of lists of node ids (get_contigs,
+    get_contigs_device, ResolvedContigs.walks), whose edge ids are looked up on the host (walk_edge_ids) and uploaded once.
+    graph: the AssemblyGraph (or, for lists, a DecodeGraph).  reads: a ReadStore on a HIP device; node v is read v >> 1, an odd
+    v its reverse complement.  prefix_length [E]: default graph.edata['prefix_length'] (a BogContigs falls back on the one it
+    was built with).  read_length [N] (optional): checked against the store, a disagreement raises (one more synchronisation).
+
+    Position p of a contig contributes the first prefix_length[edge to p+1] bases of its node's strand, the last position the
+    whole read.  DIFFERENT from the reference on purpose: a prefix below 0 or above the read's length is clamped (a Python slice
+    would take a negative prefix from the read's END) and counted in record.clamped.  A node, read or edge id out of range raises
+    GnmError (its .record holds the counts); nothing is emitted then.  One host synchronisation: the read of the record, which
+    sizes the output."""
+    from . import engine
+    from .reads import ReadStore
+    if not isinstance(reads, ReadStore):
+        raise TypeError("contig_sequences: reads must be a ReadStore")
+    dev = reads.device
+    if dev.type != "cuda":
+        raise _lib.GnmError("contig_sequences: the ReadStore must be on a HIP device (no CPU fallback; ReadStore.sequence is the "
+                            "host route)")
+    n = int(graph.n if isinstance(graph, DecodeGraph) else graph.num_nodes())
+    if prefix_length is None:
+        prefix_length = getattr(graph, "edata", {}).get("prefix_length")
+        if prefix_length is None and isinstance(walks, BogContigs):
+            prefix_length = walks.prefix_length
+        if prefix_length is None:
+            raise ValueError("contig_sequences: no prefix_length given and the graph has no edata['prefix_length']")
+    pl = torch.as_tensor(prefix_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    if isinstance(walks, BogContigs):
+        to32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()  # noqa: E731
+        contig_ptr, walk_nodes, walk_edges = to32(walks.contig_ptr), to32(walks.walk_nodes), to32(walks.walk_edges)
+    else:
+        dg = graph
+        if not isinstance(dg, DecodeGraph):
+            src, dst = graph.edges()
+            dg = DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), n)
+        if pl.numel() != dg.src.size:
+            raise ValueError("contig_sequences: prefix_length needs one entry per edge")
+        contig_ptr, walk_nodes, walk_edges = (torch.from_numpy(a).to(dev) for a in walk_edge_ids(dg, walks))
+    with torch.cuda.device(dev):
+        if read_length is not None:
+            rl = torch.as_tensor(read_length).reshape(-1).to(device=dev, dtype=torch.int64)
+            if rl.numel() != n or (n + 1) // 2 > len(reads):
+                raise ValueError(f"contig_sequences: read_length holds {rl.numel()} entries and the store {len(reads)} reads for "
+                                 f"{n} nodes")
+            diff = rl != reads.length[torch.arange(n, device=dev) >> 1]
+            if bool(diff.any()):
+                v = int(diff.nonzero()[0])
+                raise ValueError(f"contig_sequences: read_length[{v}] = {int(rl[v])}, the store holds {int(reads.length[v >> 1])} "
+                                 f"bases for read {v >> 1}")
+        C, P = int(contig_ptr.numel()) - 1, int(walk_nodes.numel())
+        i64 = lambda m: torch.empty(m, dtype=torch.int64, device=dev)  # noqa: E731
+        rec = torch.zeros(engine.SEQ_RECORD_WORDS, dtype=torch.int64, device=dev)
+        piece_len, piece_off, base_ptr = i64(P), i64(P + 1), i64(C + 1)
+        engine.seq_layout(contig_ptr, walk_nodes, walk_edges, pl, n, reads.base_off, reads.length, reads.packed, rec, piece_len,
+                          piece_off, base_ptr)
+        stats = SeqStats(*[int(v) for v in rec.cpu().tolist()])        # the one synchronisation
+        if stats.invalid:
+            err = _lib.GnmError(f"contig_sequences: {stats.invalid} of {stats.pieces} walk positions name a node, read or edge "
+                                f"that is out of range (graph of {n} nodes and {pl.numel()} edges, store of {len(reads)} reads)")
+            err.record = stats
+            raise err
+        out = torch.empty((stats.bases + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+        engine.seq_emit(walk_nodes, piece_off, n, reads.base_off, reads.length, reads.packed, stats.bases, out)
+    seqs = ContigSequences(out[:stats.bases], base_ptr, stats)
+    seqs.piece_len, seqs.piece_off = piece_len, piece_off
+    return seqs
+
+
 def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int = 50, len_threshold: int = 20,
-                  device_sampling: bool = False, decision_report: bool = False, decoder: str = "greedy"):
+                  device_sampling: bool = False, decision_report: bool = False, decoder: str = "greedy", reads=None):
     """The per-graph body of inference.inference (inference.py:444-490): logits of the whole graph under
     no_grad in eval mode, stored by edge id, then greedy decode.  Returns (scores [E], walks).
     device_sampling=True: the logits stay on the device for `get_contigs_device` (same distribution of start edges,
@@ -418,7 +629,9 @@ def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int
     decision_report=True: returns (scores, walks, report) with report = decision_table(graph, scores, graph.edata.get('y')) --
     the per-node best successor / predecessor edges and their counts, taken before the walks, which it does not change.
     decoder="best_overlap": the walks are resolve_strands(best_overlap_contigs(graph, scores, ...), len_threshold).walks --
-    deterministic, computed on the device, no sampling (nb_paths and device_sampling are not used)."""
+    deterministic, computed on the device, no sampling (nb_paths and device_sampling are not used).
+    reads: a ReadStore on the graph's device: contig_sequences(walks, graph, reads, prefix_length) -- the walks' bases, ready for
+    ContigSequences.write_fasta (inference.py:497-501) -- is appended as the LAST element of the returned tuple."""
     if decoder not in ("greedy", "best_overlap"):
         raise ValueError(f"decoder {decoder!r}: expected 'greedy' or 'best_overlap'")
     model.eval()
@@ -428,11 +641,15 @@ def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int
     if decoder == "best_overlap":
         walks = resolve_strands(best_overlap_contigs(graph, scores, prefix_length, read_length,
                                                      getattr(graph, "edata", {}).get("y")), len_threshold).walks
-        return (scores, walks, report) if decision_report else (scores, walks)
+        return _with_sequences((scores, walks, report) if decision_report else (scores, walks), walks, graph, reads, prefix_length)
     src, dst = graph.edges()
     dg = DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), graph.num_nodes())
     if device_sampling:
         walks = get_contigs_device(dg, scores, prefix_length, read_length, nb_paths, len_threshold)
     else:
         walks = get_contigs(dg, scores, prefix_length, read_length, nb_paths, len_threshold)
-    return (scores, walks, report) if decision_report else (scores, walks)
+    return _with_sequences((scores, walks, report) if decision_report else (scores, walks), walks, dg, reads, prefix_length)
+
+
+def _with_sequences(result, walks, graph, reads, prefix_length):
+    return result if reads is None else result + (contig_sequences(walks, graph, reads, prefix_length),)

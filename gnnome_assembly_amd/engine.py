@@ -2338,6 +2338,69 @@ def bog_contigs(src, dst, best_succ, best_pred, scores, y, prefix_length, read_l
           _ptr(contig_wrong), _ptr(ws), need, _stream())
 
 
+SEQ_COUNTERS = ("contigs", "pieces", "bases", "clamped", "empty", "reverse", "invalid", "calls")
+SEQ_RECORD_WORDS = len(SEQ_COUNTERS)       # the int64 words of a gnm_seq_record (include/gnm.h), in order
+SEQ_CHUNK_BASES = 4096                     # GNM_SEQ_CHUNK_BASES: output bases a workgroup of gnm_seq_emit owns at a time
+SEQ_LETTERS = "=ACMGRSVTWYHKDBN"           # the letter of every 4-bit code
+
+
+def _seq_store_args(name, n, base_off, length, packed):
+    R = int(base_off.numel())
+    for what, t, dt, m in (("base_off", base_off, torch.int64, R), ("length", length, torch.int64, R),
+                           ("packed", packed, torch.uint8, packed.numel())):
+        if t.dtype != dt or t.numel() != m or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous {str(dt).replace('torch.', '')} [{m}] tensor")
+    if packed.numel() % 16:
+        raise ValueError(f"{name}: packed holds {packed.numel()} bytes, not whole 16-byte groups")
+    return R
+
+
+@on_device_of(lambda contig_ptr, *a, **k: contig_ptr)
+def seq_layout(contig_ptr, walk_nodes, walk_edges, prefix_length, n: int, base_off, length, packed, record, piece_len, piece_off,
+               contig_base_ptr):
+    """Piece lengths, their exclusive prefix sum and the contigs' base offsets for walks in CSR form over a packed read store
+    (gnm_seq_layout: 4 launches on the current stream, no host synchronisation).  contig_ptr int32 [C+1]; walk_nodes, walk_edges
+    int32 [P]; prefix_length int64 [E]; n: nodes of the graph; base_off, length int64 [R] and packed uint8 (whole 16-byte groups):
+    the store; record: a contiguous int64 [SEQ_RECORD_WORDS] device tensor the call ADDS to; piece_len int64 [P], piece_off int64
+    [P+1], contig_base_ptr int64 [C+1]: outputs."""
+    lib = _lib.load()
+    _chk_dev(contig_ptr, walk_nodes, walk_edges, prefix_length, base_off, length, packed, record, piece_len, piece_off, contig_base_ptr)
+    C, P, E = int(contig_ptr.numel()) - 1, int(walk_nodes.numel()), int(prefix_length.numel())
+    if C < 0:
+        raise ValueError("seq_layout: contig_ptr needs at least one entry")
+    R = _seq_store_args("seq_layout", n, base_off, length, packed)
+    if record.dtype != torch.int64 or record.numel() != SEQ_RECORD_WORDS or not record.is_contiguous():
+        raise ValueError(f"seq_layout: record must be a contiguous int64 [{SEQ_RECORD_WORDS}] tensor")
+    for name, t, dt, m in (("contig_ptr", contig_ptr, torch.int32, C + 1), ("walk_nodes", walk_nodes, torch.int32, P),
+                           ("walk_edges", walk_edges, torch.int32, P), ("prefix_length", prefix_length, torch.int64, E),
+                           ("piece_len", piece_len, torch.int64, P), ("piece_off", piece_off, torch.int64, P + 1),
+                           ("contig_base_ptr", contig_base_ptr, torch.int64, C + 1)):
+        if t.dtype != dt or t.numel() != m or not t.is_contiguous():
+            raise ValueError(f"seq_layout: {name} must be a contiguous {str(dt).replace('torch.', '')} [{m}] tensor")
+    need = lib.gnm_seq_workspace_bytes(P)
+    ws = scratch(record.device).ws(need) if need else None
+    _call("gnm_seq_layout", C, P, E, int(n), R, _ptr(contig_ptr), _ptr(walk_nodes), _ptr(walk_edges), _ptr(prefix_length),
+          _ptr(base_off), _ptr(length), int(packed.numel()), _ptr(record), _ptr(piece_len), _ptr(piece_off), _ptr(contig_base_ptr),
+          _ptr(ws), need, _stream())
+
+
+@on_device_of(lambda walk_nodes, piece_off, *a, **k: piece_off)
+def seq_emit(walk_nodes, piece_off, n: int, base_off, length, packed, total: int, out):
+    """The bases of the laid-out pieces as ASCII (gnm_seq_emit: one launch, none when total == 0).  walk_nodes int32 [P] and
+    piece_off int64 [P+1] as seq_layout left them; total: record.bases of that call; out: uint8, a multiple of 16 bytes >= total.
+    Bytes [0, total) are written, and the rest of the last 16-byte group as 0."""
+    _lib.load()
+    _chk_dev(walk_nodes, piece_off, base_off, length, packed, out)
+    P = int(walk_nodes.numel())
+    R = _seq_store_args("seq_emit", n, base_off, length, packed)
+    for name, t, dt, m in (("walk_nodes", walk_nodes, torch.int32, P), ("piece_off", piece_off, torch.int64, P + 1),
+                           ("out", out, torch.uint8, out.numel())):
+        if t.dtype != dt or t.numel() != m or not t.is_contiguous():
+            raise ValueError(f"seq_emit: {name} must be a contiguous {str(dt).replace('torch.', '')} [{m}] tensor")
+    _call("gnm_seq_emit", P, int(n), R, _ptr(walk_nodes), _ptr(piece_off), _ptr(base_off), _ptr(length), _ptr(packed),
+          int(packed.numel()), int(total), _ptr(out), int(out.numel()), _stream())
+
+
 def optim_workspace(n: int, device) -> torch.Tensor:
     """The workspace of optim_step for flat buffers of n elements (gnm_optim_workspace_bytes), as int64 words: 8-byte aligned."""
     return torch.empty((_lib.load().gnm_optim_workspace_bytes(int(n)) + 7) // 8, dtype=torch.int64, device=device)

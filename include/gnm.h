@@ -819,6 +819,56 @@ int gnm_bog_contigs(int64_t n, int64_t E, const int32_t* src, const int32_t* dst
                     void* record, int32_t* contig_ptr, int32_t* walk_nodes, int32_t* walk_edges, int64_t* contig_bases,
                     int32_t* contig_wrong, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- contig sequences: a packed read store + walks in CSR form -> the contigs' bases as ASCII, on the device ----------------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: four new symbols, no existing signature changes.)
+ * evaluate.walk_to_sequence (evaluate.py:36-47) without a string per node.  DEVICE pointers except for gnm_decode_walk_edges.
+ * Store.  One entry per READ, + strand only: packed [packed_bytes] uint8, 4 bits per base in the BAM code "=ACMGRSVTWYHKDBN"
+ *   (A=1 C=2 G=4 T=8, an ambiguity code the OR of its bases, N=15), two bases per byte, low nibble first; base_off [R] int64, the
+ *   nibble index of read r's first base; length [R] int64.  packed_bytes is a multiple of 16 and packed is 4-byte aligned.  Node v
+ *   of the graph (n nodes) is read v >> 1; an odd v is the reverse complement: the read's nibbles in reverse order, the four bits
+ *   of each reversed (complement = bit reversal for every code).
+ * Walks.  contig_ptr [C+1] int32, walk_nodes [P] int32, walk_edges [P] int32 (walk_edges[p] joins positions p-1 and p; the entry
+ *   at a contig's first position is not read): the layout gnm_bog_contigs leaves.  prefix_length [E] int64.
+ * Pieces.  Position p of contig c (contig_ptr[c] <= p < contig_ptr[c+1]) with node v contributes the first k bases of v's strand:
+ *   k = length[v >> 1] at the contig's last position, else k = clamp(prefix_length[walk_edges[p+1]], 0, length[v >> 1]).  The
+ *   clamp is deliberate: a Python slice takes a negative prefix from the END of the read, which is not reproduced but counted.
+ *   A position is INVALID, gets k = 0 and has nothing read through it when: it lies in no contig (contig_ptr not ascending from
+ *   0 to P), v is outside [0, n), v >> 1 >= R, the read's [base_off, base_off + length) does not lie inside the store, or
+ *   (inner positions) the edge id is outside [0, E).  Every index is checked before it addresses anything.
+ * gnm_seq_layout (4 launches; 2 for P == 0): piece_len [P], piece_off [P+1] = the exclusive prefix sum of piece_len (blocked
+ *   integer scan: block sums, one workgroup over the block sums, in-block scan), contig_base_ptr [C+1] = piece_off[contig_ptr[c]].
+ *   record: ADDS  contigs (C), pieces (P), bases (piece_off[P]), clamped (prefix below 0 or above the read's length), empty (valid
+ *   pieces of 0 bases), reverse (valid pieces of odd nodes), invalid, calls (+1).  The caller zeroes it and reads `bases` to size
+ *   the output: the one host synchronisation.  ws: gnm_seq_workspace_bytes(P) bytes, 16-byte aligned.
+ * gnm_seq_emit (1 launch; none when total == 0): out[g] for g < total = the ASCII letter of output base g, the contigs back to
+ *   back (contig c at contig_base_ptr[c]); out_bytes is a multiple of 16 >= total and the bytes of the last 16-byte group at and
+ *   past `total` are written as 0.  total: `bases` of the layout call; the kernel never goes past piece_off[P].  A workgroup owns
+ *   chunks of GNM_SEQ_CHUNK_BASES output bases and every lane writes 16 bases with one aligned 16-byte store: from one window of
+ *   the store when they lie in one piece (forward: nibbles [s, s+16); reverse: the same window with all 64 bits reversed), base by
+ *   base when pieces end among them.  The emit pass re-checks node, read and window against the store: a piece whose source does
+ *   not check out is written as '=' (code 0), never read.  Callers refuse to emit when record.invalid != 0.
+ * No float arithmetic, no workgroup waits for another, integer atomics on the record only: the bytes and the record depend on the
+ * inputs alone.  Negative or >= 2^31 - 1 counts, a packed_bytes that is no multiple of 16, NULL or misaligned record / ws / out /
+ * packed and an out_bytes below total are errors, returned before anything is launched.
+ * gnm_decode_walk_edges (HOST pointers): walk_edges for walks given as node lists.  src, dst [E] and succ_ptr [N+1] as in
+ *   gnm_decode_build_adjacency; contig_ptr [C+1], walk_nodes [P].  walk_edges[p] = the LOWEST edge id k with src[k] ==
+ *   walk_nodes[p-1] and dst[k] == walk_nodes[p]; -1 at a contig's first position.  -2: a node outside [0, N) or a step that is
+ *   no edge; bad[0..3] = contig, position in the contig, u, v of the first one, also named in gnm_last_error.                       */
+#define GNM_SEQ_CHUNK_BASES 4096
+typedef struct gnm_seq_record {
+  int64_t contigs, pieces, bases, clamped, empty, reverse, invalid, calls;
+} gnm_seq_record;
+size_t gnm_seq_workspace_bytes(int64_t P);
+int gnm_seq_layout(int64_t C, int64_t P, int64_t E, int64_t n, int64_t R, const int32_t* contig_ptr, const int32_t* walk_nodes,
+                   const int32_t* walk_edges, const int64_t* prefix_length, const int64_t* base_off, const int64_t* length,
+                   int64_t packed_bytes, void* record, int64_t* piece_len, int64_t* piece_off, int64_t* contig_base_ptr, void* ws,
+                   size_t ws_bytes, void* stream);
+int gnm_seq_emit(int64_t P, int64_t n, int64_t R, const int32_t* walk_nodes, const int64_t* piece_off, const int64_t* base_off,
+                 const int64_t* length, const uint8_t* packed, int64_t packed_bytes, int64_t total, uint8_t* out, int64_t out_bytes,
+                 void* stream);
+int gnm_decode_walk_edges(const int32_t* src, const int32_t* dst, int64_t N, int64_t E, const int32_t* succ_ptr, int64_t C,
+                          const int32_t* contig_ptr, const int32_t* walk_nodes, int32_t* walk_edges, int64_t* bad);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
