@@ -140,6 +140,8 @@ SIGNATURES = {
     "gnm_decision_stats": (_i32, [_i64, _i64] + [_p] * 14),
     "gnm_bog_workspace_bytes": (_sz, [_i64]),
     "gnm_bog_contigs": (_i32, [_i64, _i64] + [_p] * 8 + [_f32] + [_p] * 7 + [_sz, _p]),
+    "gnm_cover_workspace_bytes": (_sz, [_i64]),
+    "gnm_cover_rounds": (_i32, [_i64, _i64] + [_p] * 8 + [_f32, _i64, _i64] + [_p] * 4 + [_sz, _p]),
     "gnm_seq_workspace_bytes": (_sz, [_i64]),
     "gnm_seq_layout": (_i32, [_i64] * 5 + [_p] * 6 + [_i64] + [_p] * 5 + [_sz, _p]),
     "gnm_seq_emit": (_i32, [_i64] * 3 + [_p] * 5 + [_i64, _i64, _p, _i64, _p]),

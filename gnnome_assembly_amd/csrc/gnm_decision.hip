@@ -30,6 +30,7 @@
 // Bounds.  Every value read from an index array is checked before it addresses anything: row pointers are clamped to
 // 0 <= lo <= hi <= E, a position or edge id outside [0, E) drops the candidate, a row nperm[i] outside [0, n) is never written.
 #include "gnm_common.h"
+#include "gnm_key.h"                                    // dec_key_: shared with gnm_cover.hip
 
 namespace gnm {
 
@@ -44,13 +45,6 @@ struct DecArgs {
   const float *scores, *y;
   int32_t* best[2];                                     // succ, pred; either may be NULL
 };
-
-__device__ __forceinline__ unsigned dec_key_(float x) {
-  unsigned u = __float_as_uint(x);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;       // NaN: below every number
-  if (u == 0x80000000u) u = 0u;                         // -0 -> +0
-  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
 
 __device__ __forceinline__ unsigned long long dec_shfl_xor_(unsigned long long v, int off) {
   const unsigned lo = __shfl_xor((unsigned)v, off, kDecLanes), hi = __shfl_xor((unsigned)(v >> 32), off, kDecLanes);

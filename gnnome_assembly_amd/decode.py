@@ -26,6 +26,9 @@ edges of the scores form disjoint paths, which list ranking turns into contigs; 
 A different algorithm from the greedy walk, not a faster form of it: the walk follows a forced single successor even when that
 edge is not the successor's best predecessor, the cover does not.
 
+`greedy_cover_contigs` iterates those mutual-best links on the device (gnm_cover_rounds) until no node with a free slot finds a
+free partner: the greedy path cover of overlap-layout assemblers, of which `best_overlap_contigs` is round one.
+
 `contig_sequences` turns the walks of any of the decoders into bases on the device over a packed `reads.ReadStore`
 (gnm_seq_layout / gnm_seq_emit), `ContigSequences.write_fasta`, `ng50` and `quick_evaluation` are evaluate.py's FASTA and report."""
 from __future__ import annotations
@@ -41,7 +44,7 @@ import torch
 from . import _lib
 
 __all__ = ["DecodeGraph", "sample_edges", "get_contigs", "get_contigs_device", "infer_contigs", "decision_table",
-           "best_overlap_contigs", "BogContigs", "BogStats", "resolve_strands", "ResolvedContigs", "n50",
+           "best_overlap_contigs", "greedy_cover_contigs", "BogContigs", "BogStats", "resolve_strands", "ResolvedContigs", "n50",
            "contig_sequences", "ContigSequences", "SeqStats", "walk_edge_ids", "ng50", "quick_evaluation", "CHR_LENGTHS"]
 
 
@@ -361,6 +364,69 @@ def best_overlap_contigs(graph, scores, prefix_length, read_length, y=None, min_
     return BogContigs(contig_ptr[:C + 1], walk_nodes, walk_edges, bases[:C], wrong[:C], stats, pl, rl)
 
 
+COVER_CHECK_EVERY = 4      # rounds per chunk of greedy_cover_contigs: one read-back of the chunk's round_links
+
+
+def greedy_cover_contigs(graph, scores, prefix_length, read_length, y=None, min_logit: float = float("-inf"),
+                         max_rounds: Optional[int] = None, check_every: int = COVER_CHECK_EVERY) -> BogContigs:
+    """Contigs of the greedy path cover of `scores`, computed on the device: best_overlap_contigs' mutual-best links are round one
+    of a sequence (gnm_cover_rounds) in which every node that still has a free out- or in-slot chooses again among its edges whose
+    other end is free too, until a round adds nothing.  The fixed point is the path cover of overlap-layout assemblers -- the edges
+    by descending score, lowest edge id among equals, an edge accepted when its source has no successor and its destination no
+    predecessor yet; self loops, NaN scores and scores < min_logit are no candidates.  Cycles CAN close: unlike the sequential
+    textbook greedy, which refuses the closing edge with a union-find, the rounds accept it, and the existing pass of
+    gnm_bog_contigs cuts every cycle at its smallest node id afterwards and counts it in stats.cycles_cut.
+    The rounds run in chunks of `check_every`; after a chunk its round_links are read back -- the loop's only synchronisation --
+    and the loop stops at the first round that added 0 links (rounds past it inside the chunk change nothing) or at `max_rounds`
+    (None: until the fixed point; at most n + 1 rounds exist).  max_rounds=1 gives the links of best_overlap_contigs.
+    Arguments and result as for best_overlap_contigs (stats.dropped is always 0: a refused edge is never proposed); the result
+    additionally carries `rounds` (the rounds run, up to and including the first empty one), `round_links` (list: the links every
+    one of them added) and `converged` (bool: the last of them added nothing).  The two strands of a read may both be covered:
+    see resolve_strands."""
+    from . import engine
+    from .graph import as_assembly_graph
+    g = as_assembly_graph(graph)
+    dev = g.device
+    if dev.type != "cuda":
+        raise _lib.GnmError("greedy_cover_contigs: the graph must be on a HIP device (no CPU fallback)")
+    if max_rounds is not None and (not isinstance(max_rounds, (int, np.integer)) or max_rounds < 1):
+        raise ValueError(f"greedy_cover_contigs: max_rounds={max_rounds!r}: expected None or an integer >= 1")
+    if not isinstance(check_every, (int, np.integer)) or check_every < 1:
+        raise ValueError(f"greedy_cover_contigs: check_every={check_every!r}: expected an integer >= 1")
+    n, E = g.num_nodes(), g.num_edges()
+    pl = torch.as_tensor(prefix_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    rl = torch.as_tensor(read_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    if pl.numel() != E or rl.numel() != n or scores.numel() != E:
+        raise ValueError("scores / prefix_length need one entry per edge, read_length one per node")
+    limit = n + 1 if max_rounds is None else int(max_rounds)
+    with torch.cuda.device(dev):
+        i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
+        idx = g.index(dev)
+        link_succ, link_pred = i32(n), i32(n)
+        ws = torch.empty(engine.cover_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        round_links, converged = [], False
+        while not converged and len(round_links) < limit:
+            chunk = torch.empty(min(int(check_every), limit - len(round_links)), dtype=torch.int64, device=dev)
+            engine.cover_rounds(idx, scores, chunk, link_succ, link_pred, ws, len(round_links), min_logit)
+            for added in chunk.cpu().tolist():                         # the loop's one synchronisation per chunk
+                round_links.append(int(added))
+                if added == 0:
+                    converged = True
+                    break
+        src, dst = g.edges()
+        rec = torch.zeros(engine.BOG_RECORD_WORDS, dtype=torch.int64, device=dev)
+        contig_ptr, walk_nodes, walk_edges, wrong = i32(n + 1), i32(n), i32(n), i32(n)
+        bases = torch.empty(n, dtype=torch.int64, device=dev)
+        engine.bog_contigs(src, dst, link_succ, link_pred, scores, y, pl, rl, rec, contig_ptr, walk_nodes, walk_edges, bases, wrong,
+                           min_logit)
+        stats = BogStats(*[int(v) for v in rec.cpu().tolist()])
+    C = stats.contigs
+    out = BogContigs(contig_ptr[:C + 1], walk_nodes, walk_edges, bases[:C], wrong[:C], stats, pl, rl)
+    out.rounds, out.round_links, out.converged = len(round_links), round_links, converged
+    out.link_succ, out.link_pred = link_succ, link_pred
+    return out
+
+
 @dataclass
 class ResolvedContigs:
     """resolve_strands' result: the kept pieces as lists of node ids and their lengths in bases, in the order they were kept."""
@@ -630,17 +696,19 @@ def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int
     the per-node best successor / predecessor edges and their counts, taken before the walks, which it does not change.
     decoder="best_overlap": the walks are resolve_strands(best_overlap_contigs(graph, scores, ...), len_threshold).walks --
     deterministic, computed on the device, no sampling (nb_paths and device_sampling are not used).
+    decoder="greedy_cover": the same over greedy_cover_contigs, the mutual-best links iterated to the greedy path cover.
     reads: a ReadStore on the graph's device: contig_sequences(walks, graph, reads, prefix_length) -- the walks' bases, ready for
     ContigSequences.write_fasta (inference.py:497-501) -- is appended as the LAST element of the returned tuple."""
-    if decoder not in ("greedy", "best_overlap"):
-        raise ValueError(f"decoder {decoder!r}: expected 'greedy' or 'best_overlap'")
+    if decoder not in ("greedy", "best_overlap", "greedy_cover"):
+        raise ValueError(f"decoder {decoder!r}: expected 'greedy', 'best_overlap' or 'greedy_cover'")
     model.eval()
     with torch.no_grad():
         scores = model(graph, None, e, pe).squeeze(-1)                 # inference.py:453-454
     report = decision_table(graph, scores, getattr(graph, "edata", {}).get("y")) if decision_report else None
-    if decoder == "best_overlap":
-        walks = resolve_strands(best_overlap_contigs(graph, scores, prefix_length, read_length,
-                                                     getattr(graph, "edata", {}).get("y")), len_threshold).walks
+    if decoder in ("best_overlap", "greedy_cover"):
+        cover = best_overlap_contigs if decoder == "best_overlap" else greedy_cover_contigs
+        walks = resolve_strands(cover(graph, scores, prefix_length, read_length, getattr(graph, "edata", {}).get("y")),
+                                len_threshold).walks
         return _with_sequences((scores, walks, report) if decision_report else (scores, walks), walks, graph, reads, prefix_length)
     src, dst = graph.edges()
     dg = DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), graph.num_nodes())

@@ -2338,6 +2338,50 @@ def bog_contigs(src, dst, best_succ, best_pred, scores, y, prefix_length, read_l
           _ptr(contig_wrong), _ptr(ws), need, _stream())
 
 
+_COVER_INDEX_KEYS = ("perm", "isrc", "in_ptr", "out_ptr", "out_pos", "out_dst")
+
+
+@on_device_of(lambda idx, scores, round_links, *a, **k: round_links)
+def cover_rounds(idx, scores, round_links, link_succ, link_pred, ws, first_round: int = 0, min_logit: float = float("-inf")):
+    """Rounds first_round .. first_round + len(round_links) - 1 of the greedy path cover (gnm_cover_rounds: two launches per round
+    and two per call on the current stream, no host synchronisation): every node with a free out- / in-slot proposes its best
+    candidate edge whose other end is free, and an edge both ends proposed becomes a link.  first_round == 0 starts from the empty
+    cover; a later call continues on `ws`, which the caller keeps and leaves untouched in between.
+    idx: the graph's index (dict of graph.index(device)); scores [E] in edge-id order; round_links: a contiguous int64 [rounds]
+    device tensor that receives the links every round of this call added; link_succ / link_pred: contiguous int32 [n] tensors that
+    receive the cover so far in the CALLER's node numbering (edge ids, -1: the slot is free) -- what bog_contigs takes as best_succ
+    / best_pred; ws: a contiguous uint8 tensor of at least cover_workspace_bytes(n) bytes (the state between calls)."""
+    lib = _lib.load()
+    n = int(idx["in_ptr"].numel()) - 1
+    nperm = idx.get("nperm")
+    _chk_dev(scores, round_links, link_succ, link_pred, ws, nperm, *[idx[k] for k in _COVER_INDEX_KEYS])
+    x = _f32c(scores.detach().reshape(-1).float())     # .float(): a half or bf16 tensor is compared as its fp32 copy (exact widening)
+    E = x.numel()
+    if E != idx["perm"].numel():
+        raise ValueError(f"cover_rounds: {E} scores for an index of {idx['perm'].numel()} edges")
+    if round_links.dtype != torch.int64 or round_links.dim() != 1 or not round_links.is_contiguous():
+        raise ValueError("cover_rounds: round_links must be a contiguous int64 [rounds] tensor")
+    if int(first_round) < 0:
+        raise ValueError(f"cover_rounds: first_round = {first_round}: expected >= 0")
+    for name, t in (("link_succ", link_succ), ("link_pred", link_pred)):
+        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"cover_rounds: {name} must be a contiguous int32 [{n}] tensor")
+    if any(idx[k].dtype != torch.int32 or not idx[k].is_contiguous() for k in _COVER_INDEX_KEYS) or \
+            (nperm is not None and (nperm.dtype != torch.int32 or nperm.numel() != n or not nperm.is_contiguous())):
+        raise ValueError("cover_rounds: the index arrays must be contiguous int32 tensors (graph.index())")
+    need = lib.gnm_cover_workspace_bytes(n)
+    if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError(f"cover_rounds: ws must be a contiguous uint8 tensor of at least {need} bytes (cover_workspace_bytes)")
+    _call("gnm_cover_rounds", n, E, _ptr(idx["perm"]), _ptr(idx["isrc"]), _ptr(idx["in_ptr"]), _ptr(idx["out_ptr"]), _ptr(idx["out_pos"]),
+          _ptr(idx["out_dst"]), _ptr(nperm), _ptr(x), float(min_logit), int(first_round), int(round_links.numel()), _ptr(round_links),
+          _ptr(link_succ), _ptr(link_pred), _ptr(ws), int(ws.numel()), _stream())
+
+
+def cover_workspace_bytes(n: int) -> int:
+    """gnm_cover_workspace_bytes: the bytes of state cover_rounds keeps per graph of n nodes between its calls."""
+    return int(_lib.load().gnm_cover_workspace_bytes(int(n)))
+
+
 SEQ_COUNTERS = ("contigs", "pieces", "bases", "clamped", "empty", "reverse", "invalid", "calls")
 SEQ_RECORD_WORDS = len(SEQ_COUNTERS)       # the int64 words of a gnm_seq_record (include/gnm.h), in order
 SEQ_CHUNK_BASES = 4096                     # GNM_SEQ_CHUNK_BASES: output bases a workgroup of gnm_seq_emit owns at a time

@@ -276,17 +276,22 @@ class DecisionStats:
 
 
 ASSEMBLY_MIN_NODES = 20      # History.assembly_valid pools the contigs of at least this many nodes (the decode's len_threshold)
+ASSEMBLY_DECODERS = ("best_overlap", "greedy_cover")    # the hyper-parameter "assembly_decoder": which cover AssemblyStats decodes
 
 
 class AssemblyStats:
     """The best-overlap contigs of an epoch's validation graphs: `rec`, the sum of their gnm_bog_records (int64 [8], host), and the
     bases of the contigs of at least `min_nodes` nodes, pooled.  add() decodes one graph on the device (decode.best_overlap_contigs:
-    one host synchronisation) and needs a HIP device.  Under torch.distributed all_reduce_() sums the records and gathers the pooled
+    one host synchronisation; with decoder="greedy_cover" decode.greedy_cover_contigs, the mutual-best links iterated to the greedy
+    path cover: one more synchronisation per chunk of rounds) and needs a HIP device.  Under torch.distributed all_reduce_() sums the records and gathers the pooled
     lengths (all_gather_object), once per epoch."""
 
-    def __init__(self, device, min_nodes: int = ASSEMBLY_MIN_NODES):
+    def __init__(self, device, min_nodes: int = ASSEMBLY_MIN_NODES, decoder: str = "best_overlap"):
+        if decoder not in ASSEMBLY_DECODERS:
+            raise ValueError(f"AssemblyStats: decoder {decoder!r}: expected one of {ASSEMBLY_DECODERS}")
         self.device = torch.device(device)
         self.min_nodes = int(min_nodes)
+        self.decoder = decoder
         self.zero_()
 
     def zero_(self):
@@ -297,7 +302,8 @@ class AssemblyStats:
 
     def add(self, graph, scores, y=None):
         from . import decode
-        c = decode.best_overlap_contigs(graph, scores.detach(), graph.edata["prefix_length"], graph.ndata["read_length"], y)
+        cover = decode.greedy_cover_contigs if self.decoder == "greedy_cover" else decode.best_overlap_contigs
+        c = cover(graph, scores.detach(), graph.edata["prefix_length"], graph.ndata["read_length"], y)
         self.rec += np.asarray(c.stats.words(), np.int64)
         keep = c.num_nodes() >= self.min_nodes
         self.bases += c.bases[keep].cpu().tolist()

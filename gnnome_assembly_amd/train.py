@@ -23,7 +23,8 @@ Differences from the reference, all deliberate:
     GNM_DECISION_METRICS=1, GNM_ASSEMBLY_METRICS=1, else off) every validation forward also feeds its logits to an observer on the
     device (metrics.py: RankingStats, DecisionStats, AssemblyStats), read once per epoch: History gains AUROC, average precision and
     the best-F1 threshold / the greedy decode's branch accuracies / contig count, N50, longest contig and wrong-link share of the
-    best-overlap contigs.  With batch_size_eval > 1 the decisions are counted on each batch's sub-graph and summed (a node at a cut
+    best-overlap contigs ("assembly_decoder": "greedy_cover", default GNM_ASSEMBLY_DECODER, else "best_overlap": of the greedy path
+    cover instead).  With batch_size_eval > 1 the decisions are counted on each batch's sub-graph and summed (a node at a cut
     sees only the candidates inside its batch) and "assembly_metrics" is refused (a cover across cluster cuts means nothing).  Under
     the symmetry loss the observers see the original scores.  Loss, schedule, best-model choice and every other History field are
     the same either way;
@@ -46,7 +47,7 @@ import torch
 import torch.distributed as dist
 
 from . import cluster, dp, engine, models
-from .metrics import (ASSEMBLY_MIN_NODES, DECISION_COUNTERS, DECISION_RECORD_WORDS, RANK_BINS, AssemblyStats, BestF1,  # noqa: F401
+from .metrics import (ASSEMBLY_DECODERS, ASSEMBLY_MIN_NODES, DECISION_COUNTERS, DECISION_RECORD_WORDS, RANK_BINS, AssemblyStats, BestF1,  # noqa: F401
                       DecisionCounts, DecisionMetrics, DecisionStats, EpochStats, RankingMetrics, RankingStats, _ratio,
                       calculate_metrics, rank_bin_lower_edge, tfpn_counts)
 
@@ -76,6 +77,9 @@ def get_hyperparameters() -> Dict:
         "decision_metrics": os.environ.get("GNM_DECISION_METRICS", "0").strip() == "1",
         # contig count, N50, longest contig and wrong-link share of the best-overlap contigs of every validation epoch (AssemblyStats)
         "assembly_metrics": os.environ.get("GNM_ASSEMBLY_METRICS", "0").strip() == "1",
+        # ... of which decoder: "best_overlap" (mutual-best links, decode.best_overlap_contigs) or "greedy_cover" (those links iterated
+        # to the greedy path cover, decode.greedy_cover_contigs); only read when assembly_metrics is on
+        "assembly_decoder": os.environ.get("GNM_ASSEMBLY_DECODER", "").strip().lower() or "best_overlap",
         # read-masking coverage augmentation: every TRAINING step keeps a fraction f = randint(low, high) / 100 of the reads (per cent,
         # 1 <= low <= high <= 100; 100 / 100: off) and runs on the induced sub-graph with its own degrees in `pe`; the 16 PageRank
         # columns are carried from the parent unless mask_recompute_pe.  Validation is never masked.
@@ -120,6 +124,8 @@ def _check_hyperparameters(hp: Dict, hooks: Dict, train_samples, valid_samples) 
         raise ValueError(f"hyper-parameter decision_metrics={hp['decision_metrics']!r}: expected True or False")
     if not isinstance(hp["assembly_metrics"], (bool, np.bool_)):
         raise ValueError(f"hyper-parameter assembly_metrics={hp['assembly_metrics']!r}: expected True or False")
+    if hp["assembly_decoder"] not in ASSEMBLY_DECODERS:
+        raise ValueError(f"hyper-parameter assembly_decoder={hp['assembly_decoder']!r}: expected one of {ASSEMBLY_DECODERS}")
     if hp["assembly_metrics"]:
         if hp["batch_size_eval"] > 1:
             raise ValueError("hyper-parameter assembly_metrics=True with batch_size_eval > 1: the contigs are decoded on the whole "
@@ -347,7 +353,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     # {fp64 loss sum, steps, TP..FN} of the pass under way (training, then validation) and of one graph's batches (mini-batch mode):
     # filled by the loss kernel (fused), or by record() below
     ep_stats, graph_stats = EpochStats(dev), EpochStats(dev)
-    observers = [(cls(dev), add, entries) for key, cls, add, entries in _OBSERVERS if hp[key]]
+    observers = [(cls(dev, decoder=hp["assembly_decoder"]) if cls is AssemblyStats else cls(dev), add, entries)
+                 for key, cls, add, entries in _OBSERVERS if hp[key]]
     if masking:
         # a generator of its own: the global `random` decides the shuffle order, which masking must not change
         mask_rng = random.Random(f"read-mask:{seed}")

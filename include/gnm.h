@@ -819,6 +819,46 @@ int gnm_bog_contigs(int64_t n, int64_t E, const int32_t* src, const int32_t* dst
                     void* record, int32_t* contig_ptr, int32_t* walk_nodes, int32_t* walk_edges, int64_t* contig_bases,
                     int32_t* contig_wrong, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- cover rounds: the greedy path cover by iterated mutual-best links (locally-dominant matching) -- all on the device -------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: two new symbols, no existing signature changes.)
+ * gnm_decision_stats + gnm_bog_contigs keep an edge only when both of its ends rank it first, and stop.  That is round one of this
+ * sequence: take the mutual-best edges, mark their out-slot and in-slot as used, let every node with a free slot choose again
+ * among the edges whose other end is still free, repeat.  The fixed point is the greedy path cover of overlap-layout assemblers:
+ * the edges by descending score (lowest edge id among equals), an edge accepted when its source has no successor and its
+ * destination no predecessor yet.  Cycles can close; they are cut afterwards by gnm_bog_contigs, which takes link_succ /
+ * link_pred unchanged in place of best_succ / best_pred (the tables are mutual by construction: it never refuses an entry).
+ * DEVICE pointers; perm .. out_dst, nperm: the graph's index as for gnm_decision_stats (idst is not needed); scores [E] fp32 in
+ * EDGE-ID order.
+ * State, per node in the index's internal numbering, kept in ws between calls: msucc / mpred, the edge id of the accepted out- /
+ *   in-edge, or -1.
+ * Candidates: an edge k = (u -> w) with u != w, every position and id in range (row pointers are clamped, an entry outside [0, E)
+ *   or [0, n) drops the candidate before it addresses anything), scores[k] not NaN and scores[k] >= min_logit (-inf: no cut).
+ *   Order: the 32-bit key of "walk decisions" above, the lowest edge id among equal keys; -0 ties +0, -inf is the lowest number.
+ * Round r, on the state after round r - 1 (two launches: propose, link):
+ *   propose  u with msucc[u] < 0 takes cs[u], its best candidate out-edge whose destination w has mpred[w] < 0, or -1; w with
+ *            mpred[w] < 0 takes cp[w], its best candidate in-edge whose source u has msucc[u] < 0, or -1.
+ *   link     u sets msucc[u] = k when k = cs[u] >= 0 and cp[dst k] == k; w sets mpred[w] = k when k = cp[w] >= 0 and
+ *            cs[src k] == k.  Every node writes its own words only.
+ *   round_links[j] (int64 [rounds], j = r - first_round) = the links round r added.  The call zeroes its `rounds` entries first.
+ * gnm_cover_rounds: first_round == 0 sets the state to -1; then rounds first_round .. first_round + rounds - 1 run on it; then
+ *   link_succ[v] / link_pred[v] (int32 [n], the CALLER's numbering through nperm; a row outside [0, n) is never written) receive
+ *   the state so far: they are valid after every call.  first_round > 0 continues on the ws of the previous call, which the caller
+ *   leaves untouched in between.  2 rounds + 2 launches on `stream` (none for n == 0 and rounds == 0), nothing read back: the
+ *   caller reads round_links and stops at the first 0 -- a round that adds nothing leaves a fixed point, and further rounds add
+ *   nothing and change nothing.  The state after any number of rounds is a set of disjoint paths and cycles.
+ * Eight lanes per node stride over its candidates and reduce by shuffles (the decision kernel's layout); a node whose two slots
+ * are taken costs its two state loads.  No cooperative launch, no workgroup waits for another, no float arithmetic, one 64-bit
+ * integer atomic per workgroup and round: the outputs depend on the inputs alone, not on the grid, gnm_set_occupancy_cap or timing.
+ * ws: gnm_cover_workspace_bytes(n) bytes (24 n; 0 for n == 0 and for an n that is refused), 16-byte aligned.
+ * n or E negative or >= 2^31 - 1, first_round or rounds negative or >= 2^31 - 1, a NULL or misaligned round_links with rounds > 0,
+ * NULL row pointers / link_succ / link_pred with n > 0, NULL perm / isrc / out_pos / out_dst / scores with E > 0 and a workspace
+ * that is NULL, short or misaligned are errors, returned before anything is launched.                                             */
+size_t gnm_cover_workspace_bytes(int64_t n);
+int gnm_cover_rounds(int64_t n, int64_t E, const int32_t* perm, const int32_t* isrc, const int32_t* in_ptr, const int32_t* out_ptr,
+                     const int32_t* out_pos, const int32_t* out_dst, const int32_t* nperm, const float* scores, float min_logit,
+                     int64_t first_round, int64_t rounds, int64_t* round_links, int32_t* link_succ, int32_t* link_pred, void* ws,
+                     size_t ws_bytes, void* stream);
+
 /* ---- contig sequences: a packed read store + walks in CSR form -> the contigs' bases as ASCII, on the device ----------------------
  * (Added without raising GNM_ABI_VERSION, which stays 7: four new symbols, no existing signature changes.)
  * evaluate.walk_to_sequence (evaluate.py:36-47) without a string per node.  DEVICE pointers except for gnm_decode_walk_edges.
