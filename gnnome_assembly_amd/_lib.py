@@ -146,6 +146,7 @@ SIGNATURES = {
     "gnm_seq_layout": (_i32, [_i64] * 5 + [_p] * 6 + [_i64] + [_p] * 5 + [_sz, _p]),
     "gnm_seq_emit": (_i32, [_i64] * 3 + [_p] * 5 + [_i64, _i64, _p, _i64, _p]),
     "gnm_decode_walk_edges": (_i32, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p]),
+    "gnm_transitive_support": (_i32, [_i64, _i64] + [_p] * 10 + [_f32, _i64] + [_p] * 4),
 }
 
 

@@ -29,6 +29,10 @@ edge is not the successor's best predecessor, the cover does not.
 `greedy_cover_contigs` iterates those mutual-best links on the device (gnm_cover_rounds) until no node with a free slot finds a
 free partner: the greedy path cover of overlap-layout assemblers, of which `best_overlap_contigs` is round one.
 
+`transitive_support` marks, on the device (gnm_transitive_support), the candidate edges a two-step path of shorter prefix explains
+(the string-graph reduction); with reduce_transitive=True the two cover decoders run on the scores with those edges masked out, so
+that a link cannot jump over reads and leave them to a parallel contig.
+
 `contig_sequences` turns the walks of any of the decoders into bases on the device over a packed `reads.ReadStore`
 (gnm_seq_layout / gnm_seq_emit), `ContigSequences.write_fasta`, `ng50` and `quick_evaluation` are evaluate.py's FASTA and report."""
 from __future__ import annotations
@@ -44,7 +48,8 @@ import torch
 from . import _lib
 
 __all__ = ["DecodeGraph", "sample_edges", "get_contigs", "get_contigs_device", "infer_contigs", "decision_table",
-           "best_overlap_contigs", "greedy_cover_contigs", "BogContigs", "BogStats", "resolve_strands", "ResolvedContigs", "n50",
+           "best_overlap_contigs", "greedy_cover_contigs", "BogContigs", "BogStats", "transitive_support", "TransitiveSupport",
+           "ReduceStats", "resolve_strands", "ResolvedContigs", "n50",
            "contig_sequences", "ContigSequences", "SeqStats", "walk_edge_ids", "ng50", "quick_evaluation", "CHR_LENGTHS"]
 
 
@@ -328,7 +333,92 @@ class BogContigs:
         return int(b.max()) if b.size else 0
 
 
-def best_overlap_contigs(graph, scores, prefix_length, read_length, y=None, min_logit: float = float("-inf")) -> BogContigs:
+@dataclass
+class ReduceStats:
+    """A gnm_reduce_record (include/gnm.h): edges (seen), candidates (no self loop, no NaN, >= min_logit), reduced (candidates with
+    support > 0), reduced_label1 (of those, the edges whose label is 1; 0 without labels), witnesses (the sum of support),
+    max_support, self_loops, calls."""
+    edges: int = 0
+    candidates: int = 0
+    reduced: int = 0
+    reduced_label1: int = 0
+    witnesses: int = 0
+    max_support: int = 0
+    self_loops: int = 0
+    calls: int = 0
+
+    @property
+    def reduced_fraction(self) -> float:
+        """reduced / candidates; NaN without a candidate."""
+        return float(self.reduced) / float(self.candidates) if self.candidates else float("nan")
+
+    def words(self) -> List[int]:
+        return [self.edges, self.candidates, self.reduced, self.reduced_label1, self.witnesses, self.max_support, self.self_loops,
+                self.calls]
+
+
+class TransitiveSupport:
+    """transitive_support's result, on the graph's device: support int32 [E] and masked_scores fp32 [E] in edge-id order (the
+    scores, NaN on every reduced edge), stats: ReduceStats."""
+
+    def __init__(self, support, masked_scores, stats: ReduceStats):
+        self.support, self.masked_scores, self.stats = support, masked_scores, stats
+
+
+def _reduce_args(who: str, reduce_transitive, fuzz):
+    """Checks the two arguments the cover decoders share; returns fuzz as given."""
+    from .engine import reduce_fuzz_word
+    if not isinstance(reduce_transitive, (bool, np.bool_)):
+        raise ValueError(f"{who}: reduce_transitive={reduce_transitive!r}: expected True or False")
+    reduce_fuzz_word(fuzz, f"{who}: fuzz")
+    return fuzz
+
+
+def _reduce_launch(g, scores, pl, y, min_logit, fuzz):
+    """The launch behind transitive_support and the decoders' reduce_transitive: (support, masked_scores, record), nothing read
+    back.  pl: int64 [E] on the graph's device."""
+    from . import engine
+    dev = g.device
+    E = g.num_edges()
+    if scores.numel() != E or pl.numel() != E:
+        raise ValueError("scores / prefix_length need one entry per edge")
+    with torch.cuda.device(dev):
+        support = torch.empty(E, dtype=torch.int32, device=dev)
+        masked = torch.empty(E, dtype=torch.float32, device=dev)
+        rec = torch.zeros(engine.REDUCE_RECORD_WORDS, dtype=torch.int64, device=dev)
+        engine.transitive_support(g.index(dev), scores, pl, y, min_logit, fuzz, support, masked, rec)
+    return support, masked, rec
+
+
+def _reduce_stats(rec) -> ReduceStats:
+    return ReduceStats(*[int(v) for v in rec.cpu().tolist()])
+
+
+def transitive_support(graph, scores, prefix_length, y=None, min_logit: float = float("-inf"), fuzz: Optional[int] = None
+                       ) -> TransitiveSupport:
+    """The string-graph reduction of the candidate edges of `scores`, computed on the device in one launch
+    (gnm_transitive_support).  A candidate is the cover decoders': no self loop, a score that is no NaN and >= min_logit.  For
+    every edge k = (a -> c), support[k] counts the candidate out-edges j = (a -> b) of a, b not a and not c, with
+    prefix_length[j] < prefix_length[k] strictly, for which a candidate edge m = (b -> c) exists -- with an integer fuzz >= 0 one
+    that also has |prefix_length[j] + prefix_length[m] - prefix_length[k]| <= fuzz (None: no length test).  An edge is reduced
+    when it is a candidate and its support is above 0; masked_scores holds the scores with a NaN on every reduced edge, which
+    every decoder of this module treats as no candidate.  The strict < keeps two edges from removing each other and never reduces
+    a node's candidate out-edge of uniquely smallest prefix.
+    `graph`: an AssemblyGraph on a HIP device; `scores`, `prefix_length`, `y` (optional, for stats.reduced_label1): [E] in edge-id
+    order.  One host synchronisation: the read of the record."""
+    from .graph import as_assembly_graph
+    _reduce_args("transitive_support", True, fuzz)
+    g = as_assembly_graph(graph)
+    dev = g.device
+    if dev.type != "cuda":
+        raise _lib.GnmError("transitive_support: the graph must be on a HIP device (no CPU fallback)")
+    pl = torch.as_tensor(prefix_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    support, masked, rec = _reduce_launch(g, scores, pl, y, min_logit, fuzz)
+    return TransitiveSupport(support, masked, _reduce_stats(rec))
+
+
+def best_overlap_contigs(graph, scores, prefix_length, read_length, y=None, min_logit: float = float("-inf"),
+                         reduce_transitive: bool = False, fuzz: Optional[int] = None) -> BogContigs:
     """Contigs of the best-overlap graph of `scores`, computed on the device: an edge is kept only when it is the top-scored
     out-edge of its source AND the top-scored in-edge of its destination (the tables of gnm_decision_stats; self loops out, ties
     to the lowest edge id, NaN lowest), not NaN and >= min_logit.  Every node then has at most one successor and one predecessor;
@@ -336,10 +426,14 @@ def best_overlap_contigs(graph, scores, prefix_length, read_length, y=None, min_
     Deterministic: no sampling, no host walk, the same bits on every run.  `graph`: an AssemblyGraph on a HIP device; `scores`
     [E] in edge-id order; prefix_length [E], read_length [N] (g.edata['prefix_length'], g.ndata['read_length']); `y` [E]
     (optional): the labels, for the wrong-link counts.  One host synchronisation: the read of the 8-word record, for the contig
-    count.  The two strands of a read may both be covered: see resolve_strands."""
+    count.  The two strands of a read may both be covered: see resolve_strands.
+    reduce_transitive=True: transitive_support(graph, scores, prefix_length, y, min_logit, fuzz) runs first and its masked_scores
+    take the place of the scores in every later call; the result additionally carries `reduce_stats` (ReduceStats).  False (the
+    default) launches nothing more and `fuzz` is not read."""
     from . import engine
     from .graph import as_assembly_graph
     from .metrics import DecisionStats
+    _reduce_args("best_overlap_contigs", reduce_transitive, fuzz)
     g = as_assembly_graph(graph)
     dev = g.device
     if dev.type != "cuda":
@@ -352,6 +446,9 @@ def best_overlap_contigs(graph, scores, prefix_length, read_length, y=None, min_
     with torch.cuda.device(dev):
         i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
         best_succ, best_pred = i32(n), i32(n)
+        red = None
+        if reduce_transitive:
+            _, scores, red = _reduce_launch(g, scores, pl, y, min_logit, fuzz)
         DecisionStats(dev).add(g, scores, y, best_succ, best_pred)
         src, dst = g.edges()
         rec = torch.zeros(engine.BOG_RECORD_WORDS, dtype=torch.int64, device=dev)
@@ -361,14 +458,18 @@ def best_overlap_contigs(graph, scores, prefix_length, read_length, y=None, min_
                            min_logit)
         stats = BogStats(*[int(v) for v in rec.cpu().tolist()])        # the one synchronisation
     C = stats.contigs
-    return BogContigs(contig_ptr[:C + 1], walk_nodes, walk_edges, bases[:C], wrong[:C], stats, pl, rl)
+    out = BogContigs(contig_ptr[:C + 1], walk_nodes, walk_edges, bases[:C], wrong[:C], stats, pl, rl)
+    if red is not None:
+        out.reduce_stats = _reduce_stats(red)
+    return out
 
 
 COVER_CHECK_EVERY = 4      # rounds per chunk of greedy_cover_contigs: one read-back of the chunk's round_links
 
 
 def greedy_cover_contigs(graph, scores, prefix_length, read_length, y=None, min_logit: float = float("-inf"),
-                         max_rounds: Optional[int] = None, check_every: int = COVER_CHECK_EVERY) -> BogContigs:
+                         max_rounds: Optional[int] = None, check_every: int = COVER_CHECK_EVERY, reduce_transitive: bool = False,
+                         fuzz: Optional[int] = None) -> BogContigs:
     """Contigs of the greedy path cover of `scores`, computed on the device: best_overlap_contigs' mutual-best links are round one
     of a sequence (gnm_cover_rounds) in which every node that still has a free out- or in-slot chooses again among its edges whose
     other end is free too, until a round adds nothing.  The fixed point is the path cover of overlap-layout assemblers -- the edges
@@ -382,9 +483,13 @@ def greedy_cover_contigs(graph, scores, prefix_length, read_length, y=None, min_
     Arguments and result as for best_overlap_contigs (stats.dropped is always 0: a refused edge is never proposed); the result
     additionally carries `rounds` (the rounds run, up to and including the first empty one), `round_links` (list: the links every
     one of them added) and `converged` (bool: the last of them added nothing).  The two strands of a read may both be covered:
-    see resolve_strands."""
+    see resolve_strands.
+    reduce_transitive=True: transitive_support(graph, scores, prefix_length, y, min_logit, fuzz) runs first and the rounds and the
+    contig pass see its masked_scores, so no link jumps over a read that a two-step path of shorter prefix reaches; the result
+    additionally carries `reduce_stats` (ReduceStats).  False (the default) launches nothing more and `fuzz` is not read."""
     from . import engine
     from .graph import as_assembly_graph
+    _reduce_args("greedy_cover_contigs", reduce_transitive, fuzz)
     g = as_assembly_graph(graph)
     dev = g.device
     if dev.type != "cuda":
@@ -402,6 +507,9 @@ def greedy_cover_contigs(graph, scores, prefix_length, read_length, y=None, min_
     with torch.cuda.device(dev):
         i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
         idx = g.index(dev)
+        red = None
+        if reduce_transitive:
+            _, scores, red = _reduce_launch(g, scores, pl, y, min_logit, fuzz)
         link_succ, link_pred = i32(n), i32(n)
         ws = torch.empty(engine.cover_workspace_bytes(n), dtype=torch.uint8, device=dev)
         round_links, converged = [], False
@@ -424,6 +532,8 @@ def greedy_cover_contigs(graph, scores, prefix_length, read_length, y=None, min_
     out = BogContigs(contig_ptr[:C + 1], walk_nodes, walk_edges, bases[:C], wrong[:C], stats, pl, rl)
     out.rounds, out.round_links, out.converged = len(round_links), round_links, converged
     out.link_succ, out.link_pred = link_succ, link_pred
+    if red is not None:
+        out.reduce_stats = _reduce_stats(red)
     return out
 
 
@@ -687,7 +797,8 @@ def contig_sequences(walks, graph, reads, prefix_length=None, read_length=None) 
 
 
 def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int = 50, len_threshold: int = 20,
-                  device_sampling: bool = False, decision_report: bool = False, decoder: str = "greedy", reads=None):
+                  device_sampling: bool = False, decision_report: bool = False, decoder: str = "greedy", reads=None,
+                  reduce_transitive: bool = False, fuzz: Optional[int] = None):
     """The per-graph body of inference.inference (inference.py:444-490): logits of the whole graph under
     no_grad in eval mode, stored by edge id, then greedy decode.  Returns (scores [E], walks).
     device_sampling=True: the logits stay on the device for `get_contigs_device` (same distribution of start edges,
@@ -698,16 +809,23 @@ def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int
     deterministic, computed on the device, no sampling (nb_paths and device_sampling are not used).
     decoder="greedy_cover": the same over greedy_cover_contigs, the mutual-best links iterated to the greedy path cover.
     reads: a ReadStore on the graph's device: contig_sequences(walks, graph, reads, prefix_length) -- the walks' bases, ready for
-    ContigSequences.write_fasta (inference.py:497-501) -- is appended as the LAST element of the returned tuple."""
+    ContigSequences.write_fasta (inference.py:497-501) -- is appended as the LAST element of the returned tuple.
+    reduce_transitive, fuzz: handed to best_overlap_contigs / greedy_cover_contigs (the string-graph reduction ahead of the cover).
+    The sampled decoder refuses reduce_transitive=True: its walks already absorb the nodes they jump over."""
     if decoder not in ("greedy", "best_overlap", "greedy_cover"):
         raise ValueError(f"decoder {decoder!r}: expected 'greedy', 'best_overlap' or 'greedy_cover'")
+    _reduce_args("infer_contigs", reduce_transitive, fuzz)
+    if reduce_transitive and decoder == "greedy":
+        raise ValueError("infer_contigs: reduce_transitive=True with decoder='greedy': the sampled walks already absorb the nodes "
+                         "they jump over; the reduction belongs to decoder='best_overlap' and 'greedy_cover'")
     model.eval()
     with torch.no_grad():
         scores = model(graph, None, e, pe).squeeze(-1)                 # inference.py:453-454
     report = decision_table(graph, scores, getattr(graph, "edata", {}).get("y")) if decision_report else None
     if decoder in ("best_overlap", "greedy_cover"):
         cover = best_overlap_contigs if decoder == "best_overlap" else greedy_cover_contigs
-        walks = resolve_strands(cover(graph, scores, prefix_length, read_length, getattr(graph, "edata", {}).get("y")),
+        extra = dict(reduce_transitive=True, fuzz=fuzz) if reduce_transitive else {}
+        walks = resolve_strands(cover(graph, scores, prefix_length, read_length, getattr(graph, "edata", {}).get("y"), **extra),
                                 len_threshold).walks
         return _with_sequences((scores, walks, report) if decision_report else (scores, walks), walks, graph, reads, prefix_length)
     src, dst = graph.edges()

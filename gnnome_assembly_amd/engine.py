@@ -2382,6 +2382,62 @@ def cover_workspace_bytes(n: int) -> int:
     return int(_lib.load().gnm_cover_workspace_bytes(int(n)))
 
 
+REDUCE_COUNTERS = ("edges", "candidates", "reduced", "reduced_label1", "witnesses", "max_support", "self_loops", "calls")
+REDUCE_RECORD_WORDS = len(REDUCE_COUNTERS)  # the int64 words of a gnm_reduce_record (include/gnm.h), in order
+
+
+def reduce_fuzz_word(fuzz, what: str = "fuzz") -> int:
+    """The `fuzz` argument of gnm_transitive_support for a Python value: -1 for None (no length test), else the integer, which
+    must be >= 0 (a bool is refused: it is no length); `what` names the argument in the ValueError."""
+    if fuzz is None:
+        return -1
+    ok = not isinstance(fuzz, bool) and type(fuzz).__name__ != "bool_" and hasattr(fuzz, "__index__")
+    if not ok or not 0 <= operator.index(fuzz) < 2 ** 63:
+        raise ValueError(f"{what}={fuzz!r}: expected None or an integer >= 0")
+    return operator.index(fuzz)
+
+
+@on_device_of(lambda idx, scores, prefix_length, y, min_logit, fuzz, support, masked_scores, rec: rec)
+def transitive_support(idx, scores, prefix_length, y, min_logit, fuzz, support, masked_scores, rec):
+    """The transitive support of every edge (gnm_transitive_support: one launch on the current stream, no workspace, no host
+    synchronisation): for k = (a -> c) the number of candidate out-edges a -> b of strictly smaller prefix that a candidate b -> c
+    closes -- within `fuzz` bases of prefix_length[k], or at all when fuzz is None / -1.  A candidate is cover_rounds': no self
+    loop, no NaN, scores >= min_logit.
+    idx: the graph's index (dict of graph.index(device)); scores [E], prefix_length [E] int64 and y [E] labels or None in edge-id
+    order; support: a contiguous int32 [E] tensor; masked_scores: None, or a contiguous fp32 [E] tensor (not `scores` itself) that
+    receives the scores with a NaN on every reduced edge (a candidate with support > 0) -- what decision_stats, cover_rounds and
+    bog_contigs take in place of the scores; rec: a contiguous int64 [REDUCE_RECORD_WORDS] device tensor the call ADDS to (the
+    caller zeroes it once).  A graph without an edge launches nothing and leaves rec as it is."""
+    n = int(idx["in_ptr"].numel()) - 1
+    nperm = idx.get("nperm")
+    _chk_dev(scores, prefix_length, y, support, masked_scores, rec, nperm, *[idx[k] for k in _COVER_INDEX_KEYS])
+    x = _f32c(scores.detach().reshape(-1).float())     # .float(): a half or bf16 tensor is compared as its fp32 copy (exact widening)
+    E = x.numel()
+    if E != idx["perm"].numel():
+        raise ValueError(f"transitive_support: {E} scores for an index of {idx['perm'].numel()} edges")
+    if y is not None:
+        y = _f32c(y.reshape(-1).float())
+        if y.numel() != E:
+            raise ValueError(f"transitive_support: {E} scores, {y.numel()} labels")
+    fz = reduce_fuzz_word(fuzz, "transitive_support: fuzz")
+    if rec.dtype != torch.int64 or rec.numel() != REDUCE_RECORD_WORDS or not rec.is_contiguous():
+        raise ValueError(f"transitive_support: rec must be a contiguous int64 [{REDUCE_RECORD_WORDS}] tensor")
+    for name, t, dt in (("prefix_length", prefix_length, torch.int64), ("support", support, torch.int32),
+                        ("masked_scores", masked_scores, torch.float32)):
+        if t is None and name == "masked_scores":
+            continue
+        if t.dtype != dt or t.numel() != E or not t.is_contiguous():
+            raise ValueError(f"transitive_support: {name} must be a contiguous {str(dt).replace('torch.', '')} [{E}] tensor")
+    if masked_scores is not None and E and masked_scores.data_ptr() == x.data_ptr():
+        raise ValueError("transitive_support: masked_scores must not be the scores tensor itself (a witness reads the scores)")
+    if any(idx[k].dtype != torch.int32 or not idx[k].is_contiguous() for k in _COVER_INDEX_KEYS) or \
+            (nperm is not None and (nperm.dtype != torch.int32 or nperm.numel() != n or not nperm.is_contiguous())):
+        raise ValueError("transitive_support: the index arrays must be contiguous int32 tensors (graph.index())")
+    _call("gnm_transitive_support", n, E, _ptr(idx["perm"]), _ptr(idx["isrc"]), _ptr(idx["in_ptr"]), _ptr(idx["out_ptr"]),
+          _ptr(idx["out_pos"]), _ptr(idx["out_dst"]), _ptr(nperm), _ptr(x), _ptr(prefix_length), _ptr(y), float(min_logit), int(fz),
+          _ptr(support), _ptr(masked_scores), _ptr(rec), _stream())
+
+
 SEQ_COUNTERS = ("contigs", "pieces", "bases", "clamped", "empty", "reverse", "invalid", "calls")
 SEQ_RECORD_WORDS = len(SEQ_COUNTERS)       # the int64 words of a gnm_seq_record (include/gnm.h), in order
 SEQ_CHUNK_BASES = 4096                     # GNM_SEQ_CHUNK_BASES: output bases a workgroup of gnm_seq_emit owns at a time

@@ -283,19 +283,27 @@ class AssemblyStats:
     """The best-overlap contigs of an epoch's validation graphs: `rec`, the sum of their gnm_bog_records (int64 [8], host), and the
     bases of the contigs of at least `min_nodes` nodes, pooled.  add() decodes one graph on the device (decode.best_overlap_contigs:
     one host synchronisation; with decoder="greedy_cover" decode.greedy_cover_contigs, the mutual-best links iterated to the greedy
-    path cover: one more synchronisation per chunk of rounds) and needs a HIP device.  Under torch.distributed all_reduce_() sums the records and gathers the pooled
+    path cover: one more synchronisation per chunk of rounds; with reduce_transitive=True either decoder runs behind
+    decode.transitive_support's string-graph reduction, `fuzz` its length tolerance, and `reduce_rec` sums the gnm_reduce_records of
+    this process) and needs a HIP device.  Under torch.distributed all_reduce_() sums the records and gathers the pooled
     lengths (all_gather_object), once per epoch."""
 
-    def __init__(self, device, min_nodes: int = ASSEMBLY_MIN_NODES, decoder: str = "best_overlap"):
+    def __init__(self, device, min_nodes: int = ASSEMBLY_MIN_NODES, decoder: str = "best_overlap", reduce_transitive: bool = False,
+                 fuzz=None):
         if decoder not in ASSEMBLY_DECODERS:
             raise ValueError(f"AssemblyStats: decoder {decoder!r}: expected one of {ASSEMBLY_DECODERS}")
+        if not isinstance(reduce_transitive, (bool, np.bool_)):
+            raise ValueError(f"AssemblyStats: reduce_transitive={reduce_transitive!r}: expected True or False")
+        engine.reduce_fuzz_word(fuzz, "AssemblyStats: fuzz")
         self.device = torch.device(device)
         self.min_nodes = int(min_nodes)
         self.decoder = decoder
+        self.reduce_transitive, self.fuzz = bool(reduce_transitive), fuzz
         self.zero_()
 
     def zero_(self):
         self.rec = np.zeros(engine.BOG_RECORD_WORDS, np.int64)
+        self.reduce_rec = np.zeros(engine.REDUCE_RECORD_WORDS, np.int64)   # the sum of the gnm_reduce_records; moves only when reduce_transitive
         self.bases: List[int] = []
         self.wrong: List[int] = []
         return self
@@ -303,8 +311,13 @@ class AssemblyStats:
     def add(self, graph, scores, y=None):
         from . import decode
         cover = decode.greedy_cover_contigs if self.decoder == "greedy_cover" else decode.best_overlap_contigs
-        c = cover(graph, scores.detach(), graph.edata["prefix_length"], graph.ndata["read_length"], y)
+        extra = dict(reduce_transitive=True, fuzz=self.fuzz) if self.reduce_transitive else {}
+        c = cover(graph, scores.detach(), graph.edata["prefix_length"], graph.ndata["read_length"], y, **extra)
         self.rec += np.asarray(c.stats.words(), np.int64)
+        if self.reduce_transitive:
+            w = np.asarray(c.reduce_stats.words(), np.int64)
+            w[5] = max(int(w[5]), int(self.reduce_rec[5])) - int(self.reduce_rec[5])   # max_support: a maximum, not a sum
+            self.reduce_rec += w
         keep = c.num_nodes() >= self.min_nodes
         self.bases += c.bases[keep].cpu().tolist()
         self.wrong += c.wrong[keep].cpu().tolist()

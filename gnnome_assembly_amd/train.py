@@ -24,7 +24,8 @@ Differences from the reference, all deliberate:
     device (metrics.py: RankingStats, DecisionStats, AssemblyStats), read once per epoch: History gains AUROC, average precision and
     the best-F1 threshold / the greedy decode's branch accuracies / contig count, N50, longest contig and wrong-link share of the
     best-overlap contigs ("assembly_decoder": "greedy_cover", default GNM_ASSEMBLY_DECODER, else "best_overlap": of the greedy path
-    cover instead).  With batch_size_eval > 1 the decisions are counted on each batch's sub-graph and summed (a node at a cut
+    cover instead; "assembly_reduce_transitive", default GNM_ASSEMBLY_REDUCE=1, else off: behind the string-graph reduction of
+    decode.transitive_support, "assembly_reduce_fuzz" its length tolerance).  With batch_size_eval > 1 the decisions are counted on each batch's sub-graph and summed (a node at a cut
     sees only the candidates inside its batch) and "assembly_metrics" is refused (a cover across cluster cuts means nothing).  Under
     the symmetry loss the observers see the original scores.  Loss, schedule, best-model choice and every other History field are
     the same either way;
@@ -80,6 +81,11 @@ def get_hyperparameters() -> Dict:
         # ... of which decoder: "best_overlap" (mutual-best links, decode.best_overlap_contigs) or "greedy_cover" (those links iterated
         # to the greedy path cover, decode.greedy_cover_contigs); only read when assembly_metrics is on
         "assembly_decoder": os.environ.get("GNM_ASSEMBLY_DECODER", "").strip().lower() or "best_overlap",
+        # ... behind the string-graph reduction of the candidate edges (decode.transitive_support): no link jumps over a read that a
+        # two-step path of shorter prefix reaches; "assembly_reduce_fuzz": None, or the bases by which the two steps' prefixes may
+        # miss the edge's; both only read when assembly_metrics is on
+        "assembly_reduce_transitive": os.environ.get("GNM_ASSEMBLY_REDUCE", "0").strip() == "1",
+        "assembly_reduce_fuzz": None,
         # read-masking coverage augmentation: every TRAINING step keeps a fraction f = randint(low, high) / 100 of the reads (per cent,
         # 1 <= low <= high <= 100; 100 / 100: off) and runs on the induced sub-graph with its own degrees in `pe`; the 16 PageRank
         # columns are carried from the parent unless mask_recompute_pe.  Validation is never masked.
@@ -126,6 +132,9 @@ def _check_hyperparameters(hp: Dict, hooks: Dict, train_samples, valid_samples) 
         raise ValueError(f"hyper-parameter assembly_metrics={hp['assembly_metrics']!r}: expected True or False")
     if hp["assembly_decoder"] not in ASSEMBLY_DECODERS:
         raise ValueError(f"hyper-parameter assembly_decoder={hp['assembly_decoder']!r}: expected one of {ASSEMBLY_DECODERS}")
+    if not isinstance(hp["assembly_reduce_transitive"], (bool, np.bool_)):
+        raise ValueError(f"hyper-parameter assembly_reduce_transitive={hp['assembly_reduce_transitive']!r}: expected True or False")
+    engine.reduce_fuzz_word(hp["assembly_reduce_fuzz"], "hyper-parameter assembly_reduce_fuzz")
     if hp["assembly_metrics"]:
         if hp["batch_size_eval"] > 1:
             raise ValueError("hyper-parameter assembly_metrics=True with batch_size_eval > 1: the contigs are decoded on the whole "
@@ -353,7 +362,8 @@ def train(train_samples: Sequence[GraphSample], valid_samples: Sequence[GraphSam
     # {fp64 loss sum, steps, TP..FN} of the pass under way (training, then validation) and of one graph's batches (mini-batch mode):
     # filled by the loss kernel (fused), or by record() below
     ep_stats, graph_stats = EpochStats(dev), EpochStats(dev)
-    observers = [(cls(dev, decoder=hp["assembly_decoder"]) if cls is AssemblyStats else cls(dev), add, entries)
+    observers = [(cls(dev, decoder=hp["assembly_decoder"], reduce_transitive=bool(hp["assembly_reduce_transitive"]),
+                      fuzz=hp["assembly_reduce_fuzz"]) if cls is AssemblyStats else cls(dev), add, entries)
                  for key, cls, add, entries in _OBSERVERS if hp[key]]
     if masking:
         # a generator of its own: the global `random` decides the shuffle order, which masking must not change

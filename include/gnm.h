@@ -909,6 +909,40 @@ int gnm_seq_emit(int64_t P, int64_t n, int64_t R, const int32_t* walk_nodes, con
 int gnm_decode_walk_edges(const int32_t* src, const int32_t* dst, int64_t N, int64_t E, const int32_t* succ_ptr, int64_t C,
                           const int32_t* contig_ptr, const int32_t* walk_nodes, int32_t* walk_edges, int64_t* bad);
 
+/* ---- transitive support: the string-graph reduction of the candidate edges ahead of the cover decoders -- one launch ---------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: one new symbol, no existing signature changes.)
+ * The overlap graph is not transitively reduced: a read overlaps its next several neighbours, and a path cover that takes a -> c
+ * over a -> b -> c leaves b to a parallel contig.  This marks the edges a two-step path of shorter prefix explains.
+ * DEVICE pointers; perm .. out_dst, nperm: the graph's index as for gnm_cover_rounds (only perm and the by-source half -- out_ptr,
+ * out_pos, out_dst -- are read); scores [E] fp32, prefix_length [E] int64, y [E] fp32 or NULL: EDGE-ID order.
+ * Candidates: gnm_cover_rounds' -- k = (u -> w) with u != w, scores[k] not NaN and scores[k] >= min_logit (-inf: no cut).
+ * support[k] (int32 [E], edge-id order), for every edge k = (a -> c) with a != c, candidate or not: the number of out-edges
+ *   j = (a -> b) of a with j a candidate, b != a, b != c, prefix_length[j] < prefix_length[k] STRICTLY, and at least one candidate
+ *   m = (b -> c) -- with fuzz >= 0 one that also has |prefix_length[j] + prefix_length[m] - prefix_length[k]| <= fuzz (int64,
+ *   wrapping); fuzz == -1: no length test.  Parallel a -> b edges each count, several parallel b -> c edges make one witness, a
+ *   self loop has support 0.  k is REDUCED when it is a candidate and support[k] > 0.  The strict < keeps two edges from removing
+ *   each other through one another and never reduces a node's candidate out-edge of uniquely smallest prefix.
+ * masked_scores (fp32 [E] or NULL): scores[k], or the quiet NaN 0x7FC00000 where k is reduced -- what gnm_decision_stats,
+ *   gnm_cover_rounds and gnm_bog_contigs take as scores: they treat a NaN as no candidate.  May not alias scores.
+ * record: ADDS  edges (edges seen), candidates, reduced, reduced_label1 (reduced edges with y == 1; 0 when y == NULL), witnesses
+ *   (the sum of support), self_loops, calls (+1), and raises max_support to the largest support seen.  8-byte aligned.
+ * Eight lanes per source node stride over its out-edges k and each walks the row again for j; "a candidate b -> c exists" is a
+ * binary search in b's by-source row, whose destinations ascend, and a scan of the equal range: d^2 log d steps for out-degree d.
+ * Every edge is written by the one lane that owns it: plain stores, no atomics but one integer atomic per record word and
+ * workgroup, no workspace, no float arithmetic, no cooperative launch: the outputs depend on the inputs alone, not on the grid or
+ * gnm_set_occupancy_cap.  Row pointers are clamped; a position or edge id outside [0, E) or a node outside [0, n) drops that edge
+ * (not counted, not written) or witness before it addresses anything.
+ * n == 0 and E == 0 are valid: nothing is launched and the record stays as it is.  n or E negative or >= 2^31 - 1, fuzz < -1, a
+ * NULL or misaligned record, NULL out_ptr with n > 0 and NULL perm / out_pos / out_dst / scores / prefix_length / support with
+ * E > 0 are errors, returned before anything is launched.                                                                         */
+typedef struct gnm_reduce_record {
+  int64_t edges, candidates, reduced, reduced_label1, witnesses, max_support, self_loops, calls;
+} gnm_reduce_record;
+int gnm_transitive_support(int64_t n, int64_t E, const int32_t* perm, const int32_t* isrc, const int32_t* in_ptr,
+                           const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, const int32_t* nperm,
+                           const float* scores, const int64_t* prefix_length, const float* y, float min_logit, int64_t fuzz,
+                           int32_t* support, float* masked_scores, void* record, void* stream);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
