@@ -147,6 +147,8 @@ SIGNATURES = {
     "gnm_seq_emit": (_i32, [_i64] * 3 + [_p] * 5 + [_i64, _i64, _p, _i64, _p]),
     "gnm_decode_walk_edges": (_i32, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p]),
     "gnm_transitive_support": (_i32, [_i64, _i64] + [_p] * 10 + [_f32, _i64] + [_p] * 4),
+    "gnm_overlap_align": (_i32, [_i64] + [_p] * 4 + [_i64, _p, _p, _i64, _i64, _i32] + [_p] * 5),
+    "gnm_overlap_align_host": (_i32, [_i64] + [_p] * 4 + [_i64, _p, _p, _i64, _i64, _i32] + [_p] * 4 + [_i32]),
 }
 
 

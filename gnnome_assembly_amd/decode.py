@@ -49,7 +49,7 @@ from . import _lib
 
 __all__ = ["DecodeGraph", "sample_edges", "get_contigs", "get_contigs_device", "infer_contigs", "decision_table",
            "best_overlap_contigs", "greedy_cover_contigs", "BogContigs", "BogStats", "transitive_support", "TransitiveSupport",
-           "ReduceStats", "resolve_strands", "ResolvedContigs", "n50",
+           "ReduceStats", "resolve_strands", "ResolvedContigs", "n50", "junction_identity", "JunctionIdentity",
            "contig_sequences", "ContigSequences", "SeqStats", "walk_edge_ids", "ng50", "quick_evaluation", "CHR_LENGTHS"]
 
 
@@ -796,9 +796,53 @@ def contig_sequences(walks, graph, reads, prefix_length=None, read_length=None) 
     return seqs
 
 
+@dataclass
+class JunctionIdentity:
+    """junction_identity's result, on the graph's device, one entry per contig: junctions int64 [C] (the contig's nodes - 1),
+    edit_distance int64 [C] (the sum of the junction edges' edit distances; an exceeded junction adds max_errors + 1, an invalid
+    one nothing), exceeded int64 [C] (junctions whose distance exceeds max_errors).  `features`: the per-edge OverlapFeatures
+    the sums were gathered from."""
+    junctions: torch.Tensor
+    edit_distance: torch.Tensor
+    exceeded: torch.Tensor
+    features: object
+
+
+def junction_identity(contigs, graph, reads, max_errors: int = 255, prefix_length=None) -> JunctionIdentity:
+    """How many of the junctions contig_sequences glues together agree: features.overlap_features(graph, reads) gathered over
+    the walk edges of `contigs` -- a BogContigs, or lists of node ids whose edge ids are looked up on the host (walk_edge_ids).
+    graph: the AssemblyGraph on a HIP device; reads: a ReadStore on that device.  Torch indexing only, no kernel of its own."""
+    from . import features
+    if prefix_length is None:
+        prefix_length = getattr(graph, "edata", {}).get("prefix_length")
+        if prefix_length is None and isinstance(contigs, BogContigs):
+            prefix_length = contigs.prefix_length
+    f = features.overlap_features(graph, reads, prefix_length, max_errors)
+    dev = graph.device
+    if isinstance(contigs, BogContigs):
+        contig_ptr, walk_edges = contigs.contig_ptr.to(dev).long(), contigs.walk_edges.to(dev).long()
+    else:
+        src, dst = graph.edges()
+        dg = DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), graph.num_nodes())
+        ptr, _, edges = walk_edge_ids(dg, contigs)
+        contig_ptr, walk_edges = torch.from_numpy(ptr).to(dev).long(), torch.from_numpy(edges).to(dev).long()
+    C, P = int(contig_ptr.numel()) - 1, int(walk_edges.numel())
+    contig = torch.repeat_interleave(torch.arange(C, device=dev), contig_ptr[1:] - contig_ptr[:-1], output_size=P)
+    first = torch.zeros(P, dtype=torch.bool, device=dev)
+    first[contig_ptr[:-1][contig_ptr[:-1] < P]] = True
+    junction = ~first & (walk_edges >= 0)
+    e = walk_edges.clamp(min=0)
+    zeros = lambda: torch.zeros(C, dtype=torch.int64, device=dev)  # noqa: E731
+    dist = f.edit_distance.long()[e] if P else zeros()[:0]
+    junctions = zeros().index_add_(0, contig, junction.long())
+    edits = zeros().index_add_(0, contig, torch.where(junction, dist.clamp(min=0), torch.zeros_like(dist)))
+    exceeded = zeros().index_add_(0, contig, (junction & (dist > int(max_errors))).long())
+    return JunctionIdentity(junctions, edits, exceeded, f)
+
+
 def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int = 50, len_threshold: int = 20,
                   device_sampling: bool = False, decision_report: bool = False, decoder: str = "greedy", reads=None,
-                  reduce_transitive: bool = False, fuzz: Optional[int] = None):
+                  reduce_transitive: bool = False, fuzz: Optional[int] = None, junction_report: bool = False):
     """The per-graph body of inference.inference (inference.py:444-490): logits of the whole graph under
     no_grad in eval mode, stored by edge id, then greedy decode.  Returns (scores [E], walks).
     device_sampling=True: the logits stay on the device for `get_contigs_device` (same distribution of start edges,
@@ -811,7 +855,11 @@ def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int
     reads: a ReadStore on the graph's device: contig_sequences(walks, graph, reads, prefix_length) -- the walks' bases, ready for
     ContigSequences.write_fasta (inference.py:497-501) -- is appended as the LAST element of the returned tuple.
     reduce_transitive, fuzz: handed to best_overlap_contigs / greedy_cover_contigs (the string-graph reduction ahead of the cover).
-    The sampled decoder refuses reduce_transitive=True: its walks already absorb the nodes they jump over."""
+    The sampled decoder refuses reduce_transitive=True: its walks already absorb the nodes they jump over.
+    junction_report=True (needs reads): junction_identity(walks, graph, reads, prefix_length=prefix_length) -- per contig the
+    junctions, their summed edit distance and how many exceed the band -- is appended behind the sequences, as the LAST element."""
+    if junction_report and reads is None:
+        raise ValueError("infer_contigs: junction_report=True needs reads (a ReadStore on the graph's device)")
     if decoder not in ("greedy", "best_overlap", "greedy_cover"):
         raise ValueError(f"decoder {decoder!r}: expected 'greedy', 'best_overlap' or 'greedy_cover'")
     _reduce_args("infer_contigs", reduce_transitive, fuzz)
@@ -827,15 +875,22 @@ def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int
         extra = dict(reduce_transitive=True, fuzz=fuzz) if reduce_transitive else {}
         walks = resolve_strands(cover(graph, scores, prefix_length, read_length, getattr(graph, "edata", {}).get("y"), **extra),
                                 len_threshold).walks
-        return _with_sequences((scores, walks, report) if decision_report else (scores, walks), walks, graph, reads, prefix_length)
+        return _with_sequences((scores, walks, report) if decision_report else (scores, walks), walks, graph, reads, prefix_length,
+                               graph if junction_report else None)
     src, dst = graph.edges()
     dg = DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), graph.num_nodes())
     if device_sampling:
         walks = get_contigs_device(dg, scores, prefix_length, read_length, nb_paths, len_threshold)
     else:
         walks = get_contigs(dg, scores, prefix_length, read_length, nb_paths, len_threshold)
-    return _with_sequences((scores, walks, report) if decision_report else (scores, walks), walks, dg, reads, prefix_length)
+    return _with_sequences((scores, walks, report) if decision_report else (scores, walks), walks, dg, reads, prefix_length,
+                           graph if junction_report else None)
 
 
-def _with_sequences(result, walks, graph, reads, prefix_length):
-    return result if reads is None else result + (contig_sequences(walks, graph, reads, prefix_length),)
+def _with_sequences(result, walks, graph, reads, prefix_length, junction_graph=None):
+    if reads is None:
+        return result
+    result = result + (contig_sequences(walks, graph, reads, prefix_length),)
+    if junction_graph is not None:
+        result = result + (junction_identity(walks, junction_graph, reads, prefix_length=prefix_length),)
+    return result

@@ -2501,6 +2501,57 @@ def seq_emit(walk_nodes, piece_off, n: int, base_off, length, packed, total: int
           int(packed.numel()), int(total), _ptr(out), int(out.numel()), _stream())
 
 
+ALIGN_COUNTERS = ("edges", "aligned", "exceeded", "empty", "clamped", "invalid", "cells", "calls")
+ALIGN_RECORD_WORDS = len(ALIGN_COUNTERS)   # the int64 words of a gnm_align_record (include/gnm.h), in order
+ALIGN_MAX_ERRORS = 255                     # the widest band: 2 K + 1 <= 512 diagonals
+
+
+def _align_args(name, src, dst, prefix_length, n, base_off, length, packed, max_errors, dist, overlap_length, similarity, rec):
+    E = int(src.numel())
+    R = _seq_store_args(name, n, base_off, length, packed)
+    if isinstance(max_errors, bool) or not hasattr(max_errors, "__index__") or not 0 <= operator.index(max_errors) <= ALIGN_MAX_ERRORS:
+        raise ValueError(f"{name}: max_errors={max_errors!r}: expected an integer in [0, {ALIGN_MAX_ERRORS}]")
+    if rec.dtype != torch.int64 or rec.numel() != ALIGN_RECORD_WORDS or not rec.is_contiguous():
+        raise ValueError(f"{name}: rec must be a contiguous int64 [{ALIGN_RECORD_WORDS}] tensor")
+    for what, t, dt in (("src", src, torch.int32), ("dst", dst, torch.int32), ("prefix_length", prefix_length, torch.int64),
+                        ("dist", dist, torch.int32), ("overlap_length", overlap_length, torch.int64),
+                        ("similarity", similarity, torch.float32)):
+        if t.dtype != dt or t.numel() != E or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous {str(dt).replace('torch.', '')} [{E}] tensor")
+    return E, R
+
+
+@on_device_of(lambda src, *a, **k: src)
+def overlap_align(src, dst, prefix_length, n: int, base_off, length, packed, max_errors: int, dist, overlap_length, similarity, rec):
+    """The banded edit distance of every edge's overlap (gnm_overlap_align: one launch on the current stream, no workspace, no
+    host synchronisation; none at all for E == 0).  src, dst int32 [E] and prefix_length int64 [E] in edge-id order; n: nodes of
+    the graph; base_off, length int64 [R] and packed uint8 (whole 16-byte groups): the read store; max_errors: the K of the rule,
+    0 .. ALIGN_MAX_ERRORS; dist int32 [E] (K + 1: exceeded, -1: invalid), overlap_length int64 [E], similarity fp32 [E]: outputs;
+    rec: a contiguous int64 [ALIGN_RECORD_WORDS] device tensor the call ADDS to (the caller zeroes it once)."""
+    _lib.load()
+    _chk_dev(src, dst, prefix_length, base_off, length, packed, dist, overlap_length, similarity, rec)
+    E, R = _align_args("overlap_align", src, dst, prefix_length, n, base_off, length, packed, max_errors, dist, overlap_length,
+                       similarity, rec)
+    _call("gnm_overlap_align", E, _ptr(src), _ptr(dst), _ptr(prefix_length), _ptr(packed), int(packed.numel()), _ptr(base_off),
+          _ptr(length), R, int(n), operator.index(max_errors), _ptr(dist), _ptr(overlap_length), _ptr(similarity), _ptr(rec), _stream())
+
+
+def overlap_align_host(src, dst, prefix_length, n: int, base_off, length, packed, max_errors: int, dist, overlap_length, similarity,
+                       rec, threads: int = 1):
+    """overlap_align's arithmetic on the CPU (gnm_overlap_align_host: the same header routine, `threads` host threads): the same
+    arguments as CPU tensors.  For tests and for scale; nothing on the product path calls it."""
+    lib = _lib.load()
+    ts = (src, dst, prefix_length, base_off, length, packed, dist, overlap_length, similarity, rec)
+    if any(t.device.type != "cpu" for t in ts):
+        raise ValueError("overlap_align_host: every tensor must be a CPU tensor")
+    E, R = _align_args("overlap_align_host", src, dst, prefix_length, n, base_off, length, packed, max_errors, dist, overlap_length,
+                       similarity, rec)
+    hp = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
+    _lib.check(lib.gnm_overlap_align_host(E, hp(src), hp(dst), hp(prefix_length), hp(packed), int(packed.numel()), hp(base_off),
+                                          hp(length), R, int(n), operator.index(max_errors), hp(dist), hp(overlap_length),
+                                          hp(similarity), hp(rec), int(threads)), "gnm_overlap_align_host")
+
+
 def optim_workspace(n: int, device) -> torch.Tensor:
     """The workspace of optim_step for flat buffers of n elements (gnm_optim_workspace_bytes), as int64 words: 8-byte aligned."""
     return torch.empty((_lib.load().gnm_optim_workspace_bytes(int(n)) + 7) // 8, dtype=torch.int64, device=device)

@@ -943,6 +943,40 @@ int gnm_transitive_support(int64_t n, int64_t E, const int32_t* perm, const int3
                            const float* scores, const int64_t* prefix_length, const float* y, float min_logit, int64_t fuzz,
                            int32_t* support, float* masked_scores, void* record, void* stream);
 
+/* ---- overlap alignment: the banded edit distance of every edge's overlap, from the packed read store -- one launch ---------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: two new symbols, no existing signature changes.)
+ * The second column of the model's edge input: graph_parser.py:268-282 copies overlap_similarity out of the overlapper's line and
+ * writes 0 where it is missing; this computes an edit-distance identity from the reads instead.  It is NOT the overlapper's own
+ * number, which has no formula in the reference.
+ * gnm_overlap_align takes DEVICE pointers, gnm_overlap_align_host HOST pointers; both run csrc/gnm_align.h.  src, dst int32 [E] and
+ * prefix_length int64 [E] in EDGE-ID order; the store (packed .. R, n) as for "contig sequences".
+ * Rule, integers only.  Edge k = (a -> c), p = prefix_length[k], la / lc the lengths of the two nodes' reads (node v: read v >> 1,
+ *   reverse-complemented when v is odd).  p < 0 or p > la is clamped (counted).  Q = bases [p, la) of a's strand, m = la - p;
+ *   T = bases [0, min(lc, m + K)) of c's strand, K = max_errors.  dist[k] = min over 0 <= j <= |T| of Levenshtein(Q, T[0:j]):
+ *   all of Q is aligned, both start at their first base, the end in T is free; substitution, insertion and deletion cost 1; two
+ *   bases match when their 4-bit codes are EQUAL (N matches N and nothing else, and so every ambiguity code).  A distance above K
+ *   is reported as K + 1 (the edge is `exceeded`); a path of cost <= K never leaves the diagonals |i - j| <= K, so the band gives
+ *   the exact answer otherwise.  overlap_length[k] = m (graph_parser.py:281).  similarity[k] = max(0, 1 - dist / m), ONE fp32
+ *   division of the two integers converted to fp32.  m == 0: dist 0, similarity 0 (`empty`).  A node outside [0, n), a read index
+ *   >= R or a read outside the store: dist -1, overlap_length 0, similarity 0 (`invalid`), nothing is read through it.
+ * max_errors: 0 .. 255.  The band is 1, 2, 4 or 8 words of 64 diagonals (K <= 31, 63, 127, 255), held in registers.
+ * record: ADDS  edges (E), aligned (dist <= K, m > 0), exceeded, empty, clamped, invalid, cells (the sum of m * |T| over the
+ *   aligned edges), calls (+1).  edges == aligned + exceeded + empty + invalid.  8-byte aligned; the caller zeroes it.
+ * One lane per edge, plain stores at the edge's id, one integer atomic per record word and workgroup: outputs and record depend on
+ * the inputs alone, not on the grid or gnm_set_occupancy_cap.  The column loop of an edge runs m times, m taken from the store
+ * before it starts.  E == 0: nothing is launched, the record stays as it is.  E negative or >= 2^31 - 1, max_errors outside
+ * [0, 255], a packed_bytes that is no multiple of 16, a NULL or misaligned record / packed, NULL arrays with E > 0 and (host)
+ * threads outside [1, 1024] are errors, returned before anything runs.                                                           */
+typedef struct gnm_align_record {
+  int64_t edges, aligned, exceeded, empty, clamped, invalid, cells, calls;
+} gnm_align_record;
+int gnm_overlap_align(int64_t E, const int32_t* src, const int32_t* dst, const int64_t* prefix_length, const uint8_t* packed,
+                      int64_t packed_bytes, const int64_t* base_off, const int64_t* length, int64_t R, int64_t n, int max_errors,
+                      int32_t* dist, int64_t* overlap_length, float* similarity, void* record, void* stream);
+int gnm_overlap_align_host(int64_t E, const int32_t* src, const int32_t* dst, const int64_t* prefix_length, const uint8_t* packed,
+                           int64_t packed_bytes, const int64_t* base_off, const int64_t* length, int64_t R, int64_t n, int max_errors,
+                           int32_t* dist, int64_t* overlap_length, float* similarity, void* record, int threads);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
