@@ -46,6 +46,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .engine import RecordStats
 
 __all__ = ["DecodeGraph", "sample_edges", "get_contigs", "get_contigs_device", "infer_contigs", "decision_table",
            "best_overlap_contigs", "greedy_cover_contigs", "BogContigs", "BogStats", "transitive_support", "TransitiveSupport",
@@ -103,6 +104,20 @@ def sample_edges(edge_scores: torch.Tensor, nb_paths: int) -> torch.Tensor:
     return torch.multinomial(p, nb_paths, replacement=True)
 
 
+def _host_walk_args(graph: DecodeGraph, num_scores: int, prefix_length, read_length, visited):
+    """What the host walks of get_contigs / get_contigs_device read besides the scores: (prefix_length, read_length) as int64
+    arrays and `visited` (a fresh one for None), checked against the graph."""
+    n, e = graph.n, graph.src.size
+    pl = np.ascontiguousarray(torch.as_tensor(prefix_length).cpu().numpy().reshape(-1), dtype=np.int64)
+    rl = np.ascontiguousarray(torch.as_tensor(read_length).cpu().numpy().reshape(-1), dtype=np.int64)
+    if num_scores != e or pl.size != e or rl.size != n:
+        raise ValueError("scores / prefix_length need one entry per edge, read_length one per node")
+    vis = np.zeros(n, np.uint8) if visited is None else visited
+    if vis.dtype != np.uint8 or vis.size != n or not vis.flags.c_contiguous:
+        raise ValueError("visited must be a contiguous uint8 array with one entry per node")
+    return pl, rl, vis
+
+
 def get_contigs(graph: DecodeGraph, scores, prefix_length, read_length, nb_paths: int = 50, len_threshold: int = 20,
                 sampler: Callable[[torch.Tensor, int], torch.Tensor] = sample_edges,
                 visited: Optional[np.ndarray] = None) -> List[List[int]]:
@@ -110,15 +125,9 @@ def get_contigs(graph: DecodeGraph, scores, prefix_length, read_length, nb_paths
     (inference.py:182-253).  `scores` [E] in edge-id order (logits), `prefix_length` [E], `read_length` [N]
     (g.edata['prefix_length'], g.ndata['read_length']).  Returns the walks as lists of node ids."""
     lib = _lib.load()
-    n, e = graph.n, graph.src.size
+    n = graph.n
     sc = np.ascontiguousarray(torch.as_tensor(scores).detach().float().cpu().numpy().reshape(-1))
-    pl = np.ascontiguousarray(torch.as_tensor(prefix_length).cpu().numpy().reshape(-1), dtype=np.int64)
-    rl = np.ascontiguousarray(torch.as_tensor(read_length).cpu().numpy().reshape(-1), dtype=np.int64)
-    if sc.size != e or pl.size != e or rl.size != n:
-        raise ValueError("scores / prefix_length need one entry per edge, read_length one per node")
-    vis = np.zeros(n, np.uint8) if visited is None else visited
-    if vis.dtype != np.uint8 or vis.size != n or not vis.flags.c_contiguous:
-        raise ValueError("visited must be a contiguous uint8 array with one entry per node")
+    pl, rl, vis = _host_walk_args(graph, sc.size, prefix_length, read_length, visited)
     sct = torch.from_numpy(sc)
     no_loop = graph.src != graph.dst
     walk = np.empty(2 * n + 2, np.int32)
@@ -177,13 +186,7 @@ def get_contigs_device(graph: DecodeGraph, scores, prefix_length, read_length, n
     n, e = graph.n, graph.src.size
     sd = scores.detach().reshape(-1)
     sd = (sd if sd.dtype == torch.float32 else sd.float()).contiguous()
-    pl = np.ascontiguousarray(torch.as_tensor(prefix_length).cpu().numpy().reshape(-1), dtype=np.int64)
-    rl = np.ascontiguousarray(torch.as_tensor(read_length).cpu().numpy().reshape(-1), dtype=np.int64)
-    if sd.numel() != e or pl.size != e or rl.size != n:
-        raise ValueError("scores / prefix_length need one entry per edge, read_length one per node")
-    vis = np.zeros(n, np.uint8) if visited is None else visited
-    if vis.dtype != np.uint8 or vis.size != n or not vis.flags.c_contiguous:
-        raise ValueError("visited must be a contiguous uint8 array with one entry per node")
+    pl, rl, vis = _host_walk_args(graph, sd.numel(), prefix_length, read_length, visited)
     nb = int(nb_paths)
     if e == 0 or nb <= 0:
         return []
@@ -267,7 +270,7 @@ def n50(lengths) -> int:
 
 
 @dataclass
-class BogStats:
+class BogStats(RecordStats):
     """A gnm_bog_record (include/gnm.h): contigs, links (kept, after the cycle cuts), cycles_cut, dropped (mutual-best edges
     refused for a NaN score or min_logit), wrong_links (links whose label is not 1), multi_nodes / multi_contigs (nodes on and
     number of paths of two or more nodes), calls."""
@@ -283,10 +286,6 @@ class BogStats:
     @property
     def wrong_link_fraction(self) -> float:
         return float(self.wrong_links) / float(self.links) if self.links else float("nan")
-
-    def words(self) -> List[int]:
-        return [self.contigs, self.links, self.cycles_cut, self.dropped, self.wrong_links, self.multi_nodes, self.multi_contigs,
-                self.calls]
 
 
 class BogContigs:
@@ -334,7 +333,7 @@ class BogContigs:
 
 
 @dataclass
-class ReduceStats:
+class ReduceStats(RecordStats):
     """A gnm_reduce_record (include/gnm.h): edges (seen), candidates (no self loop, no NaN, >= min_logit), reduced (candidates with
     support > 0), reduced_label1 (of those, the edges whose label is 1; 0 without labels), witnesses (the sum of support),
     max_support, self_loops, calls."""
@@ -351,10 +350,6 @@ class ReduceStats:
     def reduced_fraction(self) -> float:
         """reduced / candidates; NaN without a candidate."""
         return float(self.reduced) / float(self.candidates) if self.candidates else float("nan")
-
-    def words(self) -> List[int]:
-        return [self.edges, self.candidates, self.reduced, self.reduced_label1, self.witnesses, self.max_support, self.self_loops,
-                self.calls]
 
 
 class TransitiveSupport:
@@ -390,10 +385,6 @@ def _reduce_launch(g, scores, pl, y, min_logit, fuzz):
     return support, masked, rec
 
 
-def _reduce_stats(rec) -> ReduceStats:
-    return ReduceStats(*[int(v) for v in rec.cpu().tolist()])
-
-
 def transitive_support(graph, scores, prefix_length, y=None, min_logit: float = float("-inf"), fuzz: Optional[int] = None
                        ) -> TransitiveSupport:
     """The string-graph reduction of the candidate edges of `scores`, computed on the device in one launch
@@ -414,7 +405,49 @@ def transitive_support(graph, scores, prefix_length, y=None, min_logit: float = 
         raise _lib.GnmError("transitive_support: the graph must be on a HIP device (no CPU fallback)")
     pl = torch.as_tensor(prefix_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
     support, masked, rec = _reduce_launch(g, scores, pl, y, min_logit, fuzz)
-    return TransitiveSupport(support, masked, _reduce_stats(rec))
+    return TransitiveSupport(support, masked, ReduceStats.from_record(rec))
+
+
+def _cover_prologue(who: str, graph, scores, prefix_length, read_length, y, min_logit, reduce_transitive, fuzz):
+    """What the two cover decoders do before they choose links: the argument and device checks, prefix_length / read_length as
+    int64 on the graph's device, and the optional reduction.  Returns (g, scores, pl, rl, red): the AssemblyGraph, the scores the
+    decoder runs on (transitive_support's masked_scores when reducing), and the reduction's record on the device or None."""
+    from .graph import as_assembly_graph
+    _reduce_args(who, reduce_transitive, fuzz)
+    g = as_assembly_graph(graph)
+    dev = g.device
+    if dev.type != "cuda":
+        raise _lib.GnmError(f"{who}: the graph must be on a HIP device (no CPU fallback)")
+    n, E = g.num_nodes(), g.num_edges()
+    pl = torch.as_tensor(prefix_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    rl = torch.as_tensor(read_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    if pl.numel() != E or rl.numel() != n or scores.numel() != E:
+        raise ValueError("scores / prefix_length need one entry per edge, read_length one per node")
+    red = None
+    if reduce_transitive:
+        _, scores, red = _reduce_launch(g, scores, pl, y, min_logit, fuzz)
+    return g, scores, pl, rl, red
+
+
+def _links_to_contigs(g, link_succ, link_pred, scores, y, pl, rl, min_logit, red) -> BogContigs:
+    """The contigs of the links (link_succ, link_pred) -- int32 [n] edge ids on the graph's device, -1: none -- by
+    gnm_bog_contigs; the read of its record is the one synchronisation.  red: _cover_prologue's."""
+    from . import engine
+    dev, n = g.device, g.num_nodes()
+    with torch.cuda.device(dev):
+        i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
+        src, dst = g.edges()
+        rec = torch.zeros(engine.BOG_RECORD_WORDS, dtype=torch.int64, device=dev)
+        contig_ptr, walk_nodes, walk_edges, wrong = i32(n + 1), i32(n), i32(n), i32(n)
+        bases = torch.empty(n, dtype=torch.int64, device=dev)
+        engine.bog_contigs(src, dst, link_succ, link_pred, scores, y, pl, rl, rec, contig_ptr, walk_nodes, walk_edges, bases, wrong,
+                           min_logit)
+        stats = BogStats.from_record(rec)
+    C = stats.contigs
+    out = BogContigs(contig_ptr[:C + 1], walk_nodes, walk_edges, bases[:C], wrong[:C], stats, pl, rl)
+    if red is not None:
+        out.reduce_stats = ReduceStats.from_record(red)
+    return out
 
 
 def best_overlap_contigs(graph, scores, prefix_length, read_length, y=None, min_logit: float = float("-inf"),
@@ -430,38 +463,15 @@ def best_overlap_contigs(graph, scores, prefix_length, read_length, y=None, min_
     reduce_transitive=True: transitive_support(graph, scores, prefix_length, y, min_logit, fuzz) runs first and its masked_scores
     take the place of the scores in every later call; the result additionally carries `reduce_stats` (ReduceStats).  False (the
     default) launches nothing more and `fuzz` is not read."""
-    from . import engine
-    from .graph import as_assembly_graph
     from .metrics import DecisionStats
-    _reduce_args("best_overlap_contigs", reduce_transitive, fuzz)
-    g = as_assembly_graph(graph)
-    dev = g.device
-    if dev.type != "cuda":
-        raise _lib.GnmError("best_overlap_contigs: the graph must be on a HIP device (no CPU fallback)")
-    n, E = g.num_nodes(), g.num_edges()
-    pl = torch.as_tensor(prefix_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
-    rl = torch.as_tensor(read_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
-    if pl.numel() != E or rl.numel() != n or scores.numel() != E:
-        raise ValueError("scores / prefix_length need one entry per edge, read_length one per node")
+    g, scores, pl, rl, red = _cover_prologue("best_overlap_contigs", graph, scores, prefix_length, read_length, y, min_logit,
+                                             reduce_transitive, fuzz)
+    dev, n = g.device, g.num_nodes()
     with torch.cuda.device(dev):
-        i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
-        best_succ, best_pred = i32(n), i32(n)
-        red = None
-        if reduce_transitive:
-            _, scores, red = _reduce_launch(g, scores, pl, y, min_logit, fuzz)
+        best_succ = torch.empty(n, dtype=torch.int32, device=dev)
+        best_pred = torch.empty(n, dtype=torch.int32, device=dev)
         DecisionStats(dev).add(g, scores, y, best_succ, best_pred)
-        src, dst = g.edges()
-        rec = torch.zeros(engine.BOG_RECORD_WORDS, dtype=torch.int64, device=dev)
-        contig_ptr, walk_nodes, walk_edges, wrong = i32(n + 1), i32(n), i32(n), i32(n)
-        bases = torch.empty(n, dtype=torch.int64, device=dev)
-        engine.bog_contigs(src, dst, best_succ, best_pred, scores, y, pl, rl, rec, contig_ptr, walk_nodes, walk_edges, bases, wrong,
-                           min_logit)
-        stats = BogStats(*[int(v) for v in rec.cpu().tolist()])        # the one synchronisation
-    C = stats.contigs
-    out = BogContigs(contig_ptr[:C + 1], walk_nodes, walk_edges, bases[:C], wrong[:C], stats, pl, rl)
-    if red is not None:
-        out.reduce_stats = _reduce_stats(red)
-    return out
+    return _links_to_contigs(g, best_succ, best_pred, scores, y, pl, rl, min_logit, red)
 
 
 COVER_CHECK_EVERY = 4      # rounds per chunk of greedy_cover_contigs: one read-back of the chunk's round_links (DESIGN.md section 6)
@@ -488,29 +498,18 @@ def greedy_cover_contigs(graph, scores, prefix_length, read_length, y=None, min_
     contig pass see its masked_scores, so no link jumps over a read that a two-step path of shorter prefix reaches; the result
     additionally carries `reduce_stats` (ReduceStats).  False (the default) launches nothing more and `fuzz` is not read."""
     from . import engine
-    from .graph import as_assembly_graph
-    _reduce_args("greedy_cover_contigs", reduce_transitive, fuzz)
-    g = as_assembly_graph(graph)
-    dev = g.device
-    if dev.type != "cuda":
-        raise _lib.GnmError("greedy_cover_contigs: the graph must be on a HIP device (no CPU fallback)")
     if max_rounds is not None and (not isinstance(max_rounds, (int, np.integer)) or max_rounds < 1):
         raise ValueError(f"greedy_cover_contigs: max_rounds={max_rounds!r}: expected None or an integer >= 1")
     if not isinstance(check_every, (int, np.integer)) or check_every < 1:
         raise ValueError(f"greedy_cover_contigs: check_every={check_every!r}: expected an integer >= 1")
-    n, E = g.num_nodes(), g.num_edges()
-    pl = torch.as_tensor(prefix_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
-    rl = torch.as_tensor(read_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
-    if pl.numel() != E or rl.numel() != n or scores.numel() != E:
-        raise ValueError("scores / prefix_length need one entry per edge, read_length one per node")
+    g, scores, pl, rl, red = _cover_prologue("greedy_cover_contigs", graph, scores, prefix_length, read_length, y, min_logit,
+                                             reduce_transitive, fuzz)
+    dev, n = g.device, g.num_nodes()
     limit = n + 1 if max_rounds is None else int(max_rounds)
     with torch.cuda.device(dev):
-        i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
         idx = g.index(dev)
-        red = None
-        if reduce_transitive:
-            _, scores, red = _reduce_launch(g, scores, pl, y, min_logit, fuzz)
-        link_succ, link_pred = i32(n), i32(n)
+        link_succ = torch.empty(n, dtype=torch.int32, device=dev)
+        link_pred = torch.empty(n, dtype=torch.int32, device=dev)
         ws = torch.empty(engine.cover_workspace_bytes(n), dtype=torch.uint8, device=dev)
         round_links, converged = [], False
         while not converged and len(round_links) < limit:
@@ -521,19 +520,9 @@ def greedy_cover_contigs(graph, scores, prefix_length, read_length, y=None, min_
                 if added == 0:
                     converged = True
                     break
-        src, dst = g.edges()
-        rec = torch.zeros(engine.BOG_RECORD_WORDS, dtype=torch.int64, device=dev)
-        contig_ptr, walk_nodes, walk_edges, wrong = i32(n + 1), i32(n), i32(n), i32(n)
-        bases = torch.empty(n, dtype=torch.int64, device=dev)
-        engine.bog_contigs(src, dst, link_succ, link_pred, scores, y, pl, rl, rec, contig_ptr, walk_nodes, walk_edges, bases, wrong,
-                           min_logit)
-        stats = BogStats(*[int(v) for v in rec.cpu().tolist()])
-    C = stats.contigs
-    out = BogContigs(contig_ptr[:C + 1], walk_nodes, walk_edges, bases[:C], wrong[:C], stats, pl, rl)
+    out = _links_to_contigs(g, link_succ, link_pred, scores, y, pl, rl, min_logit, red)
     out.rounds, out.round_links, out.converged = len(round_links), round_links, converged
     out.link_succ, out.link_pred = link_succ, link_pred
-    if red is not None:
-        out.reduce_stats = _reduce_stats(red)
     return out
 
 
@@ -630,7 +619,7 @@ def quick_evaluation(lengths, ref_length):
 
 
 @dataclass
-class SeqStats:
+class SeqStats(RecordStats):
     """A gnm_seq_record (include/gnm.h): contigs, pieces (walk positions), bases, clamped (pieces whose prefix_length was below 0
     or above the read's length), empty (valid pieces of 0 bases), reverse (valid pieces of odd nodes), invalid (positions whose
     node, read or edge is out of range: 0 bases, nothing read), calls."""
@@ -642,9 +631,6 @@ class SeqStats:
     reverse: int = 0
     invalid: int = 0
     calls: int = 0
-
-    def words(self) -> List[int]:
-        return [self.contigs, self.pieces, self.bases, self.clamped, self.empty, self.reverse, self.invalid, self.calls]
 
 
 class ContigSequences:
@@ -725,6 +711,31 @@ def walk_edge_ids(graph: DecodeGraph, walks):
     return contig_ptr, walk_nodes, edges
 
 
+def _as_decode_graph(graph) -> DecodeGraph:
+    if isinstance(graph, DecodeGraph):
+        return graph
+    src, dst = graph.edges()
+    return DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), graph.num_nodes())
+
+
+def _default_prefix_length(walks, graph, prefix_length):
+    """prefix_length as given; else graph.edata['prefix_length']; else the one a BogContigs was built with; else None."""
+    if prefix_length is None:
+        prefix_length = getattr(graph, "edata", {}).get("prefix_length")
+    if prefix_length is None and isinstance(walks, BogContigs):
+        prefix_length = walks.prefix_length
+    return prefix_length
+
+
+def _walks_csr(walks, graph):
+    """(contig_ptr [C+1], walk_nodes [P], walk_edges [P]) of `walks` as int32 tensors: the device CSR of a BogContigs as it is, or
+    host tensors for lists of node ids, whose edge ids are looked up on the host (walk_edge_ids) over `graph`.  The caller moves
+    what it uses to its device and integer width."""
+    if isinstance(walks, BogContigs):
+        return walks.contig_ptr, walks.walk_nodes, walks.walk_edges
+    return tuple(torch.from_numpy(a) for a in walk_edge_ids(_as_decode_graph(graph), walks))
+
+
 def contig_sequences(walks, graph, reads, prefix_length=None, read_length=None) -> ContigSequences:
     """The sequences of `walks` on the device: evaluate.walk_to_sequence (evaluate.py:36-47) over a packed ReadStore.
 
@@ -748,24 +759,15 @@ def contig_sequences(walks, graph, reads, prefix_length=None, read_length=None) 
         raise _lib.GnmError("contig_sequences: the ReadStore must be on a HIP device (no CPU fallback; ReadStore.sequence is the "
                             "host route)")
     n = int(graph.n if isinstance(graph, DecodeGraph) else graph.num_nodes())
+    prefix_length = _default_prefix_length(walks, graph, prefix_length)
     if prefix_length is None:
-        prefix_length = getattr(graph, "edata", {}).get("prefix_length")
-        if prefix_length is None and isinstance(walks, BogContigs):
-            prefix_length = walks.prefix_length
-        if prefix_length is None:
-            raise ValueError("contig_sequences: no prefix_length given and the graph has no edata['prefix_length']")
+        raise ValueError("contig_sequences: no prefix_length given and the graph has no edata['prefix_length']")
     pl = torch.as_tensor(prefix_length).reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
-    if isinstance(walks, BogContigs):
-        to32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()  # noqa: E731
-        contig_ptr, walk_nodes, walk_edges = to32(walks.contig_ptr), to32(walks.walk_nodes), to32(walks.walk_edges)
-    else:
-        dg = graph
-        if not isinstance(dg, DecodeGraph):
-            src, dst = graph.edges()
-            dg = DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), n)
-        if pl.numel() != dg.src.size:
+    if not isinstance(walks, BogContigs):
+        graph = _as_decode_graph(graph)
+        if pl.numel() != graph.src.size:
             raise ValueError("contig_sequences: prefix_length needs one entry per edge")
-        contig_ptr, walk_nodes, walk_edges = (torch.from_numpy(a).to(dev) for a in walk_edge_ids(dg, walks))
+    contig_ptr, walk_nodes, walk_edges = (t.to(device=dev, dtype=torch.int32).contiguous() for t in _walks_csr(walks, graph))
     with torch.cuda.device(dev):
         if read_length is not None:
             rl = torch.as_tensor(read_length).reshape(-1).to(device=dev, dtype=torch.int64)
@@ -783,7 +785,7 @@ def contig_sequences(walks, graph, reads, prefix_length=None, read_length=None) 
         piece_len, piece_off, base_ptr = i64(P), i64(P + 1), i64(C + 1)
         engine.seq_layout(contig_ptr, walk_nodes, walk_edges, pl, n, reads.base_off, reads.length, reads.packed, rec, piece_len,
                           piece_off, base_ptr)
-        stats = SeqStats(*[int(v) for v in rec.cpu().tolist()])        # the one synchronisation
+        stats = SeqStats.from_record(rec)                              # the one synchronisation
         if stats.invalid:
             err = _lib.GnmError(f"contig_sequences: {stats.invalid} of {stats.pieces} walk positions name a node, read or edge "
                                 f"that is out of range (graph of {n} nodes and {pl.numel()} edges, store of {len(reads)} reads)")
@@ -813,19 +815,10 @@ def junction_identity(contigs, graph, reads, max_errors: int = 255, prefix_lengt
     the walk edges of `contigs` -- a BogContigs, or lists of node ids whose edge ids are looked up on the host (walk_edge_ids).
     graph: the AssemblyGraph on a HIP device; reads: a ReadStore on that device.  Torch indexing only, no kernel of its own."""
     from . import features
-    if prefix_length is None:
-        prefix_length = getattr(graph, "edata", {}).get("prefix_length")
-        if prefix_length is None and isinstance(contigs, BogContigs):
-            prefix_length = contigs.prefix_length
-    f = features.overlap_features(graph, reads, prefix_length, max_errors)
+    f = features.overlap_features(graph, reads, _default_prefix_length(contigs, graph, prefix_length), max_errors)
     dev = graph.device
-    if isinstance(contigs, BogContigs):
-        contig_ptr, walk_edges = contigs.contig_ptr.to(dev).long(), contigs.walk_edges.to(dev).long()
-    else:
-        src, dst = graph.edges()
-        dg = DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), graph.num_nodes())
-        ptr, _, edges = walk_edge_ids(dg, contigs)
-        contig_ptr, walk_edges = torch.from_numpy(ptr).to(dev).long(), torch.from_numpy(edges).to(dev).long()
+    contig_ptr, _, walk_edges = _walks_csr(contigs, graph)
+    contig_ptr, walk_edges = contig_ptr.to(dev).long(), walk_edges.to(dev).long()
     C, P = int(contig_ptr.numel()) - 1, int(walk_edges.numel())
     contig = torch.repeat_interleave(torch.arange(C, device=dev), contig_ptr[1:] - contig_ptr[:-1], output_size=P)
     first = torch.zeros(P, dtype=torch.bool, device=dev)
@@ -875,22 +868,14 @@ def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int
         extra = dict(reduce_transitive=True, fuzz=fuzz) if reduce_transitive else {}
         walks = resolve_strands(cover(graph, scores, prefix_length, read_length, getattr(graph, "edata", {}).get("y"), **extra),
                                 len_threshold).walks
-        return _with_sequences((scores, walks, report) if decision_report else (scores, walks), walks, graph, reads, prefix_length,
-                               graph if junction_report else None)
-    src, dst = graph.edges()
-    dg = DecodeGraph(src.cpu().numpy(), dst.cpu().numpy(), graph.num_nodes())
-    if device_sampling:
-        walks = get_contigs_device(dg, scores, prefix_length, read_length, nb_paths, len_threshold)
+        walk_graph = graph
     else:
-        walks = get_contigs(dg, scores, prefix_length, read_length, nb_paths, len_threshold)
-    return _with_sequences((scores, walks, report) if decision_report else (scores, walks), walks, dg, reads, prefix_length,
-                           graph if junction_report else None)
-
-
-def _with_sequences(result, walks, graph, reads, prefix_length, junction_graph=None):
-    if reads is None:
-        return result
-    result = result + (contig_sequences(walks, graph, reads, prefix_length),)
-    if junction_graph is not None:
-        result = result + (junction_identity(walks, junction_graph, reads, prefix_length=prefix_length),)
+        walk_graph = _as_decode_graph(graph)                           # built once: the walks and contig_sequences share it
+        sampled = get_contigs_device if device_sampling else get_contigs
+        walks = sampled(walk_graph, scores, prefix_length, read_length, nb_paths, len_threshold)
+    result = (scores, walks, report) if decision_report else (scores, walks)
+    if reads is not None:
+        result += (contig_sequences(walks, walk_graph, reads, prefix_length),)
+        if junction_report:
+            result += (junction_identity(walks, graph, reads, prefix_length=prefix_length),)
     return result

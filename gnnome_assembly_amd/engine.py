@@ -16,7 +16,7 @@ import functools
 import operator
 import os
 import threading
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields
 from typing import Dict, List, Optional
 
 import torch
@@ -226,6 +226,52 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != torch.float32:
         raise _lib.GnmError(f"expected float32, got {t.dtype}")
     return t if t.is_contiguous() else t.contiguous()
+
+
+# The argument rules of the wrappers from bce_with_logits down: each of these raises or returns, and a wrapper states what it
+# requires of every argument by calling them before its first launch.
+def _fits(t: torch.Tensor, dt, m: int) -> bool:
+    return t.dtype == dt and t.numel() == m and t.is_contiguous()
+
+
+def _chk_args(fn: str, *rows, optional=()):
+    """Every row (name, tensor, dtype, elements) of wrapper `fn` is a contiguous tensor of that dtype and size; the names in
+    `optional` may be None."""
+    for name, t, dt, m in rows:
+        if not (t is None and name in optional) and not _fits(t, dt, m):
+            raise ValueError(f"{fn}: {name} must be a contiguous {str(dt).replace('torch.', '')} [{m}] tensor")
+
+
+def _chk_record(fn: str, rec, words: int, name: str = "record", owner: str = ""):
+    """`rec` holds a device record of `words` int64 words; `owner`: the object whose buffer it usually is, for the message."""
+    if not _fits(rec, torch.int64, words):
+        raise ValueError(f"{fn}: {name} must be a contiguous int64 [{words}] tensor{owner}")
+
+
+def _chk_epoch_acc(scores, epoch_acc):
+    if epoch_acc is not None:
+        _chk_dev(scores, epoch_acc)
+        if not _fits(epoch_acc, torch.int64, 6):
+            raise ValueError("epoch_acc: a contiguous int64 [6] tensor (train.EpochStats.buf)")
+
+
+def _chk_index(fn: str, idx, keys, n: int):
+    """The arrays `keys` of a graph index, and its node permutation [n] when it has one, are contiguous int32 tensors."""
+    nperm = idx.get("nperm")
+    if any(idx[k].dtype != torch.int32 or not idx[k].is_contiguous() for k in keys) or \
+            (nperm is not None and not _fits(nperm, torch.int32, n)):
+        raise ValueError(f"{fn}: the index arrays must be contiguous int32 tensors (graph.index())")
+
+
+def _scores_labels(fn: str, scores, y):
+    """(scores, labels or None, E) as flat contiguous fp32 tensors of E entries each."""
+    x = _f32c(scores.detach().reshape(-1).float())     # .float(): a half or bf16 tensor is compared as its fp32 copy (exact widening)
+    E = x.numel()
+    if y is not None:
+        y = _f32c(y.reshape(-1).float())
+        if y.numel() != E:
+            raise ValueError(f"{fn}: {E} scores, {y.numel()} labels")
+    return x, y, E
 
 
 class _Scratch:
@@ -2174,10 +2220,7 @@ def bce_with_logits_counts(scores, y, pos_weight: float, need_grad: bool = True,
     loss = torch.empty(1, dtype=torch.float32, device=x.device)
     gs = torch.empty(E, 1, dtype=torch.float32, device=x.device) if need_grad else None
     counts = torch.empty(4, dtype=torch.int64, device=x.device)
-    if epoch_acc is not None:
-        _chk_dev(scores, epoch_acc)
-        if epoch_acc.dtype != torch.int64 or epoch_acc.numel() != 6 or not epoch_acc.is_contiguous():
-            raise ValueError("epoch_acc: a contiguous int64 [6] tensor (train.EpochStats.buf)")
+    _chk_epoch_acc(scores, epoch_acc)
     _call("gnm_bce_stats_fwd_bwd", E, _ptr(x), _ptr(y), float(pos_weight), _ptr(loss), _ptr(gs), _ptr(counts), _ptr(epoch_acc),
           _ptr(sc.partials), sc.partials.numel() * 8, _stream())
     return loss, gs, counts
@@ -2202,10 +2245,7 @@ def sym_bce(org, rev, y, pos_weight: float, alpha: float, need_grad: bool = True
     go = torch.empty(E, dtype=torch.float32, device=dev) if need_grad else None
     gr = torch.empty(E, dtype=torch.float32, device=dev) if need_grad else None
     counts = torch.empty(4, dtype=torch.int64, device=dev) if want_counts else None
-    if epoch_acc is not None:
-        _chk_dev(org, epoch_acc)
-        if epoch_acc.dtype != torch.int64 or epoch_acc.numel() != 6 or not epoch_acc.is_contiguous():
-            raise ValueError("epoch_acc: a contiguous int64 [6] tensor (train.EpochStats.buf)")
+    _chk_epoch_acc(org, epoch_acc)
     need = lib.gnm_sym_bce_workspace_bytes()
     ws = scratch(dev).ws(need)
     _call("gnm_sym_bce_fwd_bwd", E, _ptr(o), _ptr(r), _ptr(y), float(pos_weight), float(alpha), _ptr(loss), _ptr(parts), _ptr(go),
@@ -2219,8 +2259,7 @@ def mirror_add(g, scratch_grad, pi):
     mirrored parameters flat[pi], folded into the flat gradient buffer.  pi: int32 permutation (models.mirror_index)."""
     _chk_dev(g, scratch_grad, pi)
     n = g.numel()
-    if not (g.dtype == scratch_grad.dtype == torch.float32 and g.is_contiguous() and scratch_grad.is_contiguous()
-            and scratch_grad.numel() == n and pi.dtype == torch.int32 and pi.is_contiguous() and pi.numel() == n):
+    if not (_fits(g, torch.float32, n) and _fits(scratch_grad, torch.float32, n) and _fits(pi, torch.int32, n)):
         raise ValueError(f"mirror_add: contiguous float32 buffers and an int32 permutation of {n} elements each")
     _call("gnm_mirror_add", n, _ptr(g), _ptr(scratch_grad), _ptr(pi), _stream())
     return g
@@ -2233,8 +2272,8 @@ def mirror_gather(src, pi, out=None):
     n = src.numel()
     if out is None:
         out = torch.empty_like(src)
-    if not (src.dtype == out.dtype == torch.float32 and src.is_contiguous() and out.is_contiguous() and out.numel() == n
-            and pi.dtype == torch.int32 and pi.is_contiguous() and pi.numel() == n and out.data_ptr() != src.data_ptr()):
+    if not (_fits(src, torch.float32, n) and _fits(out, torch.float32, n) and _fits(pi, torch.int32, n)
+            and out.data_ptr() != src.data_ptr()):
         raise ValueError(f"mirror_gather: contiguous float32 buffers (out is not src) and an int32 permutation of {n} elements each")
     _call("gnm_mirror_gather", n, _ptr(out), _ptr(src), _ptr(pi), _stream())
     return out
@@ -2250,13 +2289,8 @@ def rank_hist(scores, y, record):
     [RANK_RECORD_WORDS] device tensor holding a gnm_rank_record (train.RankingStats.buf), which the caller zeroes once."""
     lib = _lib.load()
     _chk_dev(scores, y, record)
-    x = _f32c(scores.reshape(-1).float())          # .float(): a half or bf16 tensor is counted as its fp32 copy (exact widening)
-    y = _f32c(y.reshape(-1).float())
-    E = x.numel()
-    if y.numel() != E:
-        raise ValueError(f"rank_hist: {E} scores, {y.numel()} labels")
-    if record.dtype != torch.int64 or record.numel() != RANK_RECORD_WORDS or not record.is_contiguous():
-        raise ValueError(f"rank_hist: record must be a contiguous int64 [{RANK_RECORD_WORDS}] tensor (train.RankingStats.buf)")
+    x, y, E = _scores_labels("rank_hist", scores, y)
+    _chk_record("rank_hist", record, RANK_RECORD_WORDS, owner=" (train.RankingStats.buf)")
     need = lib.gnm_rank_hist_workspace_bytes(E)
     ws = scratch(x.device).ws(need) if need else None
     _call("gnm_rank_hist", E, _ptr(x), _ptr(y), _ptr(record), _ptr(ws), need, _stream())
@@ -2264,6 +2298,7 @@ def rank_hist(scores, y, record):
 
 DECISION_COUNTERS = ("dead", "forced", "forced_ok", "branch", "branch_solvable", "branch_ok", "branch_nan")
 DECISION_RECORD_WORDS = 2 * len(DECISION_COUNTERS) + 1   # int64 dir[2][7] (successors, predecessors), then calls (include/gnm.h)
+_DECISION_INDEX_KEYS = ("perm", "isrc", "idst", "in_ptr", "out_ptr", "out_pos", "out_dst")
 
 
 @on_device_of(lambda idx, scores, y, record, *a, **k: record)
@@ -2276,25 +2311,30 @@ def decision_stats(idx, scores, y, record, best_succ=None, best_pred=None):
     receive the chosen edge ids in the CALLER's node numbering (-1: no candidate)."""
     n = int(idx["in_ptr"].numel()) - 1
     nperm = idx.get("nperm")
-    _chk_dev(scores, y, record, best_succ, best_pred, nperm, *[idx[k] for k in ("perm", "isrc", "idst", "in_ptr", "out_ptr", "out_pos", "out_dst")])
-    x = _f32c(scores.detach().reshape(-1).float())     # .float(): a half or bf16 tensor is compared as its fp32 copy (exact widening)
-    E = x.numel()
-    if E != idx["perm"].numel():
-        raise ValueError(f"decision_stats: {E} scores for an index of {idx['perm'].numel()} edges")
-    if y is not None:
-        y = _f32c(y.reshape(-1).float())
-        if y.numel() != E:
-            raise ValueError(f"decision_stats: {E} scores, {y.numel()} labels")
-    if record.dtype != torch.int64 or record.numel() != DECISION_RECORD_WORDS or not record.is_contiguous():
-        raise ValueError(f"decision_stats: record must be a contiguous int64 [{DECISION_RECORD_WORDS}] tensor (train.DecisionStats.buf)")
-    for name, t in (("best_succ", best_succ), ("best_pred", best_pred)):
-        if t is not None and (t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous()):
-            raise ValueError(f"decision_stats: {name} must be a contiguous int32 [{n}] tensor")
-    if any(idx[k].dtype != torch.int32 or not idx[k].is_contiguous() for k in ("perm", "isrc", "idst", "in_ptr", "out_ptr", "out_pos", "out_dst")):
-        raise ValueError("decision_stats: the index arrays must be contiguous int32 tensors (graph.index())")
+    _chk_dev(scores, y, record, best_succ, best_pred, nperm, *[idx[k] for k in _DECISION_INDEX_KEYS])
+    if scores.numel() != idx["perm"].numel():
+        raise ValueError(f"decision_stats: {scores.numel()} scores for an index of {idx['perm'].numel()} edges")
+    x, y, E = _scores_labels("decision_stats", scores, y)
+    _chk_record("decision_stats", record, DECISION_RECORD_WORDS, owner=" (train.DecisionStats.buf)")
+    _chk_args("decision_stats", ("best_succ", best_succ, torch.int32, n), ("best_pred", best_pred, torch.int32, n),
+              optional=("best_succ", "best_pred"))
+    _chk_index("decision_stats", idx, _DECISION_INDEX_KEYS, n)
     _call("gnm_decision_stats", n, E, _ptr(idx["perm"]), _ptr(idx["isrc"]), _ptr(idx["idst"]), _ptr(idx["in_ptr"]), _ptr(idx["out_ptr"]),
           _ptr(idx["out_pos"]), _ptr(idx["out_dst"]), _ptr(nperm), _ptr(x), _ptr(y), _ptr(record), _ptr(best_succ), _ptr(best_pred),
           _stream())
+
+
+class RecordStats:
+    """Base of the dataclasses that hold one device record of counters on the host (decode.BogStats, ReduceStats, SeqStats,
+    features.AlignStats): the fields are the record's int64 words in order, the names of the record's *_COUNTERS tuple below."""
+
+    @classmethod
+    def from_record(cls, rec: torch.Tensor):
+        """The record tensor as a stats object: one device-to-host copy, which synchronises."""
+        return cls(*[int(v) for v in rec.cpu().tolist()])
+
+    def words(self) -> List[int]:
+        return [getattr(self, f.name) for f in fields(self)]
 
 
 BOG_COUNTERS = ("contigs", "links", "cycles_cut", "dropped", "wrong_links", "multi_nodes", "multi_contigs", "calls")
@@ -2315,22 +2355,15 @@ def bog_contigs(src, dst, best_succ, best_pred, scores, y, prefix_length, read_l
     _chk_dev(src, dst, best_succ, best_pred, scores, y, prefix_length, read_length, record, contig_ptr, walk_nodes, walk_edges,
              contig_bases, contig_wrong)
     n, E = int(best_succ.numel()), int(src.numel())
-    x = _f32c(scores.detach().reshape(-1).float())     # .float(): a half or bf16 tensor is compared as its fp32 copy (exact widening)
-    if x.numel() != E or dst.numel() != E:
-        raise ValueError(f"bog_contigs: {E} src entries, {dst.numel()} dst entries, {x.numel()} scores")
-    if y is not None:
-        y = _f32c(y.reshape(-1).float())
-        if y.numel() != E:
-            raise ValueError(f"bog_contigs: {E} scores, {y.numel()} labels")
-    if record.dtype != torch.int64 or record.numel() != BOG_RECORD_WORDS or not record.is_contiguous():
-        raise ValueError(f"bog_contigs: record must be a contiguous int64 [{BOG_RECORD_WORDS}] tensor")
-    for name, t, dt, m in (("src", src, torch.int32, E), ("dst", dst, torch.int32, E), ("best_succ", best_succ, torch.int32, n),
-                           ("best_pred", best_pred, torch.int32, n), ("prefix_length", prefix_length, torch.int64, E),
-                           ("read_length", read_length, torch.int64, n), ("contig_ptr", contig_ptr, torch.int32, n + 1),
-                           ("walk_nodes", walk_nodes, torch.int32, n), ("walk_edges", walk_edges, torch.int32, n),
-                           ("contig_bases", contig_bases, torch.int64, n), ("contig_wrong", contig_wrong, torch.int32, n)):
-        if t.dtype != dt or t.numel() != m or not t.is_contiguous():
-            raise ValueError(f"bog_contigs: {name} must be a contiguous {str(dt).replace('torch.', '')} [{m}] tensor")
+    if scores.numel() != E or dst.numel() != E:
+        raise ValueError(f"bog_contigs: {E} src entries, {dst.numel()} dst entries, {scores.numel()} scores")
+    x, y, _ = _scores_labels("bog_contigs", scores, y)
+    _chk_record("bog_contigs", record, BOG_RECORD_WORDS)
+    _chk_args("bog_contigs", ("src", src, torch.int32, E), ("dst", dst, torch.int32, E), ("best_succ", best_succ, torch.int32, n),
+              ("best_pred", best_pred, torch.int32, n), ("prefix_length", prefix_length, torch.int64, E),
+              ("read_length", read_length, torch.int64, n), ("contig_ptr", contig_ptr, torch.int32, n + 1),
+              ("walk_nodes", walk_nodes, torch.int32, n), ("walk_edges", walk_edges, torch.int32, n),
+              ("contig_bases", contig_bases, torch.int64, n), ("contig_wrong", contig_wrong, torch.int32, n))
     need = lib.gnm_bog_workspace_bytes(n)
     ws = scratch(record.device).ws(need) if need else None
     _call("gnm_bog_contigs", n, E, _ptr(src), _ptr(dst), _ptr(best_succ), _ptr(best_pred), _ptr(x), _ptr(y), _ptr(prefix_length),
@@ -2355,20 +2388,15 @@ def cover_rounds(idx, scores, round_links, link_succ, link_pred, ws, first_round
     n = int(idx["in_ptr"].numel()) - 1
     nperm = idx.get("nperm")
     _chk_dev(scores, round_links, link_succ, link_pred, ws, nperm, *[idx[k] for k in _COVER_INDEX_KEYS])
-    x = _f32c(scores.detach().reshape(-1).float())     # .float(): a half or bf16 tensor is compared as its fp32 copy (exact widening)
-    E = x.numel()
-    if E != idx["perm"].numel():
-        raise ValueError(f"cover_rounds: {E} scores for an index of {idx['perm'].numel()} edges")
+    if scores.numel() != idx["perm"].numel():
+        raise ValueError(f"cover_rounds: {scores.numel()} scores for an index of {idx['perm'].numel()} edges")
+    x, _, E = _scores_labels("cover_rounds", scores, None)
     if round_links.dtype != torch.int64 or round_links.dim() != 1 or not round_links.is_contiguous():
         raise ValueError("cover_rounds: round_links must be a contiguous int64 [rounds] tensor")
     if int(first_round) < 0:
         raise ValueError(f"cover_rounds: first_round = {first_round}: expected >= 0")
-    for name, t in (("link_succ", link_succ), ("link_pred", link_pred)):
-        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
-            raise ValueError(f"cover_rounds: {name} must be a contiguous int32 [{n}] tensor")
-    if any(idx[k].dtype != torch.int32 or not idx[k].is_contiguous() for k in _COVER_INDEX_KEYS) or \
-            (nperm is not None and (nperm.dtype != torch.int32 or nperm.numel() != n or not nperm.is_contiguous())):
-        raise ValueError("cover_rounds: the index arrays must be contiguous int32 tensors (graph.index())")
+    _chk_args("cover_rounds", ("link_succ", link_succ, torch.int32, n), ("link_pred", link_pred, torch.int32, n))
+    _chk_index("cover_rounds", idx, _COVER_INDEX_KEYS, n)
     need = lib.gnm_cover_workspace_bytes(n)
     if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
         raise ValueError(f"cover_rounds: ws must be a contiguous uint8 tensor of at least {need} bytes (cover_workspace_bytes)")
@@ -2411,28 +2439,16 @@ def transitive_support(idx, scores, prefix_length, y, min_logit, fuzz, support, 
     n = int(idx["in_ptr"].numel()) - 1
     nperm = idx.get("nperm")
     _chk_dev(scores, prefix_length, y, support, masked_scores, rec, nperm, *[idx[k] for k in _COVER_INDEX_KEYS])
-    x = _f32c(scores.detach().reshape(-1).float())     # .float(): a half or bf16 tensor is compared as its fp32 copy (exact widening)
-    E = x.numel()
-    if E != idx["perm"].numel():
-        raise ValueError(f"transitive_support: {E} scores for an index of {idx['perm'].numel()} edges")
-    if y is not None:
-        y = _f32c(y.reshape(-1).float())
-        if y.numel() != E:
-            raise ValueError(f"transitive_support: {E} scores, {y.numel()} labels")
+    if scores.numel() != idx["perm"].numel():
+        raise ValueError(f"transitive_support: {scores.numel()} scores for an index of {idx['perm'].numel()} edges")
+    x, y, E = _scores_labels("transitive_support", scores, y)
     fz = reduce_fuzz_word(fuzz, "transitive_support: fuzz")
-    if rec.dtype != torch.int64 or rec.numel() != REDUCE_RECORD_WORDS or not rec.is_contiguous():
-        raise ValueError(f"transitive_support: rec must be a contiguous int64 [{REDUCE_RECORD_WORDS}] tensor")
-    for name, t, dt in (("prefix_length", prefix_length, torch.int64), ("support", support, torch.int32),
-                        ("masked_scores", masked_scores, torch.float32)):
-        if t is None and name == "masked_scores":
-            continue
-        if t.dtype != dt or t.numel() != E or not t.is_contiguous():
-            raise ValueError(f"transitive_support: {name} must be a contiguous {str(dt).replace('torch.', '')} [{E}] tensor")
+    _chk_record("transitive_support", rec, REDUCE_RECORD_WORDS, "rec")
+    _chk_args("transitive_support", ("prefix_length", prefix_length, torch.int64, E), ("support", support, torch.int32, E),
+              ("masked_scores", masked_scores, torch.float32, E), optional=("masked_scores",))
     if masked_scores is not None and E and masked_scores.data_ptr() == x.data_ptr():
         raise ValueError("transitive_support: masked_scores must not be the scores tensor itself (a witness reads the scores)")
-    if any(idx[k].dtype != torch.int32 or not idx[k].is_contiguous() for k in _COVER_INDEX_KEYS) or \
-            (nperm is not None and (nperm.dtype != torch.int32 or nperm.numel() != n or not nperm.is_contiguous())):
-        raise ValueError("transitive_support: the index arrays must be contiguous int32 tensors (graph.index())")
+    _chk_index("transitive_support", idx, _COVER_INDEX_KEYS, n)
     _call("gnm_transitive_support", n, E, _ptr(idx["perm"]), _ptr(idx["isrc"]), _ptr(idx["in_ptr"]), _ptr(idx["out_ptr"]),
           _ptr(idx["out_pos"]), _ptr(idx["out_dst"]), _ptr(nperm), _ptr(x), _ptr(prefix_length), _ptr(y), float(min_logit), int(fz),
           _ptr(support), _ptr(masked_scores), _ptr(rec), _stream())
@@ -2444,12 +2460,10 @@ SEQ_CHUNK_BASES = 4096                     # GNM_SEQ_CHUNK_BASES: output bases a
 SEQ_LETTERS = "=ACMGRSVTWYHKDBN"           # the letter of every 4-bit code
 
 
-def _seq_store_args(name, n, base_off, length, packed):
+def _seq_store_args(name, base_off, length, packed):
     R = int(base_off.numel())
-    for what, t, dt, m in (("base_off", base_off, torch.int64, R), ("length", length, torch.int64, R),
-                           ("packed", packed, torch.uint8, packed.numel())):
-        if t.dtype != dt or t.numel() != m or not t.is_contiguous():
-            raise ValueError(f"{name}: {what} must be a contiguous {str(dt).replace('torch.', '')} [{m}] tensor")
+    _chk_args(name, ("base_off", base_off, torch.int64, R), ("length", length, torch.int64, R),
+              ("packed", packed, torch.uint8, packed.numel()))
     if packed.numel() % 16:
         raise ValueError(f"{name}: packed holds {packed.numel()} bytes, not whole 16-byte groups")
     return R
@@ -2468,15 +2482,12 @@ def seq_layout(contig_ptr, walk_nodes, walk_edges, prefix_length, n: int, base_o
     C, P, E = int(contig_ptr.numel()) - 1, int(walk_nodes.numel()), int(prefix_length.numel())
     if C < 0:
         raise ValueError("seq_layout: contig_ptr needs at least one entry")
-    R = _seq_store_args("seq_layout", n, base_off, length, packed)
-    if record.dtype != torch.int64 or record.numel() != SEQ_RECORD_WORDS or not record.is_contiguous():
-        raise ValueError(f"seq_layout: record must be a contiguous int64 [{SEQ_RECORD_WORDS}] tensor")
-    for name, t, dt, m in (("contig_ptr", contig_ptr, torch.int32, C + 1), ("walk_nodes", walk_nodes, torch.int32, P),
-                           ("walk_edges", walk_edges, torch.int32, P), ("prefix_length", prefix_length, torch.int64, E),
-                           ("piece_len", piece_len, torch.int64, P), ("piece_off", piece_off, torch.int64, P + 1),
-                           ("contig_base_ptr", contig_base_ptr, torch.int64, C + 1)):
-        if t.dtype != dt or t.numel() != m or not t.is_contiguous():
-            raise ValueError(f"seq_layout: {name} must be a contiguous {str(dt).replace('torch.', '')} [{m}] tensor")
+    R = _seq_store_args("seq_layout", base_off, length, packed)
+    _chk_record("seq_layout", record, SEQ_RECORD_WORDS)
+    _chk_args("seq_layout", ("contig_ptr", contig_ptr, torch.int32, C + 1), ("walk_nodes", walk_nodes, torch.int32, P),
+              ("walk_edges", walk_edges, torch.int32, P), ("prefix_length", prefix_length, torch.int64, E),
+              ("piece_len", piece_len, torch.int64, P), ("piece_off", piece_off, torch.int64, P + 1),
+              ("contig_base_ptr", contig_base_ptr, torch.int64, C + 1))
     need = lib.gnm_seq_workspace_bytes(P)
     ws = scratch(record.device).ws(need) if need else None
     _call("gnm_seq_layout", C, P, E, int(n), R, _ptr(contig_ptr), _ptr(walk_nodes), _ptr(walk_edges), _ptr(prefix_length),
@@ -2492,11 +2503,9 @@ def seq_emit(walk_nodes, piece_off, n: int, base_off, length, packed, total: int
     _lib.load()
     _chk_dev(walk_nodes, piece_off, base_off, length, packed, out)
     P = int(walk_nodes.numel())
-    R = _seq_store_args("seq_emit", n, base_off, length, packed)
-    for name, t, dt, m in (("walk_nodes", walk_nodes, torch.int32, P), ("piece_off", piece_off, torch.int64, P + 1),
-                           ("out", out, torch.uint8, out.numel())):
-        if t.dtype != dt or t.numel() != m or not t.is_contiguous():
-            raise ValueError(f"seq_emit: {name} must be a contiguous {str(dt).replace('torch.', '')} [{m}] tensor")
+    R = _seq_store_args("seq_emit", base_off, length, packed)
+    _chk_args("seq_emit", ("walk_nodes", walk_nodes, torch.int32, P), ("piece_off", piece_off, torch.int64, P + 1),
+              ("out", out, torch.uint8, out.numel()))
     _call("gnm_seq_emit", P, int(n), R, _ptr(walk_nodes), _ptr(piece_off), _ptr(base_off), _ptr(length), _ptr(packed),
           int(packed.numel()), int(total), _ptr(out), int(out.numel()), _stream())
 
@@ -2506,18 +2515,15 @@ ALIGN_RECORD_WORDS = len(ALIGN_COUNTERS)   # the int64 words of a gnm_align_reco
 ALIGN_MAX_ERRORS = 255                     # the widest band: 2 K + 1 <= 512 diagonals
 
 
-def _align_args(name, src, dst, prefix_length, n, base_off, length, packed, max_errors, dist, overlap_length, similarity, rec):
+def _align_args(name, src, dst, prefix_length, base_off, length, packed, max_errors, dist, overlap_length, similarity, rec):
     E = int(src.numel())
-    R = _seq_store_args(name, n, base_off, length, packed)
+    R = _seq_store_args(name, base_off, length, packed)
     if isinstance(max_errors, bool) or not hasattr(max_errors, "__index__") or not 0 <= operator.index(max_errors) <= ALIGN_MAX_ERRORS:
         raise ValueError(f"{name}: max_errors={max_errors!r}: expected an integer in [0, {ALIGN_MAX_ERRORS}]")
-    if rec.dtype != torch.int64 or rec.numel() != ALIGN_RECORD_WORDS or not rec.is_contiguous():
-        raise ValueError(f"{name}: rec must be a contiguous int64 [{ALIGN_RECORD_WORDS}] tensor")
-    for what, t, dt in (("src", src, torch.int32), ("dst", dst, torch.int32), ("prefix_length", prefix_length, torch.int64),
-                        ("dist", dist, torch.int32), ("overlap_length", overlap_length, torch.int64),
-                        ("similarity", similarity, torch.float32)):
-        if t.dtype != dt or t.numel() != E or not t.is_contiguous():
-            raise ValueError(f"{name}: {what} must be a contiguous {str(dt).replace('torch.', '')} [{E}] tensor")
+    _chk_record(name, rec, ALIGN_RECORD_WORDS, "rec")
+    _chk_args(name, ("src", src, torch.int32, E), ("dst", dst, torch.int32, E), ("prefix_length", prefix_length, torch.int64, E),
+              ("dist", dist, torch.int32, E), ("overlap_length", overlap_length, torch.int64, E),
+              ("similarity", similarity, torch.float32, E))
     return E, R
 
 
@@ -2530,7 +2536,7 @@ def overlap_align(src, dst, prefix_length, n: int, base_off, length, packed, max
     rec: a contiguous int64 [ALIGN_RECORD_WORDS] device tensor the call ADDS to (the caller zeroes it once)."""
     _lib.load()
     _chk_dev(src, dst, prefix_length, base_off, length, packed, dist, overlap_length, similarity, rec)
-    E, R = _align_args("overlap_align", src, dst, prefix_length, n, base_off, length, packed, max_errors, dist, overlap_length,
+    E, R = _align_args("overlap_align", src, dst, prefix_length, base_off, length, packed, max_errors, dist, overlap_length,
                        similarity, rec)
     _call("gnm_overlap_align", E, _ptr(src), _ptr(dst), _ptr(prefix_length), _ptr(packed), int(packed.numel()), _ptr(base_off),
           _ptr(length), R, int(n), operator.index(max_errors), _ptr(dist), _ptr(overlap_length), _ptr(similarity), _ptr(rec), _stream())
@@ -2544,7 +2550,7 @@ def overlap_align_host(src, dst, prefix_length, n: int, base_off, length, packed
     ts = (src, dst, prefix_length, base_off, length, packed, dist, overlap_length, similarity, rec)
     if any(t.device.type != "cpu" for t in ts):
         raise ValueError("overlap_align_host: every tensor must be a CPU tensor")
-    E, R = _align_args("overlap_align_host", src, dst, prefix_length, n, base_off, length, packed, max_errors, dist, overlap_length,
+    E, R = _align_args("overlap_align_host", src, dst, prefix_length, base_off, length, packed, max_errors, dist, overlap_length,
                        similarity, rec)
     hp = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
     _lib.check(lib.gnm_overlap_align_host(E, hp(src), hp(dst), hp(prefix_length), hp(packed), int(packed.numel()), hp(base_off),
@@ -2565,12 +2571,11 @@ def optim_step(p, g, m, v, step, stats, ws, lr, beta1, beta2, eps, max_norm=0.0,
     _chk_dev(p, g, m, v, step, stats, ws, inv_count)
     n = p.numel()
     for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+        if not _fits(t, torch.float32, n):
             raise ValueError(f"optim_step: {name} must be a contiguous float32 tensor of {n} elements")
     if step.dtype != torch.float32 or step.numel() != 1 or (inv_count is not None and (inv_count.dtype != torch.float32 or inv_count.numel() != 1)):
         raise ValueError("optim_step: step (and inv_count) must be float32 scalars")
-    if stats.dtype != torch.int64 or stats.numel() != 4 or not stats.is_contiguous():
-        raise ValueError("optim_step: stats must be a contiguous int64 [4] tensor")
+    _chk_record("optim_step", stats, 4, "stats")
     wsb = ws.numel() * ws.element_size()
     _call("gnm_optim_grad_stats", n, _ptr(g), _ptr(step), _ptr(ws), wsb, _stream())
     _call("gnm_optim_adam_step", n, _ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(step), _ptr(stats), _ptr(ws), wsb, float(lr),

@@ -9,7 +9,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .engine import _call, _ptr, _stream, on_device_of, scratch
+from .engine import RecordStats, _call, _ptr, _stream, on_device_of, scratch
 
 __all__ = ["positional_encoding", "edge_features", "prepare_graph", "overlap_features", "OverlapFeatures", "AlignStats"]
 
@@ -48,7 +48,7 @@ def edge_features(overlap_length: torch.Tensor, overlap_similarity: torch.Tensor
 
 
 @dataclass
-class AlignStats:
+class AlignStats(RecordStats):
     """A gnm_align_record (include/gnm.h): edges = aligned (distance <= max_errors, non-empty) + exceeded + empty (no overlap:
     prefix_length == the read's length) + invalid (a node that names no read of the store); clamped (prefix below 0 or above the
     read's length); cells: the sum of m * |T| over the aligned edges; calls."""
@@ -83,7 +83,7 @@ class OverlapFeatures:
     @property
     def stats(self) -> AlignStats:
         if self._stats is None:
-            self._stats = AlignStats(*[int(v) for v in self.record.cpu().tolist()])
+            self._stats = AlignStats.from_record(self.record)
         return self._stats
 
 

@@ -290,11 +290,10 @@ class AssemblyStats:
 
     def __init__(self, device, min_nodes: int = ASSEMBLY_MIN_NODES, decoder: str = "best_overlap", reduce_transitive: bool = False,
                  fuzz=None):
+        from .decode import _reduce_args
         if decoder not in ASSEMBLY_DECODERS:
             raise ValueError(f"AssemblyStats: decoder {decoder!r}: expected one of {ASSEMBLY_DECODERS}")
-        if not isinstance(reduce_transitive, (bool, np.bool_)):
-            raise ValueError(f"AssemblyStats: reduce_transitive={reduce_transitive!r}: expected True or False")
-        engine.reduce_fuzz_word(fuzz, "AssemblyStats: fuzz")
+        _reduce_args("AssemblyStats", reduce_transitive, fuzz)
         self.device = torch.device(device)
         self.min_nodes = int(min_nodes)
         self.decoder = decoder
@@ -316,7 +315,8 @@ class AssemblyStats:
         self.rec += np.asarray(c.stats.words(), np.int64)
         if self.reduce_transitive:
             w = np.asarray(c.reduce_stats.words(), np.int64)
-            w[5] = max(int(w[5]), int(self.reduce_rec[5])) - int(self.reduce_rec[5])   # max_support: a maximum, not a sum
+            k = engine.REDUCE_COUNTERS.index("max_support")
+            w[k] = max(int(w[k]), int(self.reduce_rec[k])) - int(self.reduce_rec[k])   # a maximum, not a sum
             self.reduce_rec += w
         keep = c.num_nodes() >= self.min_nodes
         self.bases += c.bases[keep].cpu().tolist()
@@ -338,5 +338,5 @@ class AssemblyStats:
         """The History.assembly_valid entry: (contigs, n50_bases, longest_bases, wrong_link_fraction) -- the first three over the
         pooled contigs, the last = wrong_links / links of the summed records (NaN without a link)."""
         from .decode import n50
-        links, wrong = int(self.rec[1]), int(self.rec[4])
+        links, wrong = (int(self.rec[engine.BOG_COUNTERS.index(k)]) for k in ("links", "wrong_links"))
         return (len(self.bases), n50(self.bases), max(self.bases, default=0), _ratio(wrong, links))

@@ -130,6 +130,7 @@ def test_sources_symbols_and_abi(lib):
         assert name + "(" in hdr and name in _lib.SIGNATURES and hasattr(lib, name), name
     assert "typedef struct gnm_align_record" in hdr and "#define GNM_ABI_VERSION 7" in hdr and lib.gnm_abi_version() == 7
     assert engine.ALIGN_COUNTERS == A.COUNTERS and engine.ALIGN_RECORD_WORDS == 8 and engine.ALIGN_MAX_ERRORS == 255
+    assert tuple(features.AlignStats.__dataclass_fields__) == engine.ALIGN_COUNTERS and features.AlignStats(*range(8)).words() == list(range(8))
     assert {"overlap_features", "OverlapFeatures", "AlignStats"} <= set(features.__all__)
     assert {"junction_identity", "JunctionIdentity"} <= set(decode.__all__)
 

@@ -250,7 +250,7 @@ def lib():
 
 def test_the_library_binds_the_entry_points_at_abi_7(lib):
     import __graft_entry__ as ge
-    from gnnome_assembly_amd import _lib, engine
+    from gnnome_assembly_amd import _lib, decode, engine
     assert "gnm_bog.hip" in ge.SOURCES
     for name in ("gnm_bog_workspace_bytes", "gnm_bog_contigs"):
         assert name in _lib.SIGNATURES and getattr(lib, name).argtypes == _lib.SIGNATURES[name][1], name
@@ -259,6 +259,7 @@ def test_the_library_binds_the_entry_points_at_abi_7(lib):
     assert "gnm_bog_record" in hdr and "int gnm_bog_contigs(" in hdr and "size_t gnm_bog_workspace_bytes(" in hdr
     assert "#define GNM_ABI_VERSION 7" in hdr
     assert engine.BOG_COUNTERS == B.COUNTERS and engine.BOG_RECORD_WORDS == B.WORDS == 8
+    assert tuple(decode.BogStats.__dataclass_fields__) == engine.BOG_COUNTERS and decode.BogStats(*range(8)).words() == list(range(8))
     assert "gnm_bog.hip" in open(os.path.join(REPO, "INTEGRATION.md")).read()
     # 72 bytes per node (two generations of a 16-byte record and an 8-byte offset, six int32 arrays) and the block sums
     assert lib.gnm_bog_workspace_bytes(0) == 0 == lib.gnm_bog_workspace_bytes(-1) == lib.gnm_bog_workspace_bytes(2 ** 31 - 1)

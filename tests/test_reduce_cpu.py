@@ -97,6 +97,7 @@ def test_the_decode_functions_refuse_a_cpu_graph_and_bad_arguments():
     g, sc, pl, rl = _cpu_args()
     assert {"transitive_support", "TransitiveSupport", "ReduceStats"} <= set(decode.__all__) and engine.REDUCE_RECORD_WORDS == 8
     assert engine.REDUCE_COUNTERS == T.COUNTERS
+    assert tuple(decode.ReduceStats.__dataclass_fields__) == engine.REDUCE_COUNTERS and decode.ReduceStats(*range(8)).words() == list(range(8))
     with pytest.raises(GnmError, match="HIP device"):
         decode.transitive_support(g, sc, pl)
     for fn in (decode.best_overlap_contigs, decode.greedy_cover_contigs):

@@ -200,7 +200,7 @@ def test_ng50_and_quick_evaluation_by_hand():
 # ---- 5. the bindings ---------------------------------------------------------------------------------------------------------------------
 def test_sources_symbols_and_abi(lib):
     import __graft_entry__ as ge
-    from gnnome_assembly_amd import _lib, engine
+    from gnnome_assembly_amd import _lib, decode, engine
     assert "gnm_seq.hip" in ge.SOURCES
     hdr = open(os.path.join(REPO, "include", "gnm.h")).read()
     for name in ("gnm_seq_layout", "gnm_seq_emit", "gnm_seq_workspace_bytes", "gnm_decode_walk_edges"):
@@ -208,6 +208,7 @@ def test_sources_symbols_and_abi(lib):
     assert lib.gnm_abi_version() == _lib.ABI_VERSION == 7
     assert f"#define GNM_SEQ_CHUNK_BASES {engine.SEQ_CHUNK_BASES}\n" in hdr and engine.SEQ_CHUNK_BASES % 16 == 0
     assert engine.SEQ_COUNTERS == S.COUNTERS and engine.SEQ_RECORD_WORDS == 8
+    assert tuple(decode.SeqStats.__dataclass_fields__) == engine.SEQ_COUNTERS and decode.SeqStats(*range(8)).words() == list(range(8))
     assert lib.gnm_seq_workspace_bytes(0) == 0 and lib.gnm_seq_workspace_bytes(257) == 16 and lib.gnm_seq_workspace_bytes(-1) == 0
 
 
