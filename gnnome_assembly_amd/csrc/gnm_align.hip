@@ -8,14 +8,15 @@
 // loops only.  The column loop of an edge runs m = la - p times, m known (and checked against the store) before it starts; a lane
 // whose edge is shorter than its wave's longest idles until the wave is done.
 // Every edge has one writer: plain vector stores of dist, overlap_length and similarity at the edge's id.  Record: counters in
-// registers, summed over the wave by shuffles and over the workgroup in LDS, then one 64-bit integer atomic per non-zero word and
-// workgroup: outputs and record depend on the inputs alone, not on the grid.
+// registers, then gnm_group.h's block_count_add (one 64-bit integer atomic per non-zero word and workgroup): outputs and record
+// depend on the inputs alone, not on the grid.
 // gnm_overlap_align_host: the same header routine over host arrays, on `threads` host threads (contiguous ranges of edges, their
 // counters added at the end).
 #include <thread>
 #include <vector>
 
 #include "gnm_common.h"
+#include "gnm_group.h"
 #include "gnm_align.h"
 
 namespace gnm {
@@ -40,25 +41,6 @@ GNM_SEQ_FN AlignEdge align_one_(const AlignArgs& a, int64_t k) {
   return r;
 }
 
-// The workgroup's sum of v, added to *word by one atomic (none when it is 0).  Every thread of the workgroup calls it.
-__device__ __forceinline__ void aln_count_(unsigned long long v, unsigned long long* lds, unsigned long long* word) {
-  unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long s = (((unsigned long long)hi << 32) | lo) +
-                                 (((unsigned long long)__shfl_xor(hi, off, 64) << 32) | __shfl_xor(lo, off, 64));
-    lo = (unsigned)s;
-    hi = (unsigned)(s >> 32);
-  }
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = ((unsigned long long)hi << 32) | lo;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long t = lds[0] + lds[1] + lds[2] + lds[3];
-    if (t) atomicAdd(word, t);
-  }
-  __syncthreads();
-}
-
 template <int NW>
 __global__ __launch_bounds__(kBlock) void overlap_align_k(AlignArgs a, unsigned long long* rec) {
   __shared__ unsigned long long lds[kWavesPerBlock];
@@ -76,12 +58,12 @@ __global__ __launch_bounds__(kBlock) void overlap_align_k(AlignArgs a, unsigned 
     aligned += r.flags & (kAlnFlagInvalid | kAlnFlagEmpty | kAlnFlagExceeded) ? 0u : 1u;
     cells += (unsigned long long)r.cells;
   }
-  aln_count_(aligned, lds, rec + kAlnAligned);
-  aln_count_(exceeded, lds, rec + kAlnExceeded);
-  aln_count_(empty, lds, rec + kAlnEmpty);
-  aln_count_(clamped, lds, rec + kAlnClamped);
-  aln_count_(invalid, lds, rec + kAlnInvalid);
-  aln_count_(cells, lds, rec + kAlnCells);
+  block_count_add((unsigned long long)aligned, lds, rec + kAlnAligned);
+  block_count_add((unsigned long long)exceeded, lds, rec + kAlnExceeded);
+  block_count_add((unsigned long long)empty, lds, rec + kAlnEmpty);
+  block_count_add((unsigned long long)clamped, lds, rec + kAlnClamped);
+  block_count_add((unsigned long long)invalid, lds, rec + kAlnInvalid);
+  block_count_add(cells, lds, rec + kAlnCells);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     atomicAdd(rec + kAlnEdges, (unsigned long long)a.E);
     atomicAdd(rec + kAlnCalls, 1ull);
@@ -111,13 +93,9 @@ static int align_check(const char* what, int64_t E, const int32_t* src, const in
   GNM_CHECK_ARG(E >= 0 && E < INT32_MAX, "%s: E = %lld: expected 0 <= E < 2^31 - 1", what, (long long)E);
   GNM_CHECK_ARG(max_errors >= 0 && max_errors <= kAlignMaxErrors, "%s: max_errors = %d: expected 0 <= max_errors <= %d", what,
                 max_errors, kAlignMaxErrors);
-  GNM_CHECK_ARG(n >= 0 && R >= 0 && n < INT32_MAX && R < INT32_MAX, "%s: n = %lld, R = %lld: expected 0 <= n, R < 2^31 - 1", what,
-                (long long)n, (long long)R);
-  GNM_CHECK_ARG(packed_bytes >= 0 && packed_bytes % 16 == 0 && packed_bytes <= (INT64_MAX >> 2),
-                "%s: packed_bytes = %lld: the store is whole 16-byte groups", what, (long long)packed_bytes);
-  GNM_CHECK_ARG(R == 0 || (base_off && length), "%s: base_off and length must not be null when R > 0", what);
+  if (seq_store_check(what, n, R, base_off, length, packed_bytes)) return -1;
   GNM_CHECK_ARG(packed_bytes == 0 || (packed && ((uintptr_t)packed & 3) == 0), "%s: packed must be non-null and 4-byte aligned", what);
-  GNM_CHECK_ARG(record && ((uintptr_t)record & 7) == 0, "%s: record must be a non-null, 8-byte aligned gnm_align_record", what);
+  if (record_check(what, record, "gnm_align_record")) return -1;
   GNM_CHECK_ARG(E == 0 || (src && dst && pl && dist && olen && sim),
                 "%s: src, dst, prefix_length, dist, overlap_length and similarity must not be null when E > 0", what);
   return 0;

@@ -17,8 +17,8 @@
 //   bog_rank_k  x K   round: a node whose ptr is live adds the record of ptr[v] to its own and takes over its ptr (a further
 //                     pointer, or the finished ~head).  The last round also stores the path's length at its head.
 //   bog_bsum_k, bog_scan_k, bog_apply_k   exclusive prefix sums in NODE order of the head flags (-> contig number) and of the
-//                     lengths stored at the heads (-> contig_ptr), in the three-phase fixed-block form of gnm_induce.hip: sums of
-//                     blocks of kBogBlk nodes, one workgroup per sequence over the block sums, in-block scan.
+//                     lengths stored at the heads (-> contig_ptr), in three phases over fixed blocks of kBogBlk nodes: their
+//                     sums, one workgroup per sequence over the block sums, in-block scan (gnm_group.h).
 //   bog_layout_k      walk_nodes / walk_edges at contig_ptr[c] + rank, contig_bases / contig_wrong from the tails, the counters.
 // Every round reads one generation and writes the other (ping-pong): no kernel reads what the same launch writes, no workgroup
 // waits for another, there is no flag, no cooperative launch and no read-back between the launches.  A node's state is one
@@ -29,6 +29,7 @@
 // Bounds.  A table entry outside [0, E) and a src / dst entry outside [0, n) drop the candidate before they address anything;
 // pointers kept in the workspace are built from checked values and are checked again where they address a caller's array.
 #include "gnm_common.h"
+#include "gnm_group.h"
 
 namespace gnm {
 
@@ -49,42 +50,6 @@ struct BogArgs {
   int64_t* contig_bases;
   unsigned long long* rec;
 };
-
-// The workgroup's sum of v, added to *word by one atomic (none when it is 0).  Every thread of the workgroup calls it.
-__device__ __forceinline__ void bog_count_(unsigned v, unsigned* lds, unsigned long long* word) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned t = lds[0] + lds[1] + lds[2] + lds[3];
-    if (t) atomicAdd(word, (unsigned long long)t);
-  }
-  __syncthreads();
-}
-
-// Exclusive scan of one value per thread over the workgroup, in thread order; `total` = the workgroup's sum.
-__device__ __forceinline__ int bog_block_scan_(int v, int* lds, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(x, off, 64);
-    if (lane >= off) x += o;
-  }
-  if (lane == 63) lds[wave] = x;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kWavesPerBlock; ++w) {
-    const int t = lds[w];
-    before += w < wave ? t : 0;
-    total += t;
-  }
-  __syncthreads();
-  return before + x - v;
-}
 
 __global__ __launch_bounds__(kBlock) void bog_link_k(BogArgs a) {
   __shared__ unsigned lds[kWavesPerBlock];
@@ -114,7 +79,7 @@ __global__ __launch_bounds__(kBlock) void bog_link_k(BogArgs a) {
     a.pedge[v] = pe;
     a.mn[0][v] = make_int2(pv, (int)v);
   }
-  bog_count_(dropped, lds, a.rec + kBogDropped);
+  block_count_add(dropped, lds, a.rec + kBogDropped);
 }
 
 __global__ __launch_bounds__(kBlock) void bog_min_k(BogArgs a, int g) {
@@ -158,7 +123,7 @@ __global__ __launch_bounds__(kBlock) void bog_rank_init_k(BogArgs a, int gmin) {
     a.ro[0][v] = off;
     a.plen[v] = 0;
   }
-  bog_count_(cut, lds, a.rec + kBogCyclesCut);
+  block_count_add(cut, lds, a.rec + kBogCyclesCut);
 }
 
 __global__ __launch_bounds__(kBlock) void bog_rank_k(BogArgs a, int g, int last) {
@@ -202,44 +167,25 @@ __device__ __forceinline__ void bog_ld4_(const BogArgs& a, int64_t k0, int f[4],
 }
 
 __global__ __launch_bounds__(kBlock) void bog_bsum_k(BogArgs a) {
-  __shared__ int red[2][kWavesPerBlock];
+  __shared__ int red[kWavesPerBlock];
   for (int64_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
     int f[4], l[4];
     bog_ld4_(a, b * kBogBlk + 4 * (int64_t)threadIdx.x, f, l);
-    int sf = f[0] + f[1] + f[2] + f[3], sl = l[0] + l[1] + l[2] + l[3];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      sf += __shfl_xor(sf, off, 64);
-      sl += __shfl_xor(sl, off, 64);
+    const int sf = block_sum(f[0] + f[1] + f[2] + f[3], red), sl = block_sum(l[0] + l[1] + l[2] + l[3], red);
+    if (threadIdx.x == 0) {
+      a.bsum[0][b] = sf;
+      a.bsum[1][b] = sl;
     }
-    if ((threadIdx.x & 63) == 0) {
-      red[0][threadIdx.x >> 6] = sf;
-      red[1][threadIdx.x >> 6] = sl;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) a.bsum[threadIdx.x][b] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-    __syncthreads();
   }
 }
 
-// Workgroup s turns the block sums of sequence s into their exclusive prefix, in place (gnm_induce.hip's ind_scan_k).  The flag
+// Workgroup s turns the block sums of sequence s into their exclusive prefix, in place (scan_block_sums).  The flag
 // sequence's total is the contig count C: contig_ptr[C] = n (every node lies on one path), record.contigs += C, calls += 1.
 __global__ __launch_bounds__(kBlock) void bog_scan_k(BogArgs a) {
   __shared__ int lds[kWavesPerBlock];
   const int s = blockIdx.x;
-  const int64_t chunk = (a.nb + kBlock - 1) / kBlock;
-  int32_t* bs = a.bsum[s];
-  const int64_t b0 = (int64_t)threadIdx.x * chunk < a.nb ? (int64_t)threadIdx.x * chunk : a.nb;
-  const int64_t b1 = b0 + chunk < a.nb ? b0 + chunk : a.nb;
-  int t = 0;
-  for (int64_t b = b0; b < b1; ++b) t += bs[b];
   int total;
-  int run = bog_block_scan_(t, lds, total);
-  for (int64_t b = b0; b < b1; ++b) {
-    const int v = bs[b];
-    bs[b] = run;
-    run += v;
-  }
+  scan_block_sums(a.bsum[s], a.nb, lds, total);
   if (s == 0 && threadIdx.x == 0) {
     if (a.contig_ptr && total >= 0 && (int64_t)total <= a.n) a.contig_ptr[total] = (int32_t)a.n;
     if (total > 0) atomicAdd(a.rec + kBogContigs, (unsigned long long)total);
@@ -253,21 +199,10 @@ __global__ __launch_bounds__(kBlock) void bog_apply_k(BogArgs a) {
     const int64_t k0 = b * kBogBlk + 4 * (int64_t)threadIdx.x;
     int f[4], l[4], total;
     bog_ld4_(a, k0, f, l);
-    const int x0 = a.bsum[0][b] + bog_block_scan_(f[0] + f[1] + f[2] + f[3], lds, total);
-    const int y0 = a.bsum[1][b] + bog_block_scan_(l[0] + l[1] + l[2] + l[3], lds, total);
-    const int x[4] = {x0, x0 + f[0], x0 + f[0] + f[1], x0 + f[0] + f[1] + f[2]};
-    const int y[4] = {y0, y0 + l[0], y0 + l[0] + l[1], y0 + l[0] + l[1] + l[2]};
-    if (k0 + 3 < a.n) {
-      *reinterpret_cast<int4*>(a.pre_f + k0) = make_int4(x[0], x[1], x[2], x[3]);
-      *reinterpret_cast<int4*>(a.pre_l + k0) = make_int4(y[0], y[1], y[2], y[3]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (k0 + i < a.n) {
-          a.pre_f[k0 + i] = x[i];
-          a.pre_l[k0 + i] = y[i];
-        }
-    }
+    const int x0 = a.bsum[0][b] + block_scan_excl(f[0] + f[1] + f[2] + f[3], lds, total);
+    const int y0 = a.bsum[1][b] + block_scan_excl(l[0] + l[1] + l[2] + l[3], lds, total);
+    store4_excl(a.pre_f, k0, a.n, x0, f);
+    store4_excl(a.pre_l, k0, a.n, y0, l);
   }
 }
 
@@ -305,17 +240,15 @@ __global__ __launch_bounds__(kBlock) void bog_layout_k(BogArgs a, int g) {
       }
     }
   }
-  bog_count_(links, lds, a.rec + kBogLinks);
-  bog_count_(wrong, lds, a.rec + kBogWrongLinks);
-  bog_count_(mnodes, lds, a.rec + kBogMultiNodes);
-  bog_count_(mcontigs, lds, a.rec + kBogMultiContigs);
+  block_count_add(links, lds, a.rec + kBogLinks);
+  block_count_add(wrong, lds, a.rec + kBogWrongLinks);
+  block_count_add(mnodes, lds, a.rec + kBogMultiNodes);
+  block_count_add(mcontigs, lds, a.rec + kBogMultiContigs);
 }
 
 }  // namespace gnm
 
 using namespace gnm;
-
-static inline size_t bog_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
 
 // ws: ra[0], ra[1] (16 n each), ro[0], ro[1] (8 n), next, prev, pedge, plen, pre_f, pre_l (4 n), two block-sum arrays
 struct BogLayout {
@@ -325,10 +258,10 @@ static BogLayout bog_layout(int64_t n) {
   BogLayout l;
   size_t off = 0;
   const size_t nb = (size_t)((n + kBogBlk - 1) / kBogBlk);
-  for (int g = 0; g < 2; ++g) { l.ra[g] = off; off += bog_pad((size_t)n * 16); }
-  for (int g = 0; g < 2; ++g) { l.ro[g] = off; off += bog_pad((size_t)n * 8); }
-  for (int i = 0; i < 6; ++i) { l.i32[i] = off; off += bog_pad((size_t)n * 4); }
-  for (int s = 0; s < 2; ++s) { l.bsum[s] = off; off += bog_pad(nb * 4); }
+  for (int g = 0; g < 2; ++g) { l.ra[g] = off; off += ws_pad((size_t)n * 16); }
+  for (int g = 0; g < 2; ++g) { l.ro[g] = off; off += ws_pad((size_t)n * 8); }
+  for (int i = 0; i < 6; ++i) { l.i32[i] = off; off += ws_pad((size_t)n * 4); }
+  for (int s = 0; s < 2; ++s) { l.bsum[s] = off; off += ws_pad(nb * 4); }
   l.bytes = off;
   return l;
 }
@@ -343,9 +276,8 @@ extern "C" int gnm_bog_contigs(int64_t n, int64_t E, const int32_t* src, const i
                                const int64_t* read_length, float min_logit, void* record, int32_t* contig_ptr, int32_t* walk_nodes,
                                int32_t* walk_edges, int64_t* contig_bases, int32_t* contig_wrong, void* ws, size_t ws_bytes,
                                void* stream) {
-  GNM_CHECK_ARG(n >= 0 && E >= 0 && n < INT32_MAX && E < INT32_MAX,
-                "bog_contigs: n = %lld, E = %lld: expected 0 <= n, E < 2^31 - 1 (32-bit node and edge ids)", (long long)n, (long long)E);
-  GNM_CHECK_ARG(record && ((uintptr_t)record & 7) == 0, "bog_contigs: record must be a non-null, 8-byte aligned gnm_bog_record");
+  if (index_size_check("bog_contigs", n, E, "32-bit node and edge ids") || record_check("bog_contigs", record, "gnm_bog_record"))
+    return -1;
   GNM_CHECK_ARG(n == 0 || (best_succ && best_pred && read_length),
                 "bog_contigs: best_succ, best_pred and read_length must not be null when n > 0");
   GNM_CHECK_ARG(n == 0 || (contig_ptr && walk_nodes && walk_edges && contig_bases && contig_wrong),
@@ -353,9 +285,7 @@ extern "C" int gnm_bog_contigs(int64_t n, int64_t E, const int32_t* src, const i
   GNM_CHECK_ARG(E == 0 || (src && dst && scores && prefix_length),
                 "bog_contigs: src, dst, scores and prefix_length must not be null when E > 0");
   const BogLayout l = bog_layout(n);
-  GNM_CHECK_ARG(l.bytes == 0 || (ws && ws_bytes >= l.bytes && ((uintptr_t)ws & 15) == 0),
-                "bog_contigs: workspace of %zu bytes too small (gnm_bog_workspace_bytes: %zu), null or not 16-byte aligned", ws_bytes,
-                l.bytes);
+  if (ws_check("bog_contigs", "gnm_bog_workspace_bytes", ws, ws_bytes, l.bytes)) return -1;
   hipStream_t st = (hipStream_t)stream;
   char* w = (char*)ws;
   BogArgs a;

@@ -37,6 +37,24 @@ int reduce_partials_batched(const double* partials, int batch, int nblk, int W, 
     if (e__ != hipSuccess) return ::gnm::hip_fail(e__, what);    \
   } while (0)
 
+// Argument checks shared by the entry points of the index kernels; `what` is the entry point's name without its gnm_ prefix.
+// Each returns 0, or -1 with the message set.
+inline size_t ws_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }   // every workspace array starts 16-byte aligned
+inline int index_size_check(const char* what, int64_t n, int64_t E, const char* why) {
+  GNM_CHECK_ARG(n >= 0 && E >= 0 && n < INT32_MAX && E < INT32_MAX, "%s: n = %lld, E = %lld: expected 0 <= n, E < 2^31 - 1 (%s)", what,
+                (long long)n, (long long)E, why);
+  return 0;
+}
+inline int record_check(const char* what, const void* record, const char* type) {
+  GNM_CHECK_ARG(record && ((uintptr_t)record & 7) == 0, "%s: record must be a non-null, 8-byte aligned %s", what, type);
+  return 0;
+}
+inline int ws_check(const char* what, const char* sizer, const void* ws, size_t ws_bytes, size_t need) {
+  GNM_CHECK_ARG(need == 0 || (ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0),
+                "%s: workspace of %zu bytes too small (%s: %zu), null or not 16-byte aligned", what, ws_bytes, sizer, need);
+  return 0;
+}
+
 // Grid for the persistent row/segment kernels: a multiple of 8 (one slice per XCD),
 // at most kMaxPartialBlocks, at least enough to give every block `min_items` items.
 // `call_cap` > 0: the caller's per-call cap on workgroups per CU (entry points that take max_blocks_per_cu);

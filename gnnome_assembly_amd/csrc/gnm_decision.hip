@@ -17,8 +17,8 @@
 // unsigned maximum (edge ids are distinct: the label bit never decides) and the winner carries its label along.  Every
 // candidate word is >= 4 (eid <= 2^31 - 3), so 0 stands for "no candidate".
 //
-// Kernel.  Mean degree is about 5, so a node takes kDecLanes = 8 lanes, not a wave: a wave serves eight consecutive nodes side
-// by side, a group's lanes stride over its node's candidates (a node with more than eight loops), and three xor-shuffles inside
+// Kernel.  Mean degree is about 5, so a node takes kGroupLanes = 8 lanes, not a wave (gnm_group.h): a wave serves eight consecutive
+// nodes side by side, a group's lanes stride over its node's candidates (a node with more than eight loops), and three xor-shuffles inside
 // the group give every lane the group's maximum, candidate count and "some candidate has y == 1".  The group's first lane
 // writes the two table entries (through nperm: the caller's numbering) and counts the node.  A group handles both directions
 // of its node; the two chains of dependent loads are independent and overlap.
@@ -30,58 +30,45 @@
 // Bounds.  Every value read from an index array is checked before it addresses anything: row pointers are clamped to
 // 0 <= lo <= hi <= E, a position or edge id outside [0, E) drops the candidate, a row nperm[i] outside [0, n) is never written.
 #include "gnm_common.h"
+#include "gnm_group.h"
 #include "gnm_key.h"                                    // dec_key_: shared with gnm_cover.hip
 
 namespace gnm {
 
-constexpr int kDecLanes = 8;                            // lanes per node
-constexpr int kDecNodes = kBlock / kDecLanes;           // nodes per workgroup and round
 constexpr int kDecCounters = 7;                         // per direction; the record's order
 enum { kDead = 0, kForced, kForcedOk, kBranch, kBranchSolvable, kBranchOk, kBranchNan };
 
 struct DecArgs {
-  int64_t n, E;
-  const int32_t *perm, *isrc, *in_ptr, *out_ptr, *out_pos, *out_dst, *nperm;
+  IndexRows ix;
   const float *scores, *y;
   int32_t* best[2];                                     // succ, pred; either may be NULL
 };
-
-__device__ __forceinline__ unsigned long long dec_shfl_xor_(unsigned long long v, int off) {
-  const unsigned lo = __shfl_xor((unsigned)v, off, kDecLanes), hi = __shfl_xor((unsigned)(v >> 32), off, kDecLanes);
-  return ((unsigned long long)hi << 32) | lo;
-}
 
 // One direction of one node (D = 0: successors, 1: predecessors).  Every lane of the group calls this together; `valid` is
 // group-uniform.  cnt: the thread's 2 x kDecCounters counters.
 template <int D>
 __device__ __forceinline__ void dec_node_(const DecArgs& a, int i, bool valid, int sub, int row, unsigned* cnt) {
-  const int E = (int)a.E;
   unsigned long long best = 0ull;
   unsigned num = 0u, anyp = 0u;
   if (valid) {
-    const int32_t* ptr = D ? a.in_ptr : a.out_ptr;
-    int lo = ptr[i], hi = ptr[i + 1];
-    lo = lo < 0 ? 0 : (lo > E ? E : lo);
-    hi = hi < lo ? lo : (hi > E ? E : hi);
-    for (int p = lo + sub; p < hi; p += kDecLanes) {
-      const int j = D ? p : a.out_pos[p];
-      const int other = D ? a.isrc[p] : a.out_dst[p];
-      if (other == i || (unsigned)j >= (unsigned)E) continue;          // a self loop; a position outside the index
-      const int eid = a.perm[j];
-      if ((unsigned)eid >= (unsigned)E) continue;
-      const unsigned yp = (a.y && a.y[eid] == 1.0f) ? 1u : 0u;         // any other label, NaN included: not 1
-      const unsigned long long w = ((unsigned long long)dec_key_(a.scores[eid]) << 32) | ((0x7fffffffu - (unsigned)eid) << 1) | yp;
-      best = w > best ? w : best;
-      num += 1u;
-      anyp |= yp;
-    }
+    int lo, hi;
+    row_clamped(D ? a.ix.in_ptr : a.ix.out_ptr, i, (int)a.ix.E, lo, hi);
+    walk_candidates<D>(
+        a.ix, lo + sub, hi, [&](int other) { return other != i; },     // a self loop is no candidate
+        [&](int, int, int, int eid) {
+          const unsigned yp = (a.y && a.y[eid] == 1.0f) ? 1u : 0u;     // any other label, NaN included: not 1
+          const unsigned long long w = ((unsigned long long)dec_key_(a.scores[eid]) << 32) | ((0x7fffffffu - (unsigned)eid) << 1) | yp;
+          best = w > best ? w : best;
+          num += 1u;
+          anyp |= yp;
+        });
   }
 #pragma unroll
-  for (int off = kDecLanes / 2; off > 0; off >>= 1) {
-    const unsigned long long o = dec_shfl_xor_(best, off);
+  for (int off = kGroupLanes / 2; off > 0; off >>= 1) {                // the maximum as group_max_u64 does it, its steps shared
+    const unsigned long long o = shfl_xor_u64<kGroupLanes>(best, off);
     best = o > best ? o : best;
-    num += __shfl_xor(num, off, kDecLanes);
-    anyp |= __shfl_xor(anyp, off, kDecLanes);
+    num += __shfl_xor(num, off, kGroupLanes);
+    anyp |= __shfl_xor(anyp, off, kGroupLanes);
   }
   if (!valid || sub != 0) return;
   unsigned* c = cnt + D * kDecCounters;
@@ -109,25 +96,24 @@ __global__ __launch_bounds__(kBlock) void decision_stats_k(DecArgs a, unsigned l
   unsigned cnt[2 * kDecCounters];
 #pragma unroll
   for (int k = 0; k < 2 * kDecCounters; ++k) cnt[k] = 0u;
-  const int sub = threadIdx.x & (kDecLanes - 1), grp = threadIdx.x / kDecLanes;
-  // base is workgroup-uniform: every lane of a wave takes the same number of rounds, so the shuffles never meet an idle group
-  for (int64_t base = (int64_t)blockIdx.x * kDecNodes; base < a.n; base += (int64_t)gridDim.x * kDecNodes) {
+  // for_group_nodes written out, and the three shuffles of a step kept together in dec_node_: through the shared forms the
+  // compiler orders this loop differently, and the launch measured 151 us against 146 us (7.5 M edges, windows within 5 us).
+  const int sub = threadIdx.x & (kGroupLanes - 1), grp = threadIdx.x / kGroupLanes;
+  for (int64_t base = (int64_t)blockIdx.x * kGroupNodes; base < a.ix.n; base += (int64_t)gridDim.x * kGroupNodes) {
     const int64_t i64 = base + grp;
-    const bool valid = i64 < a.n;
+    const bool valid = i64 < a.ix.n;
     const int i = valid ? (int)i64 : 0;
     int row = -1;                                       // the caller's id of node i; -1: outside [0, n), never written
     if (valid && sub == 0) {
-      const int64_t v = a.nperm ? (int64_t)a.nperm[i] : i64;
-      row = (v >= 0 && v < a.n) ? (int)v : -1;
+      const int64_t v = a.ix.nperm ? (int64_t)a.ix.nperm[i] : i64;
+      row = (v >= 0 && v < a.ix.n) ? (int)v : -1;
     }
     dec_node_<0>(a, i, valid, sub, row, cnt);
     dec_node_<1>(a, i, valid, sub, row, cnt);
   }
 #pragma unroll
   for (int k = 0; k < 2 * kDecCounters; ++k) {
-    unsigned v = cnt[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    const unsigned v = wave_sum(cnt[k]);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(&tot[k], v);
   }
   __syncthreads();
@@ -143,19 +129,17 @@ extern "C" int gnm_decision_stats(int64_t n, int64_t E, const int32_t* perm, con
                                   const int32_t* nperm, const float* scores, const float* y, void* record, int32_t* best_succ,
                                   int32_t* best_pred, void* stream) {
   (void)idst;                                           // the index travels whole; the destination of in-edge j of node i is i
-  GNM_CHECK_ARG(n >= 0 && E >= 0 && n < INT32_MAX && E < INT32_MAX,
-                "decision_stats: n = %lld, E = %lld: expected 0 <= n, E < 2^31 - 1 (the index holds 32-bit positions)", (long long)n,
-                (long long)E);
-  GNM_CHECK_ARG(record && ((uintptr_t)record & 7) == 0, "decision_stats: record must be a non-null, 8-byte aligned gnm_decision_record");
+  if (index_size_check("decision_stats", n, E, "the index holds 32-bit positions") ||
+      record_check("decision_stats", record, "gnm_decision_record"))
+    return -1;
   GNM_CHECK_ARG(n == 0 || (in_ptr && out_ptr), "decision_stats: in_ptr and out_ptr must not be null when n > 0");
   GNM_CHECK_ARG(E == 0 || (perm && isrc && out_pos && out_dst && scores),
                 "decision_stats: perm, isrc, out_pos, out_dst and scores must not be null when E > 0");
   DecArgs a;
-  a.n = n; a.E = E;
-  a.perm = perm; a.isrc = isrc; a.in_ptr = in_ptr; a.out_ptr = out_ptr; a.out_pos = out_pos; a.out_dst = out_dst; a.nperm = nperm;
+  a.ix = IndexRows{n, E, perm, isrc, in_ptr, out_ptr, out_pos, out_dst, nperm};
   a.scores = scores; a.y = y;
   a.best[0] = best_succ; a.best[1] = best_pred;
-  const int grid = persistent_grid(n, kDecNodes, 8);
+  const int grid = persistent_grid(n, kGroupNodes, 8);
   hipLaunchKernelGGL(decision_stats_k, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, (unsigned long long*)record);
   GNM_LAUNCH_CHECK("decision_stats");
   return 0;

@@ -11,11 +11,12 @@
 // The prefix sum has three phases over FIXED blocks of kIndBlk elements (independent of the grid and the CU count):
 //   ind_flags_k   flags (bytes) + one int32 sum per block      (launch A: sequences 0-2; launch B: 3-4, which read keepE)
 //   ind_scan_k    one workgroup per sequence turns its block sums into their exclusive prefix; totals n', e' as int64
-//   ind_apply_k   in-block scan (DPP row_shr inside the waves, four wave totals through LDS) + the block's offset
+//   ind_apply_k   in-block scan (gnm_group.h's block_scan_excl) + the block's offset
 // No kernel waits for another workgroup: no look-back, no flag, no atomic.  ind_fill_k then writes every array of the sub-graph.
 // Every index that is read from memory is range-checked before it addresses anything: a malformed index or sizes that do not
 // belong to the count before them can give wrong numbers, never an access outside the caller's arrays.
 #include "gnm_common.h"
+#include "gnm_group.h"
 
 namespace gnm {
 
@@ -68,40 +69,6 @@ __device__ __forceinline__ uint32_t ind_ldflags(const uint8_t* __restrict__ f, i
   return w;
 }
 
-template <int CTRL>
-__device__ __forceinline__ int dpp_mov_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-// Inclusive scan over the 64 lanes in lane order (gnm_features.hip's wave_scan_f64 on integers): row_shr 1/2/4/8 inside the
-// 16-lane rows, then the totals of the rows before this lane's row.  `total` = the wave's sum, in every lane.
-__device__ __forceinline__ int wave_scan_i32(int v, int& total) {
-  v += dpp_mov_i32<0x111>(v);
-  v += dpp_mov_i32<0x112>(v);
-  v += dpp_mov_i32<0x114>(v);
-  v += dpp_mov_i32<0x118>(v);
-  const int r0 = __shfl(v, 15, 64), r1 = __shfl(v, 31, 64), r2 = __shfl(v, 47, 64), r3 = __shfl(v, 63, 64);
-  const int row = (threadIdx.x & 63) >> 4;
-  total = r0 + r1 + r2 + r3;
-  return v + (row > 0 ? r0 : 0) + (row > 1 ? r1 : 0) + (row > 2 ? r2 : 0);
-}
-// Exclusive scan of one value per thread over the workgroup, in thread order; `total` = the workgroup's sum.  Every thread of the
-// workgroup calls it; `lds` [kWavesPerBlock] may be reused right after the call.
-__device__ __forceinline__ int block_scan_excl_i32(int v, int* lds, int& total) {
-  int wt;
-  const int incl = wave_scan_i32(v, wt);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) lds[wave] = wt;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kWavesPerBlock; ++w) {
-    const int x = lds[w];
-    before += w < wave ? x : 0;
-    total += x;
-  }
-  __syncthreads();
-  return before + incl - v;
-}
-
 // Phase 1: the flags of the sequences in `seqs` and the sum of every block of kIndBlk of them.
 __global__ __launch_bounds__(kBlock) void ind_flags_k(IndArgs a, unsigned seqs, int64_t nblocks) {
   __shared__ int red[kWavesPerBlock];
@@ -151,35 +118,19 @@ __global__ __launch_bounds__(kBlock) void ind_flags_k(IndArgs a, unsigned seqs, 
       for (int i = 0; i < 4; ++i)
         if (k0 + i < len) fl[k0 + i] = (uint8_t)f[i];
     }
-    int cnt = f[0] + f[1] + f[2] + f[3];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) a.bsum[s][b] = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
+    const int cnt = block_sum(f[0] + f[1] + f[2] + f[3], red);
+    if (threadIdx.x == 0) a.bsum[s][b] = cnt;
   }
 }
 
-// Phase 2: workgroup s turns the block sums of sequence s into their exclusive prefix, in place: thread t owns `chunk`
-// consecutive blocks, the workgroup scans the 256 chunk totals.  Totals in int64 (the sums themselves stay below 2^31: E does).
+// Phase 2: workgroup s turns the block sums of sequence s into their exclusive prefix, in place (scan_block_sums).  The totals
+// leave as int64 (the sums themselves stay below 2^31: E does).
 __global__ __launch_bounds__(kBlock) void ind_scan_k(IndArgs a) {
   __shared__ int lds[kWavesPerBlock];
   const int s = blockIdx.x;
   if (s == 1 && !a.has_rank) return;
-  const int64_t nblk = ind_nblk(a, s), chunk = (nblk + kBlock - 1) / kBlock;
-  int32_t* bs = a.bsum[s];
-  const int64_t b0 = (int64_t)threadIdx.x * chunk < nblk ? (int64_t)threadIdx.x * chunk : nblk;
-  const int64_t b1 = b0 + chunk < nblk ? b0 + chunk : nblk;
-  int64_t t = 0;
-  for (int64_t b = b0; b < b1; ++b) t += bs[b];
   int total;
-  int run = block_scan_excl_i32((int)t, lds, total);
-  for (int64_t b = b0; b < b1; ++b) {
-    const int v = bs[b];
-    bs[b] = run;
-    run += v;
-  }
+  scan_block_sums(a.bsum[s], ind_nblk(a, s), lds, total);
   if (threadIdx.x == 0) {
     if (s == 0) a.sizes[0] = (int64_t)total;
     if (s == 2) a.sizes[1] = (int64_t)total;
@@ -195,18 +146,10 @@ __global__ __launch_bounds__(kBlock) void ind_apply_k(IndArgs a, unsigned seqs, 
     if (!ind_locate(a, seqs, c, s, b)) break;
     const int64_t len = ind_len(a, s), k0 = b * kIndBlk + 4 * (int64_t)threadIdx.x;
     const uint32_t w = ind_ldflags(a.flag[s], k0, len);
-    const int f0 = w & 1u, f1 = (w >> 8) & 1u, f2 = (w >> 16) & 1u, f3 = (w >> 24) & 1u;
+    const int f[4] = {(int)(w & 1u), (int)((w >> 8) & 1u), (int)((w >> 16) & 1u), (int)((w >> 24) & 1u)};
     int total;
-    const int x0 = a.bsum[s][b] + block_scan_excl_i32(f0 + f1 + f2 + f3, lds, total);
-    int32_t* out = a.pre[s];
-    if (k0 + 3 < len) {
-      *reinterpret_cast<int4*>(out + k0) = make_int4(x0, x0 + f0, x0 + f0 + f1, x0 + f0 + f1 + f2);
-    } else {
-      const int x[4] = {x0, x0 + f0, x0 + f0 + f1, x0 + f0 + f1 + f2};
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (k0 + i < len) out[k0 + i] = x[i];
-    }
+    const int x0 = a.bsum[s][b] + block_scan_excl(f[0] + f[1] + f[2] + f[3], lds, total);
+    store4_excl(a.pre[s], k0, len, x0, f);
   }
 }
 
@@ -300,7 +243,6 @@ __global__ __launch_bounds__(kBlock) void ind_fill_k(IndFill a, int64_t groups) 
 
 using namespace gnm;
 
-static inline size_t ind_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
 static inline int64_t ind_blocks(int64_t n) { return (n + kIndBlk - 1) / kIndBlk; }
 
 // ws: the five prefix arrays (int32), the five flag arrays (bytes), the five block-sum arrays (int32); each 16-byte aligned
@@ -310,9 +252,9 @@ struct IndLayout {
 static IndLayout ind_layout(int64_t N, int64_t E) {
   IndLayout l;
   size_t off = 0;
-  for (int s = 0; s < kIndSeqs; ++s) { l.pre[s] = off; off += ind_pad((size_t)(s < 2 ? N : E) * sizeof(int32_t)); }
-  for (int s = 0; s < kIndSeqs; ++s) { l.flag[s] = off; off += ind_pad((size_t)(s < 2 ? N : E)); }
-  for (int s = 0; s < kIndSeqs; ++s) { l.bsum[s] = off; off += ind_pad((size_t)ind_blocks(s < 2 ? N : E) * sizeof(int32_t)); }
+  for (int s = 0; s < kIndSeqs; ++s) { l.pre[s] = off; off += ws_pad((size_t)(s < 2 ? N : E) * sizeof(int32_t)); }
+  for (int s = 0; s < kIndSeqs; ++s) { l.flag[s] = off; off += ws_pad((size_t)(s < 2 ? N : E)); }
+  for (int s = 0; s < kIndSeqs; ++s) { l.bsum[s] = off; off += ws_pad((size_t)ind_blocks(s < 2 ? N : E) * sizeof(int32_t)); }
   l.bytes = off;
   return l;
 }

@@ -10,7 +10,7 @@
 // from removing each other through one another (b -> c and c -> b may both exist) and what spares a node's out-edge of uniquely
 // smallest prefix.
 //
-// Kernel.  The decision kernel's layout: eight lanes per source node a; the lanes stride over the positions p of a's by-source row
+// Kernel.  Eight lanes per source node a (gnm_group.h); the lanes stride over the positions p of a's by-source row
 // (edge k), and every lane walks the whole row again (position q, edge j).  All eight lanes meet the same j in the same order, so
 // its loads are broadcasts and the branch on "j is a candidate" is group-uniform; the lanes differ in c alone.  The out-rows are
 // stored by ascending internal position, i.e. by ascending internal destination inside a row: "a candidate b -> c exists" is a
@@ -25,19 +25,17 @@
 // Bounds.  Row pointers are clamped to 0 <= lo <= hi <= E; a position or edge id outside [0, E) and a destination outside [0, n)
 // drop the edge (it is not counted and nothing is written for it) or the witness before they address anything.
 #include "gnm_common.h"
+#include "gnm_group.h"
 #include "gnm_key.h"
 
 namespace gnm {
 
-constexpr int kRedLanes = 8;                            // lanes per source node: the decision kernel's layout
-constexpr int kRedNodes = kBlock / kRedLanes;           // nodes per workgroup and pass
 enum { kRedEdges = 0, kRedCandidates, kRedReduced, kRedLabel1, kRedSelfLoops, kRedCounters };   // the 32-bit thread counters
 // the record's words: edges, candidates, reduced, reduced_label1, witnesses, max_support, self_loops, calls
 enum { kRecEdges = 0, kRecCandidates, kRecReduced, kRecLabel1, kRecWitnesses, kRecMaxSupport, kRecSelfLoops, kRecCalls };
 
 struct RedArgs {
-  int64_t n, E;
-  const int32_t *perm, *out_ptr, *out_pos, *out_dst;
+  IndexRows ix;                                         // the by-source half of it is all this reads
   const float *scores, *y;
   const int64_t* pl;
   float min_logit;
@@ -48,28 +46,19 @@ struct RedArgs {
 
 __device__ __forceinline__ bool red_candidate_(const RedArgs& a, float s) { return dec_key_(s) != 0u && s >= a.min_logit; }
 
-// the row of node v, clamped
-__device__ __forceinline__ void red_row_(const RedArgs& a, int v, int& lo, int& hi) {
-  const int E = (int)a.E;
-  lo = a.out_ptr[v];
-  hi = a.out_ptr[v + 1];
-  lo = lo < 0 ? 0 : (lo > E ? E : lo);
-  hi = hi < lo ? lo : (hi > E ? E : hi);
-}
-
 // Is there a candidate edge m = (b -> c) -- and, with fuzz >= 0, one with |pj + pl[m] - pk| <= fuzz?
 __device__ __forceinline__ bool red_closes_(const RedArgs& a, int b, int c, int64_t pj, int64_t pk) {
-  const unsigned E = (unsigned)a.E;
+  const unsigned E = (unsigned)a.ix.E;
   int lo, end;
-  red_row_(a, b, lo, end);
+  row_clamped(a.ix.out_ptr, b, (int)a.ix.E, lo, end);
   for (int hi = end; lo < hi;) {                        // lower bound of c in the ascending destinations of b's row
     const int mid = lo + ((hi - lo) >> 1);
-    if (a.out_dst[mid] < c) lo = mid + 1; else hi = mid;
+    if (a.ix.out_dst[mid] < c) lo = mid + 1; else hi = mid;
   }
-  for (int t = lo; t < end && a.out_dst[t] == c; ++t) {
-    const int jm = a.out_pos[t];
+  for (int t = lo; t < end && a.ix.out_dst[t] == c; ++t) {
+    const int jm = a.ix.out_pos[t];
     if ((unsigned)jm >= E) continue;
-    const int em = a.perm[jm];
+    const int em = a.ix.perm[jm];
     if ((unsigned)em >= E) continue;
     if (!red_candidate_(a, a.scores[em])) continue;
     if (a.fuzz < 0) return true;
@@ -91,68 +80,55 @@ __global__ __launch_bounds__(kBlock) void transitive_support_k(RedArgs a, unsign
   for (int k = 0; k < kRedCounters; ++k) cnt[k] = 0u;
   unsigned long long witnesses = 0ull;
   unsigned max_support = 0u;
-  const unsigned E = (unsigned)a.E, n = (unsigned)a.n;
-  const int sub = threadIdx.x & (kRedLanes - 1), grp = threadIdx.x / kRedLanes;
-  for (int64_t base = (int64_t)blockIdx.x * kRedNodes; base < a.n; base += (int64_t)gridDim.x * kRedNodes) {
+  const unsigned E = (unsigned)a.ix.E, n = (unsigned)a.ix.n;
+  const int sub = threadIdx.x & (kGroupLanes - 1), grp = threadIdx.x / kGroupLanes;
+  for (int64_t base = (int64_t)blockIdx.x * kGroupNodes; base < a.ix.n; base += (int64_t)gridDim.x * kGroupNodes) {
     const int64_t i64 = base + grp;
-    if (i64 >= a.n) continue;                           // no shuffle inside the loop: an idle group may leave
+    if (i64 >= a.ix.n) continue;                        // no shuffle inside the loop: an idle group may leave
     const int i = (int)i64;
     int lo, hi;
-    red_row_(a, i, lo, hi);
-    for (int p = lo + sub; p < hi; p += kRedLanes) {
-      const int c = a.out_dst[p], jk = a.out_pos[p];
-      if ((unsigned)c >= n || (unsigned)jk >= E) continue;             // outside the index: the edge is dropped
-      const int ek = a.perm[jk];
-      if ((unsigned)ek >= E) continue;
-      const float sk = a.scores[ek];
-      cnt[kRedEdges] += 1u;
-      unsigned sup = 0u;
-      bool cand = false;
-      if (c == i) {
-        cnt[kRedSelfLoops] += 1u;
-      } else {
-        cand = red_candidate_(a, sk);
-        const int64_t pk = a.pl[ek];
-        for (int q = lo; q < hi; ++q) {
-          const int b = a.out_dst[q], jj = a.out_pos[q];
-          if (b == i || b == c || (unsigned)b >= n || (unsigned)jj >= E) continue;
-          const int ej = a.perm[jj];
-          if ((unsigned)ej >= E) continue;
-          const int64_t pj = a.pl[ej];
-          if (!(pj < pk) || !red_candidate_(a, a.scores[ej])) continue;
-          if (red_closes_(a, b, c, pj, pk)) sup += 1u;
-        }
-      }
-      const bool reduced = cand && sup > 0u;
-      a.support[ek] = (int32_t)sup;
-      if (a.masked) a.masked[ek] = reduced ? __uint_as_float(0x7fc00000u) : sk;
-      cnt[kRedCandidates] += cand ? 1u : 0u;
-      cnt[kRedReduced] += reduced ? 1u : 0u;
-      cnt[kRedLabel1] += (reduced && a.y && a.y[ek] == 1.0f) ? 1u : 0u;
-      witnesses += sup;
-      max_support = sup > max_support ? sup : max_support;
-    }
+    row_clamped(a.ix.out_ptr, i, (int)E, lo, hi);
+    walk_candidates<0>(
+        a.ix, lo + sub, hi, [&](int c) { return (unsigned)c < n; },    // outside the index: the edge is dropped
+        [&](int, int, int c, int ek) {
+          const float sk = a.scores[ek];
+          cnt[kRedEdges] += 1u;
+          unsigned sup = 0u;
+          bool cand = false;
+          if (c == i) {
+            cnt[kRedSelfLoops] += 1u;
+          } else {
+            cand = red_candidate_(a, sk);
+            const int64_t pk = a.pl[ek];
+            for (int q = lo; q < hi; ++q) {
+              const int b = a.ix.out_dst[q], jj = a.ix.out_pos[q];
+              if (b == i || b == c || (unsigned)b >= n || (unsigned)jj >= E) continue;
+              const int ej = a.ix.perm[jj];
+              if ((unsigned)ej >= E) continue;
+              const int64_t pj = a.pl[ej];
+              if (!(pj < pk) || !red_candidate_(a, a.scores[ej])) continue;
+              if (red_closes_(a, b, c, pj, pk)) sup += 1u;
+            }
+          }
+          const bool reduced = cand && sup > 0u;
+          a.support[ek] = (int32_t)sup;
+          if (a.masked) a.masked[ek] = reduced ? __uint_as_float(0x7fc00000u) : sk;
+          cnt[kRedCandidates] += cand ? 1u : 0u;
+          cnt[kRedReduced] += reduced ? 1u : 0u;
+          cnt[kRedLabel1] += (reduced && a.y && a.y[ek] == 1.0f) ? 1u : 0u;
+          witnesses += sup;
+          max_support = sup > max_support ? sup : max_support;
+        });
   }
 #pragma unroll
   for (int k = 0; k < kRedCounters; ++k) {
-    unsigned v = cnt[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    const unsigned v = wave_sum(cnt[k]);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(&tot[k], v);
   }
   {
-    unsigned wl = (unsigned)witnesses, wh = (unsigned)(witnesses >> 32), m = max_support;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned long long o = ((unsigned long long)__shfl_xor(wh, off, 64) << 32) | __shfl_xor(wl, off, 64);
-      const unsigned long long s = (((unsigned long long)wh << 32) | wl) + o;
-      wl = (unsigned)s;
-      wh = (unsigned)(s >> 32);
-      const unsigned om = __shfl_xor(m, off, 64);
-      m = om > m ? om : m;
-    }
+    const unsigned long long s = wave_sum(witnesses);
+    const unsigned m = wave_max(max_support);
     if ((threadIdx.x & 63) == 0) {
-      const unsigned long long s = ((unsigned long long)wh << 32) | wl;
       if (s) atomicAdd(&wit, s);
       if (m) atomicMax(&tot[kRedCounters], m);
     }
@@ -177,23 +153,19 @@ extern "C" int gnm_transitive_support(int64_t n, int64_t E, const int32_t* perm,
                                       const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, const int32_t* nperm,
                                       const float* scores, const int64_t* prefix_length, const float* y, float min_logit, int64_t fuzz,
                                       int32_t* support, float* masked_scores, void* record, void* stream) {
-  (void)isrc; (void)in_ptr; (void)nperm;                // the index travels whole; the by-source half of it is all this reads
-  GNM_CHECK_ARG(n >= 0 && E >= 0 && n < INT32_MAX && E < INT32_MAX,
-                "transitive_support: n = %lld, E = %lld: expected 0 <= n, E < 2^31 - 1 (the index holds 32-bit positions)", (long long)n,
-                (long long)E);
+  if (index_size_check("transitive_support", n, E, "the index holds 32-bit positions")) return -1;
   GNM_CHECK_ARG(fuzz >= -1, "transitive_support: fuzz = %lld: expected -1 (no length test) or a length >= 0", (long long)fuzz);
-  GNM_CHECK_ARG(record && ((uintptr_t)record & 7) == 0, "transitive_support: record must be a non-null, 8-byte aligned gnm_reduce_record");
+  if (record_check("transitive_support", record, "gnm_reduce_record")) return -1;
   GNM_CHECK_ARG(n == 0 || out_ptr, "transitive_support: out_ptr must not be null when n > 0");
   GNM_CHECK_ARG(E == 0 || (perm && out_pos && out_dst && scores && prefix_length && support),
                 "transitive_support: perm, out_pos, out_dst, scores, prefix_length and support must not be null when E > 0");
   if (n == 0 || E == 0) return 0;                       // no edge: nothing to write, nothing launched, the record stays as it is
   RedArgs a;
-  a.n = n; a.E = E;
-  a.perm = perm; a.out_ptr = out_ptr; a.out_pos = out_pos; a.out_dst = out_dst;
+  a.ix = IndexRows{n, E, perm, isrc, in_ptr, out_ptr, out_pos, out_dst, nperm};
   a.scores = scores; a.y = y; a.pl = prefix_length;
   a.min_logit = min_logit; a.fuzz = fuzz;
   a.support = support; a.masked = masked_scores;
-  const int grid = persistent_grid(n, kRedNodes, 8);
+  const int grid = persistent_grid(n, kGroupNodes, 8);
   hipLaunchKernelGGL(transitive_support_k, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, (unsigned long long*)record);
   GNM_LAUNCH_CHECK("transitive_support");
   return 0;

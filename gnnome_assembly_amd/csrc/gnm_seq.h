@@ -22,6 +22,17 @@ struct SeqStore {            // the packed + strands: 4 bits per base, BAM code,
   int64_t nibbles, R, n;     // n: nodes of the graph; node v is read v >> 1, reversed and complemented when v is odd
 };
 
+#ifdef GNM_CHECK_ARG         // inside the library (gnm_common.h came first): the store's part of an entry point's argument check
+inline int seq_store_check(const char* what, int64_t n, int64_t R, const int64_t* base_off, const int64_t* length, int64_t packed_bytes) {
+  GNM_CHECK_ARG(n >= 0 && R >= 0 && n < INT32_MAX && R < INT32_MAX, "%s: n = %lld, R = %lld: expected 0 <= n, R < 2^31 - 1", what,
+                (long long)n, (long long)R);
+  GNM_CHECK_ARG(packed_bytes >= 0 && packed_bytes % 16 == 0 && packed_bytes <= (INT64_MAX >> 2),
+                "%s: packed_bytes = %lld: the store is whole 16-byte groups", what, (long long)packed_bytes);
+  GNM_CHECK_ARG(R == 0 || (base_off && length), "%s: base_off and length must not be null when R > 0", what);
+  return 0;
+}
+#endif
+
 struct SeqSrc {              // where the bases of one piece come from
   int64_t first, len;        // nibble index of the read's first base, the read's length
   int rev, ok;               // ok == 0: the node does not name a read that lies inside the store; nothing is read through it

@@ -4,7 +4,7 @@
 // gnm_seq_layout, four launches on one stream:
 //   seq_len_k     piece_len[p] of every walk position (the position's contig by binary search in contig_ptr, the node, read and
 //                 edge checked before they address anything), the sum of every block of kBlock positions, the counters.
-//   seq_scan_k    ONE workgroup: the block sums -> their exclusive prefix, in place (gnm_induce.hip's ind_scan_k, in int64);
+//   seq_scan_k    ONE workgroup: the block sums -> their exclusive prefix, in place (gnm_group.h's scan_block_sums, in int64);
 //                 piece_off[P] = the total; record: contigs, pieces, bases, calls.
 //   seq_apply_k   piece_off[p] = block prefix + in-block exclusive scan of piece_len.
 //   seq_cptr_k    contig_base_ptr[c] = piece_off[contig_ptr[c]].
@@ -15,6 +15,7 @@
 // No workgroup waits for another, nothing is read back between the launches, no float arithmetic; integer atomics on the record
 // words only (one per counter and workgroup): bytes and record depend on the inputs alone, not on the grid or on timing.
 #include "gnm_common.h"
+#include "gnm_group.h"
 #include "gnm_seq.h"
 
 namespace gnm {
@@ -32,42 +33,6 @@ struct SeqArgs {
   uint8_t* out;
 };
 
-// The workgroup's sum of v, added to *word by one atomic (none when it is 0).  Every thread of the workgroup calls it.
-__device__ __forceinline__ void seq_count_(unsigned v, unsigned* lds, unsigned long long* word) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned t = lds[0] + lds[1] + lds[2] + lds[3];
-    if (t) atomicAdd(word, (unsigned long long)t);
-  }
-  __syncthreads();
-}
-
-// Exclusive scan of one int64 per thread over the workgroup, in thread order; `total` = the workgroup's sum.
-__device__ __forceinline__ int64_t seq_block_scan_(int64_t v, int64_t* lds, int64_t& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const long long o = __shfl_up(x, off, 64);
-    if (lane >= off) x += o;
-  }
-  if (lane == 63) lds[wave] = x;
-  __syncthreads();
-  int64_t before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kWavesPerBlock; ++w) {
-    const int64_t t = lds[w];
-    before += w < wave ? t : 0;
-    total += t;
-  }
-  __syncthreads();
-  return before + x - v;
-}
-
 __global__ __launch_bounds__(kBlock) void seq_len_k(SeqArgs a) {
   __shared__ int64_t lds64[kWavesPerBlock];
   __shared__ unsigned lds[kWavesPerBlock];
@@ -84,30 +49,19 @@ __global__ __launch_bounds__(kBlock) void seq_len_k(SeqArgs a) {
       invalid += (f >> 2) & 1u;
       empty += (k == 0 && !(f & 4u)) ? 1u : 0u;
     }
-    int64_t total;
-    seq_block_scan_(k, lds64, total);
+    const int64_t total = block_sum(k, lds64);
     if (threadIdx.x == 0) a.bsum[b] = total;
   }
-  seq_count_(clamped, lds, a.rec + kSeqClamped);
-  seq_count_(empty, lds, a.rec + kSeqEmpty);
-  seq_count_(reverse, lds, a.rec + kSeqReverse);
-  seq_count_(invalid, lds, a.rec + kSeqInvalid);
+  block_count_add(clamped, lds, a.rec + kSeqClamped);
+  block_count_add(empty, lds, a.rec + kSeqEmpty);
+  block_count_add(reverse, lds, a.rec + kSeqReverse);
+  block_count_add(invalid, lds, a.rec + kSeqInvalid);
 }
 
 __global__ __launch_bounds__(kBlock) void seq_scan_k(SeqArgs a) {
   __shared__ int64_t lds64[kWavesPerBlock];
-  const int64_t chunk = (a.nb + kBlock - 1) / kBlock;
-  const int64_t b0 = (int64_t)threadIdx.x * chunk < a.nb ? (int64_t)threadIdx.x * chunk : a.nb;
-  const int64_t b1 = b0 + chunk < a.nb ? b0 + chunk : a.nb;
-  int64_t t = 0;
-  for (int64_t b = b0; b < b1; ++b) t += a.bsum[b];
   int64_t total;
-  int64_t run = seq_block_scan_(t, lds64, total);
-  for (int64_t b = b0; b < b1; ++b) {
-    const int64_t v = a.bsum[b];
-    a.bsum[b] = run;
-    run += v;
-  }
+  scan_block_sums(a.bsum, a.nb, lds64, total);
   if (threadIdx.x == 0) {
     a.piece_off[a.P] = total;
     if (a.C > 0) atomicAdd(a.rec + kSeqContigs, (unsigned long long)a.C);
@@ -122,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void seq_apply_k(SeqArgs a) {
   for (int64_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
     const int64_t p = b * kBlock + threadIdx.x;
     int64_t total;
-    const int64_t x = a.bsum[b] + seq_block_scan_(p < a.P ? a.piece_len[p] : 0, lds64, total);
+    const int64_t x = a.bsum[b] + block_scan_excl<int64_t>(p < a.P ? a.piece_len[p] : 0, lds64, total);
     if (p < a.P) a.piece_off[p] = x;
   }
 }
@@ -171,22 +125,11 @@ __global__ __launch_bounds__(kBlock) void seq_emit_k(SeqArgs a) {
 
 using namespace gnm;
 
-static inline size_t seq_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
-
 static_assert(kSeqChunkBases == GNM_SEQ_CHUNK_BASES, "include/gnm.h states the chunk size");
 
 extern "C" size_t gnm_seq_workspace_bytes(int64_t P) {
   if (P < 0 || P >= INT32_MAX) return 0;
-  return seq_pad((size_t)((P + kBlock - 1) / kBlock) * 8);
-}
-
-static int seq_store_check(const char* what, int64_t n, int64_t R, const int64_t* base_off, const int64_t* length, int64_t packed_bytes) {
-  GNM_CHECK_ARG(n >= 0 && R >= 0 && n < INT32_MAX && R < INT32_MAX, "%s: n = %lld, R = %lld: expected 0 <= n, R < 2^31 - 1", what,
-                (long long)n, (long long)R);
-  GNM_CHECK_ARG(packed_bytes >= 0 && packed_bytes % 16 == 0 && packed_bytes <= (INT64_MAX >> 2),
-                "%s: packed_bytes = %lld: the store is whole 16-byte groups", what, (long long)packed_bytes);
-  GNM_CHECK_ARG(R == 0 || (base_off && length), "%s: base_off and length must not be null when R > 0", what);
-  return 0;
+  return ws_pad((size_t)((P + kBlock - 1) / kBlock) * 8);
 }
 
 extern "C" int gnm_seq_layout(int64_t C, int64_t P, int64_t E, int64_t n, int64_t R, const int32_t* contig_ptr,
@@ -196,13 +139,12 @@ extern "C" int gnm_seq_layout(int64_t C, int64_t P, int64_t E, int64_t n, int64_
   GNM_CHECK_ARG(C >= 0 && P >= 0 && E >= 0 && C < INT32_MAX && P < INT32_MAX && E < INT32_MAX,
                 "seq_layout: C = %lld, P = %lld, E = %lld: expected 0 <= C, P, E < 2^31 - 1", (long long)C, (long long)P, (long long)E);
   if (seq_store_check("seq_layout", n, R, base_off, length, packed_bytes)) return -1;
-  GNM_CHECK_ARG(record && ((uintptr_t)record & 7) == 0, "seq_layout: record must be a non-null, 8-byte aligned gnm_seq_record");
+  if (record_check("seq_layout", record, "gnm_seq_record")) return -1;
   GNM_CHECK_ARG(contig_ptr && piece_off && contig_base_ptr, "seq_layout: contig_ptr, piece_off and contig_base_ptr must not be null");
   GNM_CHECK_ARG(P == 0 || (walk_nodes && walk_edges && piece_len), "seq_layout: walk_nodes, walk_edges and piece_len must not be null when P > 0");
   GNM_CHECK_ARG(E == 0 || prefix_length, "seq_layout: prefix_length must not be null when E > 0");
   const size_t need = gnm_seq_workspace_bytes(P);
-  GNM_CHECK_ARG(need == 0 || (ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0),
-                "seq_layout: workspace of %zu bytes too small (gnm_seq_workspace_bytes: %zu), null or not 16-byte aligned", ws_bytes, need);
+  if (ws_check("seq_layout", "gnm_seq_workspace_bytes", ws, ws_bytes, need)) return -1;
   hipStream_t st = (hipStream_t)stream;
   SeqArgs a = {};
   a.s.packed = nullptr; a.s.base_off = base_off; a.s.length = length; a.s.nibbles = packed_bytes * 2; a.s.R = R; a.s.n = n;

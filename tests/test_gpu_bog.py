@@ -130,7 +130,7 @@ def test_no_edges(lib, n):
 
 
 # ---- 2. single paths and single cycles at the round count's edges -----------------------------------------------------------------------
-@pytest.mark.parametrize("n", [2, 3, 1024, 1025, 4097])
+@pytest.mark.parametrize("n", [2, 3, 1024, 1025, 4097, 256 * 1024 + 5])     # the last: 257 scan blocks, two block sums per thread
 def test_one_path_with_permuted_ids(lib, n):
     case = _chain(n, seed=n)
     c, got = _check(case, f"path/{n}")

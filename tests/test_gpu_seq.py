@@ -120,6 +120,18 @@ def test_empty_pieces_first_last_inner_and_in_runs(lib, B):
     assert cs.record.empty >= 20
 
 
+def test_more_scan_blocks_than_threads(lib):
+    """P = 256 * 256 + 3 pieces of one to three bases in one contig: 257 block sums, so a thread of the scan workgroup owns two of
+    them, the last threads own none and the last block holds three pieces."""
+    rng = np.random.default_rng(14)
+    reads = _reads(14, rng.integers(3, 7, 40))
+    P = 256 * 256 + 3
+    walk = rng.integers(0, 2 * len(reads), P).tolist()
+    wedges = [-1] + rng.integers(0, 3, P - 1).tolist()
+    cs = _check([walk], [wedges], [1, 2, 3], reads, "P = 256 * 256 + 3")
+    assert cs.record.pieces == P and cs.record.clamped == 0 and cs.record.empty == 0
+
+
 def test_a_contig_of_one_node_and_empty_contigs(lib):
     reads = _reads(6, [33, 0, 18])
     cs = _check([[4], [], [2], [3], [1, 5]], [[-1], [], [-1], [-1], [-1, 0]], [9], reads, "one node / empty")
