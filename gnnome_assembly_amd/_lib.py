@@ -148,6 +148,10 @@ SIGNATURES = {
     "gnm_decode_walk_edges": (_i32, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p]),
     "gnm_transitive_support": (_i32, [_i64, _i64] + [_p] * 10 + [_f32, _i64] + [_p] * 4),
     "gnm_overlap_align": (_i32, [_i64] + [_p] * 4 + [_i64, _p, _p, _i64, _i64, _i32] + [_p] * 5),
+    "gnm_resolve_workspace_bytes": (_sz, [_i64] * 3),
+    "gnm_resolve_prepare": (_i32, [_i64] * 4 + [_p] * 4 + [_i64] + [_p] * 2 + [_sz, _p]),
+    "gnm_resolve_rounds": (_i32, [_i64] * 4 + [_p] * 4 + [_i64] * 3 + [_p] * 3 + [_sz, _p]),
+    "gnm_resolve_layout": (_i32, [_i64] * 4 + [_p] * 4 + [_i64] + [_p] * 10 + [_sz, _p]),
     "gnm_overlap_align_host": (_i32, [_i64] + [_p] * 4 + [_i64, _p, _p, _i64, _i64, _i32] + [_p] * 4 + [_i32]),
 }
 

@@ -33,6 +33,9 @@ free partner: the greedy path cover of overlap-layout assemblers, of which `best
 (the string-graph reduction); with reduce_transitive=True the two cover decoders run on the scores with those edges masked out, so
 that a link cannot jump over reads and leave them to a parallel contig.
 
+`resolve_strands_device` is `resolve_strands` on the device (gnm_resolve_prepare / _rounds / _layout): the same pieces in the same
+order, as a `BogContigs` that `contig_sequences` and `junction_identity` take as it is.
+
 `contig_sequences` turns the walks of any of the decoders into bases on the device over a packed `reads.ReadStore`
 (gnm_seq_layout / gnm_seq_emit), `ContigSequences.write_fasta`, `ng50` and `quick_evaluation` are evaluate.py's FASTA and report."""
 from __future__ import annotations
@@ -50,7 +53,7 @@ from .engine import RecordStats
 
 __all__ = ["DecodeGraph", "sample_edges", "get_contigs", "get_contigs_device", "infer_contigs", "decision_table",
            "best_overlap_contigs", "greedy_cover_contigs", "BogContigs", "BogStats", "transitive_support", "TransitiveSupport",
-           "ReduceStats", "resolve_strands", "ResolvedContigs", "n50", "junction_identity", "JunctionIdentity",
+           "ReduceStats", "resolve_strands", "ResolvedContigs", "resolve_strands_device", "StrandContigs", "ResolveStats", "n50", "junction_identity", "JunctionIdentity",
            "contig_sequences", "ContigSequences", "SeqStats", "walk_edge_ids", "ng50", "quick_evaluation", "CHR_LENGTHS"]
 
 
@@ -578,6 +581,104 @@ def resolve_strands(contigs: BogContigs, len_threshold: int = 20) -> ResolvedCon
     return ResolvedContigs(walks, bases)
 
 
+# ---- one strand per read on the device (gnm_resolve.hip) ----------------------------------------------------------------------------
+@dataclass
+class ResolveStats(RecordStats):
+    """A gnm_resolve_record (include/gnm.h): contigs (given), eligible (of at least len_threshold nodes), pieces (kept), dropped
+    (non-empty pieces below the threshold), nodes (on the kept pieces), serial (eligible contigs that hold both strands of a read:
+    cut by one lane), invalid (positions, contig_ptr rows and order entries that failed the input check), calls."""
+    contigs: int = 0
+    eligible: int = 0
+    pieces: int = 0
+    dropped: int = 0
+    nodes: int = 0
+    serial: int = 0
+    invalid: int = 0
+    calls: int = 0
+
+
+class StrandContigs(BogContigs):
+    """resolve_strands_device's result: the kept pieces as a BogContigs of their own, on the device, in the order resolve_strands
+    keeps them (walk_edges is -1 at every piece's first node).  `stats`: ResolveStats; `rounds`: the rounds the rule took."""
+
+    def __init__(self, contig_ptr, walk_nodes, walk_edges, bases, wrong, stats: ResolveStats, prefix_length, read_length, rounds: int):
+        super().__init__(contig_ptr, walk_nodes, walk_edges, bases, wrong, stats, prefix_length, read_length)
+        self.rounds = rounds
+
+    def resolved(self) -> ResolvedContigs:
+        """The pieces in resolve_strands' own format (lists on the host), for comparison with it."""
+        return ResolvedContigs(self.walks(), [int(b) for b in self.host()["bases"].tolist()])
+
+
+RESOLVE_CHECK_EVERY = 4    # rounds per chunk of resolve_strands_device: one read-back of the chunk's undecided counts
+
+
+def resolve_strands_device(contigs: BogContigs, len_threshold: int = 20, y=None, check_every: int = RESOLVE_CHECK_EVERY
+                           ) -> StrandContigs:
+    """resolve_strands on the device: the same pieces, in the same order, with the same bases -- as a StrandContigs, so that
+    contig_sequences, junction_identity, .walks(), .n50() and .longest() take the result where it is.
+    The rule runs in rounds (gnm_resolve_rounds): the contigs are ordered by a stable descending sort of `bases` (ascending contig
+    index among equals, resolve_strands' key); a contig is cut once every contig that holds the other strand of one of its reads
+    and comes earlier in that order is finished, so a contig and its reverse complement take two rounds and all contigs that share no
+    read are cut side by side.  A contig that holds both strands of some read is cut by one lane (stats.serial counts them).
+    `contigs`: a BogContigs on a HIP device whose nodes occur once each (a path cover); `y` [E] (optional): the labels, for `wrong`.
+    The rounds run in chunks of `check_every`; the synchronisations are one read of a chunk's counts per chunk and the read of the
+    record.  A node or edge id out of range, or a node listed twice, raises GnmError with `.record` (ResolveStats) set; nothing is
+    written then.  No contig, or none of len_threshold nodes, gives zero-length tensors.
+    The result's tensors are leading slices of buffers laid out for all P input positions before the kept pieces are counted, so
+    the result keeps 24 bytes per INPUT position alive (36 MB at 1.5 M positions) however few nodes it keeps; `.clone()` the five
+    tensors to hold on to a small result for long."""
+    from . import engine
+    if not isinstance(check_every, (int, np.integer)) or isinstance(check_every, bool) or check_every < 1:
+        raise ValueError(f"resolve_strands_device: check_every={check_every!r}: expected an integer >= 1")
+    if not isinstance(contigs, BogContigs):
+        raise TypeError("resolve_strands_device: contigs must be a BogContigs")
+    dev = contigs.walk_nodes.device
+    if dev.type != "cuda":
+        raise _lib.GnmError("resolve_strands_device: the contigs must be on a HIP device (no CPU fallback; resolve_strands is the "
+                            "host route)")
+    thr = max(1, int(len_threshold))
+    i32c = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()  # noqa: E731
+    C = len(contigs)
+    contig_ptr, walk_nodes = i32c(contigs.contig_ptr[:C + 1]), i32c(contigs.walk_nodes)
+    P = int(walk_nodes.numel())
+    walk_edges = i32c(contigs.walk_edges[:P])
+    pl = contigs.prefix_length.to(device=dev, dtype=torch.int64).contiguous()
+    rl = contigs.read_length.to(device=dev, dtype=torch.int64).contiguous()
+    n, E = int(rl.numel()), int(pl.numel())
+    with torch.cuda.device(dev):
+        order = i32c(torch.sort(contigs.bases[:C].to(dev), descending=True, stable=True).indices)
+        cover = (contig_ptr, walk_nodes, walk_edges, order)
+        rec = torch.zeros(engine.RESOLVE_RECORD_WORDS, dtype=torch.int64, device=dev)
+        ws = torch.empty(engine.resolve_workspace_bytes(C, P, n), dtype=torch.uint8, device=dev)
+        engine.resolve_prepare(cover, n, E, thr, rec, ws)
+        rounds, left = 0, 1
+        while left > 0:
+            if rounds > C:                                             # every round finishes a contig: cannot happen
+                raise _lib.GnmError(f"resolve_strands_device: {left} contigs still undecided after {rounds} rounds")
+            chunk = torch.empty(int(check_every), dtype=torch.int64, device=dev)
+            engine.resolve_rounds(cover, n, E, thr, chunk, rec, ws, rounds)
+            for left in chunk.cpu().tolist():                          # the loop's one synchronisation per chunk
+                rounds += 1
+                if left <= 0:
+                    break
+        if left < 0:
+            stats = ResolveStats.from_record(rec)
+            err = _lib.GnmError(f"resolve_strands_device: {stats.invalid} walk positions or order entries name a node or edge that "
+                                f"is out of range or listed twice (cover of {C} contigs and {P} positions, graph of {n} nodes and "
+                                f"{E} edges)")
+            err.record = stats
+            raise err
+        out_ptr = torch.empty(P + 1, dtype=torch.int32, device=dev)
+        out_nodes, out_edges, out_wrong = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+        out_bases = torch.empty(P, dtype=torch.int64, device=dev)
+        engine.resolve_layout(cover, n, E, thr, pl, rl, y if y is None else y.to(dev), rec, out_ptr, out_nodes, out_edges, out_bases,
+                              out_wrong, ws)
+        stats = ResolveStats.from_record(rec)
+    K, N = stats.pieces, stats.nodes
+    return StrandContigs(out_ptr[:K + 1], out_nodes[:N], out_edges[:N], out_bases[:K], out_wrong[:K], stats, pl, rl, rounds)
+
+
 # ---- contig sequences: walks + a packed read store -> bases, FASTA, N50 / NG50 (evaluate.py) ------------------------------------------
 # evaluate.py:9-33, retyped: the chromosome lengths quick_evaluation divides by
 CHR_LENGTHS = {
@@ -835,7 +936,8 @@ def junction_identity(contigs, graph, reads, max_errors: int = 255, prefix_lengt
 
 def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int = 50, len_threshold: int = 20,
                   device_sampling: bool = False, decision_report: bool = False, decoder: str = "greedy", reads=None,
-                  reduce_transitive: bool = False, fuzz: Optional[int] = None, junction_report: bool = False):
+                  reduce_transitive: bool = False, fuzz: Optional[int] = None, junction_report: bool = False,
+                  device_resolve: bool = False):
     """The per-graph body of inference.inference (inference.py:444-490): logits of the whole graph under
     no_grad in eval mode, stored by edge id, then greedy decode.  Returns (scores [E], walks).
     device_sampling=True: the logits stay on the device for `get_contigs_device` (same distribution of start edges,
@@ -850,7 +952,15 @@ def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int
     reduce_transitive, fuzz: handed to best_overlap_contigs / greedy_cover_contigs (the string-graph reduction ahead of the cover).
     The sampled decoder refuses reduce_transitive=True: its walks already absorb the nodes they jump over.
     junction_report=True (needs reads): junction_identity(walks, graph, reads, prefix_length=prefix_length) -- per contig the
-    junctions, their summed edit distance and how many exceed the band -- is appended behind the sequences, as the LAST element."""
+    junctions, their summed edit distance and how many exceed the band -- is appended behind the sequences, as the LAST element.
+    device_resolve=True (cover decoders only): the strand rule runs on the device (resolve_strands_device): the walks are its
+    .walks() -- the same lists -- and, with reads, the sequences and the junction report are computed from its device CSR directly,
+    without looking the edge ids up on the host again.  False (the default) is resolve_strands on the host."""
+    if not isinstance(device_resolve, (bool, np.bool_)):
+        raise ValueError(f"infer_contigs: device_resolve={device_resolve!r}: expected True or False")
+    if device_resolve and decoder == "greedy":
+        raise ValueError("infer_contigs: device_resolve=True with decoder='greedy': the sampled walks keep one strand per read "
+                         "themselves; the strand rule belongs to decoder='best_overlap' and 'greedy_cover'")
     if junction_report and reads is None:
         raise ValueError("infer_contigs: junction_report=True needs reads (a ReadStore on the graph's device)")
     if decoder not in ("greedy", "best_overlap", "greedy_cover"):
@@ -866,8 +976,13 @@ def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int
     if decoder in ("best_overlap", "greedy_cover"):
         cover = best_overlap_contigs if decoder == "best_overlap" else greedy_cover_contigs
         extra = dict(reduce_transitive=True, fuzz=fuzz) if reduce_transitive else {}
-        walks = resolve_strands(cover(graph, scores, prefix_length, read_length, getattr(graph, "edata", {}).get("y"), **extra),
-                                len_threshold).walks
+        labels = getattr(graph, "edata", {}).get("y")
+        covered = cover(graph, scores, prefix_length, read_length, labels, **extra)
+        if device_resolve:
+            on_device = resolve_strands_device(covered, len_threshold, labels)
+            walks = on_device.walks()
+        else:
+            walks = resolve_strands(covered, len_threshold).walks
         walk_graph = graph
     else:
         walk_graph = _as_decode_graph(graph)                           # built once: the walks and contig_sequences share it
@@ -875,7 +990,8 @@ def infer_contigs(model, graph, e, pe, prefix_length, read_length, nb_paths: int
         walks = sampled(walk_graph, scores, prefix_length, read_length, nb_paths, len_threshold)
     result = (scores, walks, report) if decision_report else (scores, walks)
     if reads is not None:
-        result += (contig_sequences(walks, walk_graph, reads, prefix_length),)
+        laid_out = on_device if device_resolve else walks              # the device CSR as it is, or lists of node ids
+        result += (contig_sequences(laid_out, walk_graph, reads, prefix_length),)
         if junction_report:
-            result += (junction_identity(walks, graph, reads, prefix_length=prefix_length),)
+            result += (junction_identity(laid_out, graph, reads, prefix_length=prefix_length),)
     return result

@@ -2410,6 +2410,78 @@ def cover_workspace_bytes(n: int) -> int:
     return int(_lib.load().gnm_cover_workspace_bytes(int(n)))
 
 
+RESOLVE_COUNTERS = ("contigs", "eligible", "pieces", "dropped", "nodes", "serial", "invalid", "calls")
+RESOLVE_RECORD_WORDS = len(RESOLVE_COUNTERS)  # the int64 words of a gnm_resolve_record (include/gnm.h), in order
+
+
+def resolve_workspace_bytes(C: int, P: int, n: int) -> int:
+    """gnm_resolve_workspace_bytes: the bytes of state the three resolve_* calls share for C contigs of P positions over n nodes."""
+    return int(_lib.load().gnm_resolve_workspace_bytes(int(C), int(P), int(n)))
+
+
+def _resolve_head(fn: str, cover, n: int, E: int, len_threshold: int, record, ws, *more):
+    """The arguments the three resolve_* wrappers share, checked: cover = (contig_ptr [C+1], walk_nodes [P], walk_edges [P], order
+    [C]) int32; returns the leading arguments of the entry point and the trailing (ws, bytes, stream)."""
+    contig_ptr, walk_nodes, walk_edges, order = cover
+    _chk_dev(contig_ptr, walk_nodes, walk_edges, order, record, ws, *more)
+    nc, P = int(contig_ptr.numel()) - 1, int(walk_nodes.numel())
+    if nc < 0:
+        raise ValueError(f"{fn}: contig_ptr is empty: expected C + 1 entries, at least the leading 0")
+    if isinstance(len_threshold, bool) or not hasattr(len_threshold, "__index__") or operator.index(len_threshold) < 1:
+        raise ValueError(f"{fn}: len_threshold={len_threshold!r}: expected an integer >= 1")
+    _chk_record(fn, record, RESOLVE_RECORD_WORDS)
+    _chk_args(fn, ("contig_ptr", contig_ptr, torch.int32, nc + 1), ("walk_nodes", walk_nodes, torch.int32, P),
+              ("walk_edges", walk_edges, torch.int32, P), ("order", order, torch.int32, nc))
+    need = resolve_workspace_bytes(nc, P, n)
+    if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError(f"{fn}: ws must be a contiguous uint8 tensor of at least {need} bytes (resolve_workspace_bytes)")
+    head = (nc, P, int(n), int(E), _ptr(contig_ptr), _ptr(walk_nodes), _ptr(walk_edges), _ptr(order), operator.index(len_threshold))
+    return head, (_ptr(ws), int(ws.numel()), _stream())
+
+
+@on_device_of(lambda cover, n, E, len_threshold, record, ws: record)
+def resolve_prepare(cover, n, E, len_threshold, record, ws):
+    """Reset `ws`, check the cover and classify its contigs (gnm_resolve_prepare: 3 launches, no host synchronisation).  cover:
+    (contig_ptr, walk_nodes, walk_edges, order) contiguous int32 device tensors -- a BogContigs' CSR and the contigs in priority
+    order; n nodes, E edges; record: a contiguous int64 [RESOLVE_RECORD_WORDS] device tensor the call ADDS to; ws: a contiguous
+    uint8 tensor of at least resolve_workspace_bytes(C, P, n) bytes, kept for resolve_rounds and resolve_layout."""
+    head, tail = _resolve_head("resolve_prepare", cover, n, E, len_threshold, record, ws)
+    _call("gnm_resolve_prepare", *head, _ptr(record), *tail)
+
+
+@on_device_of(lambda cover, n, E, len_threshold, undecided, *a, **k: undecided)
+def resolve_rounds(cover, n, E, len_threshold, undecided, record, ws, first_round: int = 0):
+    """Rounds first_round .. first_round + len(undecided) - 1 of the strand rule on the state resolve_prepare left in `ws`
+    (gnm_resolve_rounds: one launch per round and one per call): undecided, a contiguous int64 [rounds] device tensor, receives
+    the contigs not finished after every round, -1 when resolve_prepare found the input invalid."""
+    if undecided.dtype != torch.int64 or undecided.dim() != 1 or not undecided.is_contiguous():
+        raise ValueError("resolve_rounds: undecided must be a contiguous int64 [rounds] tensor")
+    if int(first_round) < 0:
+        raise ValueError(f"resolve_rounds: first_round = {first_round}: expected >= 0")
+    head, tail = _resolve_head("resolve_rounds", cover, n, E, len_threshold, record, ws, undecided)
+    _call("gnm_resolve_rounds", *head, int(first_round), int(undecided.numel()), _ptr(undecided), _ptr(record), *tail)
+
+
+@on_device_of(lambda cover, n, E, len_threshold, prefix_length, read_length, y, record, *a, **k: record)
+def resolve_layout(cover, n, E, len_threshold, prefix_length, read_length, y, record, out_ptr, out_nodes, out_edges, out_bases,
+                   out_wrong, ws):
+    """The kept pieces of a finished resolve_rounds state as a cover of their own (gnm_resolve_layout: 5 launches, no host
+    synchronisation): out_ptr int32 [P+1], out_nodes, out_edges, out_wrong int32 [P], out_bases int64 [P], of which the first
+    K+1 / N / N / K / K entries are defined (record.pieces, record.nodes).  prefix_length [E], read_length [n] int64; y [E] labels
+    or None."""
+    P = int(cover[1].numel())
+    if y is not None:
+        y = _f32c(y.reshape(-1).float())
+    head, tail = _resolve_head("resolve_layout", cover, n, E, len_threshold, record, ws, prefix_length, read_length, y, out_ptr,
+                               out_nodes, out_edges, out_bases, out_wrong)
+    _chk_args("resolve_layout", ("prefix_length", prefix_length, torch.int64, int(E)), ("read_length", read_length, torch.int64, int(n)),
+              ("y", y, torch.float32, int(E)), ("out_ptr", out_ptr, torch.int32, P + 1), ("out_nodes", out_nodes, torch.int32, P),
+              ("out_edges", out_edges, torch.int32, P), ("out_bases", out_bases, torch.int64, P),
+              ("out_wrong", out_wrong, torch.int32, P), optional=("y",))
+    _call("gnm_resolve_layout", *head, _ptr(prefix_length), _ptr(read_length), _ptr(y), _ptr(record), _ptr(out_ptr), _ptr(out_nodes),
+          _ptr(out_edges), _ptr(out_bases), _ptr(out_wrong), *tail)
+
+
 REDUCE_COUNTERS = ("edges", "candidates", "reduced", "reduced_label1", "witnesses", "max_support", "self_loops", "calls")
 REDUCE_RECORD_WORDS = len(REDUCE_COUNTERS)  # the int64 words of a gnm_reduce_record (include/gnm.h), in order
 

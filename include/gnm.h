@@ -977,6 +977,52 @@ int gnm_overlap_align_host(int64_t E, const int32_t* src, const int32_t* dst, co
                            int64_t packed_bytes, const int64_t* base_off, const int64_t* length, int64_t R, int64_t n, int max_errors,
                            int32_t* dist, int64_t* overlap_length, float* similarity, void* record, int threads);
 
+/* ---- resolve strands: one strand per read over the contigs of a path cover -- all on the device ----------------------------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: four new symbols, no existing signature changes.)
+ * Nodes 2i and 2i+1 are the two strands of read i; a cover usually holds a contig and its reverse complement.  The rule (the
+ * host's decode.resolve_strands): the contigs are taken in the order `order` gives (descending bases, ascending contig index among
+ * equals); a contig of fewer than len_threshold nodes is never walked; a node whose read is taken ends the current piece and
+ * belongs to none; a piece of at least len_threshold nodes is kept and takes its reads, a shorter one is dropped and takes none; a
+ * read met twice inside one piece ends it too (kept: the node is skipped; dropped: the node starts the next piece).
+ * DEVICE pointers.  contig_ptr [C+1], walk_nodes [P], walk_edges [P]: the layout gnm_bog_contigs leaves; order int32 [C]: a
+ * permutation of the contigs, first contig first; prefix_length [E], read_length [n] int64; y [E] fp32 or NULL.
+ * Every node may occur at most ONCE in walk_nodes (a path cover).  Then taken[r] is written only by the contig of either strand
+ * of r, and the rule runs in rounds: a contig is READY when every contig that holds the other strand of one of its reads is the
+ * contig itself, comes later in `order`, or was finished in an earlier round; ready contigs share no read and are cut side by
+ * side, one wave each: ballots find the runs of free positions (the open run is carried across chunks of 64), a second pass keeps
+ * the runs of at least len_threshold.  A contig that holds both strands of some read is cut by one lane, by the rule as written.
+ * The first unfinished contig of `order` is always ready, so every round finishes at least one.
+ * gnm_resolve_prepare (3 launches): resets ws, checks the input, classifies the contigs.  record ADDS contigs (C), eligible,
+ *   serial (eligible contigs that hold both strands of a read), invalid, calls (+1).  INVALID: a contig_ptr row that does not
+ *   ascend inside [0, P], a node outside [0, n), an inner edge id outside [0, E), an order entry outside [0, C), and every
+ *   position (order entry) whose node (contig) is listed twice.  With invalid != 0 the later calls launch kernels that return at
+ *   once: nothing is written but undecided, which reads -1.
+ * gnm_resolve_rounds (1 + rounds launches): rounds first_round .. first_round + rounds - 1 on the state in ws; undecided[j]
+ *   (int64 [rounds]) = the eligible contigs not finished after round first_round + j (-1: invalid input).  The caller stops at the
+ *   first 0; a round on a finished state changes nothing.  record ADDS dropped (the non-empty pieces below the threshold).
+ * gnm_resolve_layout (5 launches), once the rounds have ended: the kept pieces, by the order of their contigs and then by
+ *   position, as a cover of their own -- out_ptr [K+1] (room for P+1), out_nodes, out_edges [N] (room for P; -1 at a piece's first
+ *   node), out_bases int64 [K] (the sum of prefix_length over the inner links + read_length of the last node), out_wrong [K] (inner
+ *   links with y != 1; 0 when y == NULL), room for P each.  record ADDS pieces (K), nodes (N): the caller reads them to size its views.
+ * ws: gnm_resolve_workspace_bytes(C, P, n) bytes, 16-byte aligned, the same for the three calls and untouched in between.
+ * Integers only; one integer atomic per workgroup and counter; no workgroup waits for another: outputs and record depend on the
+ * inputs alone, not on the grid or gnm_set_occupancy_cap.  Counts negative or >= 2^31 - 1, len_threshold < 1, NULL or misaligned
+ * record / ws / undecided, NULL arrays that the sizes need are errors, returned before anything is launched.                      */
+typedef struct gnm_resolve_record {
+  int64_t contigs, eligible, pieces, dropped, nodes, serial, invalid, calls;
+} gnm_resolve_record;
+size_t gnm_resolve_workspace_bytes(int64_t C, int64_t P, int64_t n);
+int gnm_resolve_prepare(int64_t C, int64_t P, int64_t n, int64_t E, const int32_t* contig_ptr, const int32_t* walk_nodes,
+                        const int32_t* walk_edges, const int32_t* order, int64_t len_threshold, void* record, void* ws,
+                        size_t ws_bytes, void* stream);
+int gnm_resolve_rounds(int64_t C, int64_t P, int64_t n, int64_t E, const int32_t* contig_ptr, const int32_t* walk_nodes,
+                       const int32_t* walk_edges, const int32_t* order, int64_t len_threshold, int64_t first_round, int64_t rounds,
+                       int64_t* undecided, void* record, void* ws, size_t ws_bytes, void* stream);
+int gnm_resolve_layout(int64_t C, int64_t P, int64_t n, int64_t E, const int32_t* contig_ptr, const int32_t* walk_nodes,
+                       const int32_t* walk_edges, const int32_t* order, int64_t len_threshold, const int64_t* prefix_length,
+                       const int64_t* read_length, const float* y, void* record, int32_t* out_ptr, int32_t* out_nodes,
+                       int32_t* out_edges, int64_t* out_bases, int32_t* out_wrong, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
