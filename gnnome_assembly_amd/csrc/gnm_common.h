@@ -23,6 +23,19 @@ int reduce_partials_strided(const double* partials, int nblk, int row_stride, in
                             void* stream);
 int reduce_partials_batched(const double* partials, int batch, int nblk, int W, float* out, void* stream);
 
+// ---- shared across translation units (each defined in the file named; declared here only) ------
+// kernel-generation switches of gnm_debug_set_variant (gnm_fused.hip)
+int eb_variant();   // edge_bwd_tr_k: 1 = LDS stash + pinned prefetch (default), 2 = registers, unpinned
+int gate2_wg();     // workgroups per CU of the two-sided forward sweep: 2 (default) or 1
+// gnm_fused.hip: the split-mode route of gnm_gemm_f32 (gnm_gemm.hip) for big-M shapes whose other dimensions are multiples of 128.
+// *_try: 1 = done, 0 = not eligible (the caller runs the fp32-MFMA kernel), < 0 = error.
+size_t gemm_b3_workspace_bytes(int mode, int64_t M, int64_t N, int64_t K);
+int gemm_b3_try(int mode, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
+                float* C, int64_t ldc, const float* bias, const float* resid, int64_t ldr, int relu, void* ws,
+                size_t ws_bytes, hipStream_t st);
+int gemm_b3_tn_colsum_try(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+                          int64_t ldc, float* colsum, void* ws, size_t ws_bytes, hipStream_t st);
+
 #define GNM_CHECK_ARG(cond, ...)                     \
   do {                                               \
     if (!(cond)) {                                   \
@@ -103,6 +116,7 @@ __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<floa
 // streams do not push the gathered node rows -- which ARE re-used, by the ~5 edges of a node -- out of
 // the 4 MB per-XCD L2.
 typedef float floatx4_ __attribute__((ext_vector_type(4)));
+typedef float floatx16 __attribute__((ext_vector_type(16)));   // one 32x32 MFMA accumulator block per lane
 __device__ __forceinline__ float4 ld4_nt(const float* p) {
   const floatx4_ v = __builtin_nontemporal_load(reinterpret_cast<const floatx4_*>(p));
   return make_float4(v.x, v.y, v.z, v.w);

@@ -36,8 +36,6 @@
 
 namespace gnm {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
 constexpr int FH = 128;          // hidden width these kernels are built for
 constexpr int FTR = 64;          // rows per tile
 constexpr int FP = FH + 4;       // LDS row pitch (floats)
@@ -143,8 +141,6 @@ __device__ __forceinline__ int64_t clampi(int64_t r, int64_t hi) { return r < hi
 // A policy stages tile rows into its LDS image(s), keeps this wave's weight block as fragments in
 // VGPRs, and accumulates rows 0-31 / 32-63 of the tile into acc0 / acc1.
 // ------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int BP = FH + 8;          // bf16 image row pitch (272 B): ds_read_b128 fragment reads conflict-free
 constexpr int BIMG = FTR * BP;      // elements per bf16 image
 constexpr int BKC = FH / 16;        // 8 k-chunks of 16
@@ -172,6 +168,8 @@ struct MmF32 {
   }
 };
 
+// The arithmetic of split3f (gnm_tr.h), statement for statement, with the last remainder in a named temporary.  Both stay: hipcc
+// schedules the MmB3 kernels here a few instructions differently when they call split3f instead.
 __device__ __forceinline__ void split3(const float4& v, bf16x4& hi, bf16x4& mid, bf16x4& lo) {
   const float x[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -1819,16 +1817,6 @@ using namespace gnm;
 
 static inline int64_t cdiv_(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-namespace gnm {   // gnm_tr.hip: the split-mode TN kernel on swizzled row-major images + transpose reads
-int tn_tr_rows_per_tile();
-int tn_tr_occupancy(bool conv = false, bool h2 = false);
-void tn_tr_launch(int64_t M, const float* A, int64_t lda, int ncg, const void* B, int64_t ldb, int ncgb, float* slab,
-                  double* partials, int nslot, int64_t tiles_per_slot, hipStream_t st, const TnConv* cv = nullptr, bool h2 = false);
-size_t edge_bwd_tr_pack_bytes();
-int edge_bwd_tr_launch(int64_t E, const float* ge, float* ge_out, const float* t, const float* e_in, const float* stat_e,
-                       const float* bstat_e, const float* gamma_e, const float* W3, void* wpack, float* slab,
-                       double* partials, hipStream_t st, bool h2 = false, bool given = false);
-}
 // kernel-generation switches for same-process A/B runs (gnm_debug_set_variant, GNM_VARIANTS).  Round 5 removed the generations
 // that had lost their A/B (the round-1 split-mode edge backward / weight gradient / VALU encoders, the unpipelined t kernels,
 // the role-split chained kernel): their numbers are in profiles/r02_ab_kernels.txt, r03_chain_phases.txt, r04_ab_*.txt.
@@ -1837,10 +1825,8 @@ static int g_eb_variant = 1;     // edge_bwd_tr_k: 1 = LDS stash + pinned prefet
 // (W3 stationary: +32 registers per thread, over the 128 of four waves per SIMD) would be confined to: the measured price of
 // "t never materialised" in the forward sweep (profiles/r06_ab_gate2_occupancy.txt).  The caller passes the plan built for that partition.
 static int g_gate2_wg = 2;
-namespace gnm {
-int eb_variant() { return g_eb_variant; }
-int gate2_wg() { return g_gate2_wg; }
-}
+int gnm::eb_variant() { return g_eb_variant; }
+int gnm::gate2_wg() { return g_gate2_wg; }
 extern "C" int gnm_debug_set_variant(const char* what, int v) {
   if (what && !strcmp(what, "edge_bwd")) { g_eb_variant = v; return 0; }
   if (what && !strcmp(what, "gate2_wg") && (v == 1 || v == 2)) { g_gate2_wg = v; return 0; }
@@ -1974,13 +1960,45 @@ extern "C" int gnm_node_proj_fwd(int64_t N, int H, int ncols, const float* h, co
                           : node_proj_fwd_impl<MmF32>(N, ncols, h, W, b, Pout, ws, stream);
 }
 
-namespace gnm {
-int edge_bwd_chain_launch(const ChainArgs& in, const float* W3, void* wpack, hipStream_t st, bool h2 = false);   // gnm_tr.hip
-}
-extern "C" size_t gnm_edge_bwd_fused_workspace_bytes(void);
+// The workspace of the edge backward kernels: the packed W3, then one 128 x 128 slab of gW3 per possible workgroup.
+static float* w3_slabs(void* ws) { return (float*)((char*)ws + gnm_rowtile_workspace_bytes(FH)); }
 
-// The fused edge backward of layer i chained with the by-destination backward pass of layer i-1 (gnm.h).
-static int edge_bwd_chain_impl(int64_t N, int64_t E, int H, const float* ge, float* ge_out, const float* t_hi,
+// The weight-gradient epilogue of every edge backward: gW3 = the sum of the `grid` slabs a kernel left in the workspace, then
+// gb3 = the sum of its `grid` partial rows.  Returns 0, or -3.
+static int w3_grad_reduce(const char* what, void* ws, double* partials, int grid, float* gW3, float* gb3, void* stream) {
+  hipLaunchKernelGGL(slab_reduce_k, dim3(FH * FH / 128), dim3(256), 0, (hipStream_t)stream, (const float*)w3_slabs(ws), grid, FH * FH, gW3);
+  GNM_LAUNCH_CHECK(what);
+  return gnm_reduce_partials(partials, grid, 1, FH, gb3, stream) ? -3 : 0;
+}
+
+// THE place that validates and launches a chained sweep (edge_bwd_chain_launch, gnm_tr.hip).  `a` arrives with the entry point's own
+// fields; here the workspace, the partition (one 512-thread workgroup per CU), the 32-bit buffer offsets and the plan's partition are
+// checked, and what every sweep sets alike is set.  H: the row pitch of the layer-(i-1) tensors (256: one 128-column half per call).
+// W3_hi == NULL: no layer above.  *nblk_out: the grid = the number of gW3 slabs and of partial rows of both kinds.
+static int chain_sweep(const char* what, int64_t N, int64_t E, int H, const int32_t* isrc, const int32_t* idst, const int32_t* in_ptr,
+                       const uint32_t* sinfo, int64_t plan_nodes_per_block, ChainArgs& a, const float* W3_hi, int* nblk_out,
+                       void* ws, size_t ws_bytes, void* stream) {
+  GNM_CHECK_ARG(ws && ws_bytes >= gnm_edge_bwd_fused_workspace_bytes(), "%s: workspace %zu < %zu", what, ws_bytes,
+                gnm_edge_bwd_fused_workspace_bytes());
+  int64_t npb = 0;
+  gnm_sweep_partition(N, 1, &npb, nullptr);
+  // the walkers' / run sums' rows are addressed through 32-bit buffer offsets over the workgroup's node range
+  GNM_CHECK_ARG((npb + 2 * kSweepMargin) * 5 * H * 4 < (int64_t)INT32_MAX, "%s: %lld nodes per workgroup exceed the 32-bit buffer offsets",
+                what, (long long)npb);
+  GNM_CHECK_ARG(!sinfo || plan_nodes_per_block == npb, "%s: the sweep plan was built for %lld nodes per workgroup, the kernel uses %lld "
+                "(gnm_sweep_partition(N, 1))", what, (long long)plan_nodes_per_block, (long long)npb);
+  a.E = E; a.N = N; a.hfull = H;
+  a.isrc = isrc; a.idst = idst; a.in_ptr = in_ptr;
+  a.sinfo = sinfo; a.margin = kSweepMargin; a.slab = w3_slabs(ws);
+  const int g = edge_bwd_chain_launch(a, W3_hi, W3_hi ? ws : nullptr, (hipStream_t)stream, W3_hi && g_matmul_mode == 2);
+  GNM_CHECK_ARG(g > 0, "%s: no kernel for this configuration", what);
+  GNM_LAUNCH_CHECK(what);
+  *nblk_out = g;
+  return 0;
+}
+
+// The fused edge backward of layer i chained with the by-destination backward pass of layer i-1 (gnm.h); sinfo: the two-sided sweep.
+static int edge_bwd_chain_impl(const char* what, int64_t N, int64_t E, int H, const float* ge, float* ge_out, const float* t_hi,
                                const float* e_mid, const float* stat_hi, const float* bstat_hi, const float* gamma_hi,
                                const float* W3_hi, float* gW3_hi, float* gb3_hi, double* partials_hi,
                                const float* t_lo, const float* stat_lo, const float* P_lo, const float* Q_lo,
@@ -1988,42 +2006,22 @@ static int edge_bwd_chain_impl(int64_t N, int64_t E, int H, const float* ge, flo
                                const int32_t* in_ptr, float* gP_lo, float* Ud_lo, float* Td_lo, double* partials_lo,
                                const uint32_t* sinfo, int64_t plan_nodes_per_block, float* UT_lo,
                                int* nblk_out, void* ws, size_t ws_bytes, void* stream) {
-  GNM_CHECK_ARG(H == FH, "edge_bwd_chain: H=%d (only 128 is built)", H);
-  GNM_CHECK_ARG(g_matmul_mode >= 1, "edge_bwd_chain: only built for the split matmul modes");
+  GNM_CHECK_ARG(H == FH, "%s: H=%d (only 128 is built)", what, H);
+  GNM_CHECK_ARG(g_matmul_mode >= 1, "%s: only built for the split matmul modes", what);
   GNM_CHECK_ARG(N > 0 && E > 0 && ge && ge_out && t_hi && e_mid && stat_hi && bstat_hi && gamma_hi && W3_hi && gW3_hi &&
                     gb3_hi && partials_hi && t_lo && stat_lo && P_lo && Q_lo && hf_lo && hb_lo && isrc && idst && in_ptr &&
                     gP_lo && Ud_lo && Td_lo && partials_lo && nblk_out && partials_hi != partials_lo,
-                "edge_bwd_chain: null / aliased argument");
-  GNM_CHECK_ARG(ws && ws_bytes >= gnm_edge_bwd_fused_workspace_bytes(), "edge_bwd_chain: workspace %zu < %zu", ws_bytes,
-                gnm_edge_bwd_fused_workspace_bytes());
-  hipStream_t st = (hipStream_t)stream;
-  float* slab = (float*)((char*)ws + gnm_rowtile_workspace_bytes(FH));
+                "%s: null / aliased argument", what);
+  GNM_CHECK_ARG(!sinfo || UT_lo, "%s: UT_lo is null", what);
   ChainArgs a{};
-  a.E = E; a.N = N;
   a.ge = ge; a.ge_out = ge_out; a.t_hi = t_hi; a.e_mid = e_mid;
-  a.stat_hi = stat_hi; a.bstat_hi = bstat_hi; a.gamma_hi = gamma_hi;
-  a.slab = slab; a.partials = partials_hi;
+  a.stat_hi = stat_hi; a.bstat_hi = bstat_hi; a.gamma_hi = gamma_hi; a.partials = partials_hi;
   a.t_lo = t_lo; a.stat_lo = stat_lo; a.P_lo = P_lo; a.Q_lo = Q_lo; a.hf_lo = hf_lo; a.hb_lo = hb_lo;
-  a.isrc = isrc; a.idst = idst; a.in_ptr = in_ptr;
-  a.gP_lo = gP_lo; a.Ud_lo = Ud_lo; a.Td_lo = Td_lo; a.partials_lo = partials_lo;
-  a.sinfo = sinfo; a.UT_lo = UT_lo; a.margin = kSweepMargin;
+  a.gP_lo = gP_lo; a.Ud_lo = Ud_lo; a.Td_lo = Td_lo; a.partials_lo = partials_lo; a.UT_lo = UT_lo;
   a.ud_pitch = Td_lo == Ud_lo + FH ? 2 * FH : FH;       // [Ud | Td] as one [N,2H] array, or two [N,H] arrays
-  int64_t npb = 0;
-  gnm_sweep_partition(N, 1, &npb, nullptr);      // one 512-thread workgroup per CU
-  // the walkers' / run sums' rows are addressed through 32-bit buffer offsets over the workgroup's node range
-  GNM_CHECK_ARG((npb + 2 * kSweepMargin) * 5 * FH * 4 < (int64_t)INT32_MAX, "edge_bwd_chain: %lld nodes per workgroup exceed the 32-bit buffer offsets",
-                (long long)npb);
-  if (sinfo) {
-    GNM_CHECK_ARG(UT_lo, "edge_bwd_chain_src: UT_lo is null");
-    GNM_CHECK_ARG(plan_nodes_per_block == npb, "edge_bwd_chain_src: the sweep plan was built for %lld nodes per workgroup, the kernel uses %lld "
-                  "(gnm_sweep_partition(N, 1))", (long long)plan_nodes_per_block, (long long)npb);
-  }
-  const int grid = edge_bwd_chain_launch(a, W3_hi, ws, st, g_matmul_mode == 2);
-  GNM_LAUNCH_CHECK("edge_bwd_chain");
-  hipLaunchKernelGGL(slab_reduce_k, dim3(FH * FH / 128), dim3(256), 0, st, (const float*)slab, grid, FH * FH, gW3_hi);
-  GNM_LAUNCH_CHECK("edge_bwd_chain slab reduce");
-  *nblk_out = grid;
-  return gnm_reduce_partials(partials_hi, grid, 1, FH, gb3_hi, stream) ? -3 : 0;
+  if (const int rc = chain_sweep(what, N, E, H, isrc, idst, in_ptr, sinfo, plan_nodes_per_block, a, W3_hi, nblk_out, ws, ws_bytes, stream))
+    return rc;
+  return w3_grad_reduce("edge_bwd_chain slab reduce", ws, partials_hi, *nblk_out, gW3_hi, gb3_hi, stream);
 }
 
 // the top of the stack: gnm_edge_bwd_dst (+ the by-source sums through the sweep plan) on the chained kernel's sweep
@@ -2035,30 +2033,32 @@ extern "C" int gnm_edge_bwd_top(int64_t N, int64_t E, int H, float* ge, const fl
   GNM_CHECK_ARG(H == FH || (H == 2 * FH && sinfo), "edge_bwd_top: H=%d (128; 256 with a sweep plan, one sweep per 128-column half)", H);
   GNM_CHECK_ARG(N > 0 && E > 0 && ge && e_out && t && stat_e && P && Q && hf && hb && isrc && idst && in_ptr && gP && Ud &&
                     Td && partials && nblk_out && (!sinfo || UT), "edge_bwd_top: null argument");
-  GNM_CHECK_ARG(ws && ws_bytes >= gnm_edge_bwd_fused_workspace_bytes(), "edge_bwd_top: workspace %zu < %zu", ws_bytes,
-                gnm_edge_bwd_fused_workspace_bytes());
-  int64_t npb = 0;
-  gnm_sweep_partition(N, 1, &npb, nullptr);
-  GNM_CHECK_ARG((npb + 2 * kSweepMargin) * 5 * H * 4 < (int64_t)INT32_MAX, "edge_bwd_top: %lld nodes per workgroup exceed the 32-bit buffer offsets",
-                (long long)npb);
-  GNM_CHECK_ARG(!sinfo || plan_nodes_per_block == npb, "edge_bwd_top: the sweep plan was built for %lld nodes per workgroup, the kernel uses %lld",
-                (long long)plan_nodes_per_block, (long long)npb);
   for (int c0 = 0; c0 < H; c0 += FH) {                             // a 256-wide layer = two 128-column problems with row pitch 256
     ChainArgs a{};
-    a.E = E; a.N = N; a.hfull = H;
     a.ge = ge + c0; a.ge_out = ge + c0; a.e_mid = e_out + c0;      // t_hi == NULL selects the sweep without a layer above
-    a.slab = (float*)((char*)ws + gnm_rowtile_workspace_bytes(FH));
     a.t_lo = t + c0; a.stat_lo = stat_e + c0; a.P_lo = P + c0; a.Q_lo = Q + c0; a.hf_lo = hf + c0; a.hb_lo = hb + c0;
-    a.isrc = isrc; a.idst = idst; a.in_ptr = in_ptr;
     a.gP_lo = gP + c0; a.Ud_lo = Ud + c0; a.Td_lo = Td + c0; a.partials_lo = partials + c0;
-    a.sinfo = sinfo; a.UT_lo = UT ? UT + c0 : nullptr; a.margin = kSweepMargin;
+    a.UT_lo = UT ? UT + c0 : nullptr;
     a.ud_pitch = Td == Ud + H ? 2 * H : H;
-    const int g = edge_bwd_chain_launch(a, nullptr, nullptr, (hipStream_t)stream);
-    GNM_CHECK_ARG(g > 0, "edge_bwd_top: no kernel for this configuration");
-    *nblk_out = g;
-    GNM_LAUNCH_CHECK("edge_bwd_top");
+    if (const int rc = chain_sweep("edge_bwd_top", N, E, H, isrc, idst, in_ptr, sinfo, plan_nodes_per_block, a, nullptr, nblk_out, ws,
+                                   ws_bytes, stream))
+      return rc;
   }
   return 0;
+}
+
+// The layer-(i-1) half of a LayerNorm sweep: ge in place, Q = gnm_ln_node_bwd's [N,4H] = Qf | Rf | Qb | Rb, the sums of gt by
+// destination / by source straight into their column groups of gP (no BatchNorm-backward means to wait for).
+static ChainArgs ln_sweep_lo(int H, float* ge, const float* e_mid, const float* t, const float* gamma, const float* beta, int width,
+                             const float* P, const float* Q, const float* hf, const float* hb, float* gP, float* gt, double* partials) {
+  ChainArgs a{};
+  a.ge = ge; a.ge_out = ge; a.e_mid = e_mid;
+  a.t_lo = t; a.P_lo = P; a.Q_lo = Q; a.q_pitch = 4 * H; a.qb_off = 2 * H; a.hf_lo = hf; a.hb_lo = hb;
+  a.gP_lo = gP; a.Ud_lo = gP + 4 * H; a.Td_lo = gP + 4 * H; a.ud_pitch = 5 * H;     // sum_dst gt = gB2h, straight into its column group
+  a.UT_lo = gP + 3 * H; a.ut_pitch = 5 * H;                                            // sum_src gt = gB1h
+  a.partials_lo = partials;
+  a.ln_gamma = gamma; a.ln_beta = beta; a.ln_width = width; a.gt_out = gt;
+  return a;
 }
 
 // The LayerNorm form of gnm_edge_bwd_top (round 6; H = 128, with a sweep plan): gnm_ln_edge_bwd_dst + gnm_ln_edge_bwd_src as ONE two-sided sweep.
@@ -2074,30 +2074,8 @@ extern "C" int gnm_ln_edge_bwd_top(int64_t N, int64_t E, int H, float* ge, const
   GNM_CHECK_ARG(width >= 1 && width <= H, "ln_edge_bwd_top: width must be in [1, H]");
   GNM_CHECK_ARG(N > 0 && E > 0 && ge && e_out && t && gamma_e && beta_e && P && Q && hf && hb && isrc && idst && in_ptr && gP && gt &&
                     partials && sinfo && nblk_out, "ln_edge_bwd_top: null argument");
-  GNM_CHECK_ARG(ws && ws_bytes >= gnm_edge_bwd_fused_workspace_bytes(), "ln_edge_bwd_top: workspace %zu < %zu", ws_bytes,
-                gnm_edge_bwd_fused_workspace_bytes());
-  int64_t npb = 0;
-  gnm_sweep_partition(N, 1, &npb, nullptr);
-  GNM_CHECK_ARG((npb + 2 * kSweepMargin) * 5 * H * 4 < (int64_t)INT32_MAX, "ln_edge_bwd_top: %lld nodes per workgroup exceed the 32-bit buffer offsets",
-                (long long)npb);
-  GNM_CHECK_ARG(plan_nodes_per_block == npb, "ln_edge_bwd_top: the sweep plan was built for %lld nodes per workgroup, the kernel uses %lld",
-                (long long)plan_nodes_per_block, (long long)npb);
-  ChainArgs a{};
-  a.E = E; a.N = N; a.hfull = H;
-  a.ge = ge; a.ge_out = ge; a.e_mid = e_out;
-  a.slab = (float*)((char*)ws + gnm_rowtile_workspace_bytes(FH));
-  a.t_lo = t; a.P_lo = P; a.Q_lo = Q; a.q_pitch = 4 * H; a.qb_off = 2 * H; a.hf_lo = hf; a.hb_lo = hb;
-  a.isrc = isrc; a.idst = idst; a.in_ptr = in_ptr;
-  a.gP_lo = gP; a.Ud_lo = gP + 4 * H; a.Td_lo = gP + 4 * H; a.ud_pitch = 5 * H;     // sum_dst gt = gB2h, straight into its column group
-  a.UT_lo = gP + 3 * H; a.ut_pitch = 5 * H;                                            // sum_src gt = gB1h
-  a.partials_lo = partials;
-  a.sinfo = sinfo; a.margin = kSweepMargin;
-  a.ln_gamma = gamma_e; a.ln_beta = beta_e; a.ln_width = width; a.gt_out = gt;
-  const int g = edge_bwd_chain_launch(a, nullptr, nullptr, (hipStream_t)stream);
-  GNM_CHECK_ARG(g > 0, "ln_edge_bwd_top: no kernel for this configuration");
-  *nblk_out = g;
-  GNM_LAUNCH_CHECK("ln_edge_bwd_top");
-  return 0;
+  ChainArgs a = ln_sweep_lo(H, ge, e_out, t, gamma_e, beta_e, width, P, Q, hf, hb, gP, gt, partials);
+  return chain_sweep("ln_edge_bwd_top", N, E, H, isrc, idst, in_ptr, sinfo, plan_nodes_per_block, a, nullptr, nblk_out, ws, ws_bytes, stream);
 }
 
 // The CHAINED LayerNorm backward (round 6; H = 128, split matmul modes, with a sweep plan): gnm_edge_bwd_fused_gt of layer i (its gt GIVEN:
@@ -2115,34 +2093,12 @@ extern "C" int gnm_ln_edge_bwd_chain(int64_t N, int64_t E, int H, float* ge, con
   GNM_CHECK_ARG(N > 0 && E > 0 && ge && gt_hi && e_mid && W3_hi && gW3_hi && gb3_hi && partials_hi && t_lo && gamma_lo && beta_lo && P_lo &&
                     Q_lo && hf_lo && hb_lo && isrc && idst && in_ptr && gP_lo && gt_lo && partials_lo && sinfo && nblk_out &&
                     partials_hi != partials_lo && gt_hi != gt_lo, "ln_edge_bwd_chain: null / aliased argument");
-  GNM_CHECK_ARG(ws && ws_bytes >= gnm_edge_bwd_fused_workspace_bytes(), "ln_edge_bwd_chain: workspace %zu < %zu", ws_bytes,
-                gnm_edge_bwd_fused_workspace_bytes());
-  hipStream_t st = (hipStream_t)stream;
-  float* slab = (float*)((char*)ws + gnm_rowtile_workspace_bytes(FH));
-  int64_t npb = 0;
-  gnm_sweep_partition(N, 1, &npb, nullptr);
-  GNM_CHECK_ARG((npb + 2 * kSweepMargin) * 5 * FH * 4 < (int64_t)INT32_MAX, "ln_edge_bwd_chain: %lld nodes per workgroup exceed the 32-bit buffer offsets",
-                (long long)npb);
-  GNM_CHECK_ARG(plan_nodes_per_block == npb, "ln_edge_bwd_chain: the sweep plan was built for %lld nodes per workgroup, the kernel uses %lld",
-                (long long)plan_nodes_per_block, (long long)npb);
-  ChainArgs a{};
-  a.E = E; a.N = N; a.hfull = H;
-  a.ge = ge; a.ge_out = ge; a.t_hi = gt_hi; a.e_mid = e_mid;
-  a.slab = slab; a.partials = partials_hi;
-  a.t_lo = t_lo; a.P_lo = P_lo; a.Q_lo = Q_lo; a.q_pitch = 4 * H; a.qb_off = 2 * H; a.hf_lo = hf_lo; a.hb_lo = hb_lo;
-  a.isrc = isrc; a.idst = idst; a.in_ptr = in_ptr;
-  a.gP_lo = gP_lo; a.Ud_lo = gP_lo + 4 * H; a.Td_lo = gP_lo + 4 * H; a.ud_pitch = 5 * H;
-  a.UT_lo = gP_lo + 3 * H; a.ut_pitch = 5 * H;
-  a.partials_lo = partials_lo;
-  a.sinfo = sinfo; a.margin = kSweepMargin;
-  a.ln_gamma = gamma_lo; a.ln_beta = beta_lo; a.ln_width = width; a.gt_out = gt_lo;
-  const int grid = edge_bwd_chain_launch(a, W3_hi, ws, st, g_matmul_mode == 2);
-  GNM_CHECK_ARG(grid > 0, "ln_edge_bwd_chain: no kernel for this configuration");
-  GNM_LAUNCH_CHECK("ln_edge_bwd_chain");
-  hipLaunchKernelGGL(slab_reduce_k, dim3(FH * FH / 128), dim3(256), 0, st, (const float*)slab, grid, FH * FH, gW3_hi);
-  GNM_LAUNCH_CHECK("ln_edge_bwd_chain slab reduce");
-  *nblk_out = grid;
-  return gnm_reduce_partials(partials_hi, grid, 1, FH, gb3_hi, stream) ? -3 : 0;
+  ChainArgs a = ln_sweep_lo(H, ge, e_mid, t_lo, gamma_lo, beta_lo, width, P_lo, Q_lo, hf_lo, hb_lo, gP_lo, gt_lo, partials_lo);
+  a.t_hi = gt_hi; a.partials = partials_hi;
+  if (const int rc = chain_sweep("ln_edge_bwd_chain", N, E, H, isrc, idst, in_ptr, sinfo, plan_nodes_per_block, a, W3_hi, nblk_out, ws,
+                                 ws_bytes, stream))
+    return rc;
+  return w3_grad_reduce("ln_edge_bwd_chain slab reduce", ws, partials_hi, *nblk_out, gW3_hi, gb3_hi, stream);
 }
 
 extern "C" int gnm_edge_bwd_chain(int64_t N, int64_t E, int H, const float* ge, float* ge_out, const float* t_hi,
@@ -2152,8 +2108,8 @@ extern "C" int gnm_edge_bwd_chain(int64_t N, int64_t E, int H, const float* ge, 
                                   const float* hf_lo, const float* hb_lo, const int32_t* isrc, const int32_t* idst,
                                   const int32_t* in_ptr, float* gP_lo, float* Ud_lo, float* Td_lo, double* partials_lo,
                                   int* nblk_out, void* ws, size_t ws_bytes, void* stream) {
-  return edge_bwd_chain_impl(N, E, H, ge, ge_out, t_hi, e_mid, stat_hi, bstat_hi, gamma_hi, W3_hi, gW3_hi, gb3_hi, partials_hi,
-                             t_lo, stat_lo, P_lo, Q_lo, hf_lo, hb_lo, isrc, idst, in_ptr, gP_lo, Ud_lo, Td_lo, partials_lo,
+  return edge_bwd_chain_impl("edge_bwd_chain", N, E, H, ge, ge_out, t_hi, e_mid, stat_hi, bstat_hi, gamma_hi, W3_hi, gW3_hi, gb3_hi,
+                             partials_hi, t_lo, stat_lo, P_lo, Q_lo, hf_lo, hb_lo, isrc, idst, in_ptr, gP_lo, Ud_lo, Td_lo, partials_lo,
                              nullptr, 0, nullptr, nblk_out, ws, ws_bytes, stream);
 }
 
@@ -2166,8 +2122,8 @@ extern "C" int gnm_edge_bwd_chain_src(int64_t N, int64_t E, int H, const float* 
                                       const uint32_t* sinfo, int64_t plan_nodes_per_block,
                                       float* UT_lo, int* nblk_out, void* ws, size_t ws_bytes, void* stream) {
   GNM_CHECK_ARG(sinfo, "edge_bwd_chain_src: sinfo is null");
-  return edge_bwd_chain_impl(N, E, H, ge, ge_out, t_hi, e_mid, stat_hi, bstat_hi, gamma_hi, W3_hi, gW3_hi, gb3_hi, partials_hi,
-                             t_lo, stat_lo, P_lo, Q_lo, hf_lo, hb_lo, isrc, idst, in_ptr, gP_lo, Ud_lo, Td_lo, partials_lo,
+  return edge_bwd_chain_impl("edge_bwd_chain_src", N, E, H, ge, ge_out, t_hi, e_mid, stat_hi, bstat_hi, gamma_hi, W3_hi, gW3_hi, gb3_hi,
+                             partials_hi, t_lo, stat_lo, P_lo, Q_lo, hf_lo, hb_lo, isrc, idst, in_ptr, gP_lo, Ud_lo, Td_lo, partials_lo,
                              sinfo, plan_nodes_per_block, UT_lo, nblk_out, ws, ws_bytes, stream);
 }
 
@@ -2181,25 +2137,20 @@ static int edge_bwd_fused_impl(int64_t E, const float* ge, float* ge_out, const 
                                const float* stat_e, const float* bstat_e, const float* gamma_e, const float* W3,
                                float* gW3, float* gb3, double* partials, void* ws, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  float* slab = (float*)((char*)ws + gnm_rowtile_workspace_bytes(FH));
   int grid;
   if constexpr (MM::kSplit) {
-    grid = edge_bwd_tr_launch(E, ge, ge_out, t, e_in, stat_e, bstat_e, gamma_e, W3, ws, slab, partials, st, g_matmul_mode == 2);
+    grid = edge_bwd_tr_launch(E, ge, ge_out, t, e_in, stat_e, bstat_e, gamma_e, W3, ws, w3_slabs(ws), partials, st, g_matmul_mode == 2);
     GNM_LAUNCH_CHECK("edge_bwd_fused (tr)");
-    hipLaunchKernelGGL(slab_reduce_k, dim3(FH * FH / 128), dim3(256), 0, st, (const float*)slab, grid, FH * FH, gW3);
-    GNM_LAUNCH_CHECK("edge_bwd_fused slab reduce");
-    return gnm_reduce_partials(partials, grid, 1, FH, gb3, stream) ? -3 : 0;
+  } else {
+    launch_pack<MM>(W3, FH, FH / 32, 1, ws, st);
+    GNM_LAUNCH_CHECK("pack_w (NN)");
+    const int64_t ntiles = cdiv_(E, FTR2);
+    grid = persistent_grid(ntiles, 8, occ_blocks<edge_bwd_fused32_k>());
+    hipLaunchKernelGGL(edge_bwd_fused32_k, dim3(grid), dim3(kBlock), 0, st, E, ge, ge_out, t, e_in, stat_e, bstat_e,
+                       gamma_e, (const void*)ws, w3_slabs(ws), partials, cdiv_(ntiles, grid));
+    GNM_LAUNCH_CHECK("edge_bwd_fused");
   }
-  launch_pack<MM>(W3, FH, FH / 32, 1, ws, st);
-  GNM_LAUNCH_CHECK("pack_w (NN)");
-  const int64_t ntiles = cdiv_(E, FTR2);
-  grid = persistent_grid(ntiles, 8, occ_blocks<edge_bwd_fused32_k>());
-  hipLaunchKernelGGL(edge_bwd_fused32_k, dim3(grid), dim3(kBlock), 0, st, E, ge, ge_out, t, e_in, stat_e, bstat_e,
-                     gamma_e, (const void*)ws, slab, partials, cdiv_(ntiles, grid));
-  GNM_LAUNCH_CHECK("edge_bwd_fused");
-  hipLaunchKernelGGL(slab_reduce_k, dim3(FH * FH / 128), dim3(256), 0, st, (const float*)slab, grid, FH * FH, gW3);
-  GNM_LAUNCH_CHECK("edge_bwd_fused slab reduce");
-  return gnm_reduce_partials(partials, grid, 1, FH, gb3, stream) ? -3 : 0;
+  return w3_grad_reduce("edge_bwd_fused slab reduce", ws, partials, grid, gW3, gb3, stream);
 }
 
 extern "C" int gnm_edge_bwd_fused(int64_t E, int H, const float* ge, float* ge_out, const float* t, const float* e_in,
@@ -2227,13 +2178,10 @@ extern "C" int gnm_edge_bwd_fused_gt(int64_t E, int H, const float* ge, float* g
   GNM_CHECK_ARG(ws && ws_bytes >= gnm_edge_bwd_fused_workspace_bytes(), "edge_bwd_fused_gt: workspace %zu < %zu", ws_bytes,
                 gnm_edge_bwd_fused_workspace_bytes());
   if (!g_matmul_mode) { ::gnm::set_error("edge_bwd_fused_gt: built for the split matmul modes (1, 2) only"); return -4; }
-  hipStream_t st = (hipStream_t)stream;
-  float* slab = (float*)((char*)ws + gnm_rowtile_workspace_bytes(FH));
-  const int grid = edge_bwd_tr_launch(E, ge, ge_out, gt, e_in, nullptr, nullptr, nullptr, W3, ws, slab, partials, st, g_matmul_mode == 2, true);
+  const int grid = edge_bwd_tr_launch(E, ge, ge_out, gt, e_in, nullptr, nullptr, nullptr, W3, ws, w3_slabs(ws), partials,
+                                      (hipStream_t)stream, g_matmul_mode == 2, true);
   GNM_LAUNCH_CHECK("edge_bwd_fused_gt (tr)");
-  hipLaunchKernelGGL(slab_reduce_k, dim3(FH * FH / 128), dim3(256), 0, st, (const float*)slab, grid, FH * FH, gW3);
-  GNM_LAUNCH_CHECK("edge_bwd_fused_gt slab reduce");
-  return gnm_reduce_partials(partials, grid, 1, FH, gb3, stream) ? -3 : 0;
+  return w3_grad_reduce("edge_bwd_fused_gt slab reduce", ws, partials, grid, gW3, gb3, stream);
 }
 
 static int tn_colgroups(int64_t N, const float* A, int64_t lda, int ncg, const float* B, float* gW, float* gb,
@@ -2267,7 +2215,6 @@ static int tn_colgroups(int64_t N, const float* A, int64_t lda, int ncg, const f
 // 128: NT / NN through gemm_rows_b3_k, TN through tn_tr_k with (A group, B group) classes.  Returns 1 = done,
 // 0 = not eligible (the caller runs the fp32-MFMA kernel), < 0 = error.
 // ------------------------------------------------------------------------------------------
-namespace gnm {
 static bool gemm_b3_shape_ok(int mode, int64_t M, int64_t N, int64_t K) {
   if (!g_matmul_mode) return false;
   if (mode == GNM_GEMM_TN) return K >= 4096 && M > 0 && N > 0 && M % FH == 0 && N % FH == 0 && (M / FH) * (N / FH) <= 64;
@@ -2282,7 +2229,7 @@ static int gemm_b3_tn_slots(int64_t rows, int ncls) {
   if (nslot < kXcds) nslot = kXcds;
   return nslot;
 }
-size_t gemm_b3_workspace_bytes(int mode, int64_t M, int64_t N, int64_t K) {
+size_t gnm::gemm_b3_workspace_bytes(int mode, int64_t M, int64_t N, int64_t K) {
   if (!gemm_b3_shape_ok(mode, M, N, K)) return 0;
   if (mode == GNM_GEMM_TN) {
     const int ncls = (int)((M / FH) * (N / FH));
@@ -2291,7 +2238,7 @@ size_t gemm_b3_workspace_bytes(int mode, int64_t M, int64_t N, int64_t K) {
   }
   return (size_t)(N / FH) * (K / FH) * 4 * MmB3::kPackBytes;
 }
-int gemm_b3_try(int mode, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
+int gnm::gemm_b3_try(int mode, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
                 float* C, int64_t ldc, const float* bias, const float* resid, int64_t ldr, int relu, void* ws,
                 size_t ws_bytes, hipStream_t st) {
   if (!gemm_b3_shape_ok(mode, M, N, K)) return 0;
@@ -2328,7 +2275,7 @@ int gemm_b3_try(int mode, int64_t M, int64_t N, int64_t K, const float* A, int64
 }
 // the same TN product plus the column sums of A (a Linear's bias gradient beside its weight gradient): tn_tr_k keeps them
 // in fp64 per workgroup anyway
-int gemm_b3_tn_colsum_try(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+int gnm::gemm_b3_tn_colsum_try(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
                           int64_t ldc, float* colsum, void* ws, size_t ws_bytes, hipStream_t st) {
   const int rc = gemm_b3_try(GNM_GEMM_TN, M, N, K, A, lda, B, ldb, C, ldc, nullptr, nullptr, 0, 0, ws, ws_bytes, st);
   if (rc != 1) return rc;
@@ -2339,7 +2286,6 @@ int gemm_b3_tn_colsum_try(int64_t M, int64_t N, int64_t K, const float* A, int64
     if (gnm_reduce_partials(partials + (size_t)(cga * ncgb) * nslot * FH, nslot, 1, FH, colsum + (size_t)cga * FH, (void*)st)) return -3;
   return 1;
 }
-}  // namespace gnm
 
 // gh_in = gh_out + gP W  (W [ncols,128] row-major, ncols % 128 == 0);  gW = gP^T h_in;  gb = sum gP.
 // ws: packed W (ncols/32 fragment blocks) + slabs [ncg][nslot][128][128]; partials double[ncg*nslot][128]
@@ -2347,33 +2293,49 @@ extern "C" size_t gnm_node_proj_bwd_workspace_bytes(int ncols) {
   return gnm_rowtile_workspace_bytes(ncols) + (size_t)kMaxPartialBlocks * FH * FH * sizeof(float);
 }
 
+// Split modes: the stacked weight packed by ONE launch for all column groups (W rows cg*128.. form the [k=128, c=128] block of group
+// cg; pack_w3_gen_k with one output class: k runs over the whole stacked weight, block (cg*4 + wv) as pack_w3_k lays it out), then
+// gh_in = gh_out + gP W over groups of T 32-row tiles.  partials: rowtile_nn2_k, the same product with the BatchNorm_h backward sums
+// of the layer below (z_lo, stat_h_lo) in its epilogue, *nblk_out partial rows.
+template <class MM>
+static int node_proj_bwd_nn_split(int64_t N, int ncols, const float* gP, const float* W, const float* gh_out, float* gh_in,
+                                  const float* z_lo, const float* stat_h_lo, double* partials, int* nblk_out, void* ws, hipStream_t st) {
+  constexpr int T = 4;
+  const int ncg = ncols / FH;
+  if constexpr (MM::kScaled) launch_pack_w2_gen(W, (int64_t)FH, 1, ncg, 1, ws, st);
+  else hipLaunchKernelGGL(pack_w3_gen_k, dim3(4 * ncg), dim3(256), 0, st, W, (int64_t)FH, 1, ncg, 1, (bf16x8*)ws);
+  GNM_LAUNCH_CHECK("pack_w (NN, node)");
+  const int64_t ngroups = cdiv_(N, NR3 * T);
+  const int grid = persistent_grid(ngroups, 1, partials ? occ_blocks<rowtile_nn2_k<MM, T>>() : occ_blocks<rowtile_nn_group32_b3_k<MM, T>>());
+  const Nn2Args a{N, gP, (int64_t)ncols, ncg, (const void*)ws, gh_out, gh_in, cdiv_(ngroups, grid), z_lo, stat_h_lo, partials};
+  if (partials) {
+    hipLaunchKernelGGL((rowtile_nn2_k<MM, T>), dim3(grid), dim3(kBlock), 0, st, a);
+    *nblk_out = grid;
+  } else {
+    hipLaunchKernelGGL((rowtile_nn_group32_b3_k<MM, T>), dim3(grid), dim3(kBlock), 0, st, a.M, a.X, a.ldx, a.ncg, a.Wp, a.R, a.Y,
+                       a.groups_per_block);
+  }
+  GNM_LAUNCH_CHECK(partials ? "node_proj_bwd_nn_stats" : "node_proj_bwd (NN)");
+  return 0;
+}
+
 template <class MM>
 static int node_proj_bwd_nn(int64_t N, int ncols, const float* gP, const float* W, const float* gh_out, float* gh_in,
                             void* ws, hipStream_t st) {
-  const int ncg = ncols / FH;
-  if constexpr (MM::kSplit) {        // W rows cg*128.. form the [k=128, c=128] block of group cg: ONE launch for all groups
-    // (pack_w3_gen_k with one output class: k runs over the whole stacked weight, block (cg*4 + wv) as pack_w3_k lays it out)
-    if constexpr (MM::kScaled) launch_pack_w2_gen(W, (int64_t)FH, 1, ncg, 1, ws, st);
-    else hipLaunchKernelGGL(pack_w3_gen_k, dim3(4 * ncg), dim3(256), 0, st, W, (int64_t)FH, 1, ncg, 1, (bf16x8*)ws);
+  if constexpr (MM::kSplit) {
+    return node_proj_bwd_nn_split<MM>(N, ncols, gP, W, gh_out, gh_in, nullptr, nullptr, nullptr, nullptr, ws, st);
   } else {
+    const int ncg = ncols / FH;
     for (int cg = 0; cg < ncg; ++cg)
       launch_pack<MM>(W + (size_t)cg * FH * FH, FH, FH / 32, 1, (char*)ws + (size_t)cg * 4 * MM::kPackBytes, st);
-  }
-  GNM_LAUNCH_CHECK("pack_w (NN, node)");
-  if constexpr (MM::kSplit) {
-    constexpr int T = 4;
-    const int64_t ngroups = cdiv_(N, NR3 * T);
-    const int grid = persistent_grid(ngroups, 1, occ_blocks<rowtile_nn_group32_b3_k<MM, T>>());
-    hipLaunchKernelGGL((rowtile_nn_group32_b3_k<MM, T>), dim3(grid), dim3(kBlock), 0, st, N, gP, (int64_t)ncols, ncg,
-                       (const void*)ws, gh_out, gh_in, cdiv_(ngroups, grid));
-  } else {
+    GNM_LAUNCH_CHECK("pack_w (NN, node)");
     const int64_t ntiles = cdiv_(N, FTR);
     const int grid = persistent_grid(ntiles, 2, occ_blocks<rowtile_nn_acc_k<MM>>());
     hipLaunchKernelGGL(rowtile_nn_acc_k<MM>, dim3(grid), dim3(kBlock), 0, st, N, gP, (int64_t)ncols, ncg,
                        (const void*)ws, gh_out, gh_in, cdiv_(ntiles, grid));
+    GNM_LAUNCH_CHECK("node_proj_bwd (NN)");
+    return 0;
   }
-  GNM_LAUNCH_CHECK("node_proj_bwd (NN)");
-  return 0;
 }
 
 // The two halves of gnm_node_proj_bwd as separate entry points (same workspace layout), so that a caller can
@@ -2390,7 +2352,7 @@ extern "C" int gnm_node_proj_bwd_nn(int64_t N, int H, int ncols, const float* gP
 }
 
 // gnm_node_proj_bwd_nn with the BatchNorm_h backward sums of the layer below (gnm_node_bwd_stats over gh_in and z_lo) in its
-// epilogue; see rowtile_nn2_k.  bf16x3 mode, H = 128.  partials / *nblk_out: as gnm_node_bwd_stats leaves them.
+// epilogue; see rowtile_nn2_k.  Split matmul modes, H = 128.  partials / *nblk_out: as gnm_node_bwd_stats leaves them.
 extern "C" int gnm_node_proj_bwd_nn_stats(int64_t N, int H, int ncols, const float* gP, const float* W, const float* gh_out,
                                           float* gh_in, const float* z_lo, const float* stat_h_lo, double* partials,
                                           int* nblk_out, void* ws, size_t ws_bytes, void* stream) {
@@ -2400,20 +2362,8 @@ extern "C" int gnm_node_proj_bwd_nn_stats(int64_t N, int H, int ncols, const flo
                 "node_proj_bwd_nn_stats: bad argument");
   GNM_CHECK_ARG(ws && ws_bytes >= gnm_rowtile_workspace_bytes(ncols), "node_proj_bwd_nn_stats: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  const int ncg = ncols / FH;
-  const bool h2 = g_matmul_mode == 2;
-  if (h2) launch_pack_w2_gen(W, (int64_t)FH, 1, ncg, 1, ws, st);
-  else hipLaunchKernelGGL(pack_w3_gen_k, dim3(4 * ncg), dim3(256), 0, st, W, (int64_t)FH, 1, ncg, 1, (bf16x8*)ws);
-  GNM_LAUNCH_CHECK("pack_w (NN, node, stats)");
-  constexpr int T = 4;
-  const int64_t ngroups = cdiv_(N, NR3 * T);
-  const int grid = persistent_grid(ngroups, 1, h2 ? occ_blocks<rowtile_nn2_k<MmH2, T>>() : occ_blocks<rowtile_nn2_k<MmB3, T>>());
-  const Nn2Args a{N, gP, (int64_t)ncols, ncg, (const void*)ws, gh_out, gh_in, cdiv_(ngroups, grid), z_lo, stat_h_lo, partials};
-  if (h2) hipLaunchKernelGGL((rowtile_nn2_k<MmH2, T>), dim3(grid), dim3(kBlock), 0, st, a);
-  else hipLaunchKernelGGL((rowtile_nn2_k<MmB3, T>), dim3(grid), dim3(kBlock), 0, st, a);
-  *nblk_out = grid;
-  GNM_LAUNCH_CHECK("node_proj_bwd_nn_stats");
-  return 0;
+  return g_matmul_mode == 2 ? node_proj_bwd_nn_split<MmH2>(N, ncols, gP, W, gh_out, gh_in, z_lo, stat_h_lo, partials, nblk_out, ws, st)
+                            : node_proj_bwd_nn_split<MmB3>(N, ncols, gP, W, gh_out, gh_in, z_lo, stat_h_lo, partials, nblk_out, ws, st);
 }
 
 extern "C" int gnm_node_proj_bwd_tn(int64_t N, int H, int ncols, const float* gP, const float* h_in, float* gW, float* gb,

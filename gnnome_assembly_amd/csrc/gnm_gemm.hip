@@ -22,8 +22,6 @@
 
 namespace gnm {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
 constexpr int BM = 128, BN = 128, BK = 32;
 constexpr int PITCH_R = BK + 4;    // 36
 constexpr int PITCH_C = BM + 4;    // 132
@@ -368,15 +366,6 @@ static int tn_skinny_try(int64_t M, int64_t N, int64_t K, const float* A, int64_
 }  // namespace gnm
 
 using namespace gnm;
-
-namespace gnm {   // gnm_fused.hip: the split-mode (bf16x3) route for big-M shapes with 128-multiple other dimensions
-size_t gemm_b3_workspace_bytes(int mode, int64_t M, int64_t N, int64_t K);
-int gemm_b3_try(int mode, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
-                float* C, int64_t ldc, const float* bias, const float* resid, int64_t ldr, int relu, void* ws,
-                size_t ws_bytes, hipStream_t st);
-int gemm_b3_tn_colsum_try(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
-                          int64_t ldc, float* colsum, void* ws, size_t ws_bytes, hipStream_t st);
-}
 
 extern "C" size_t gnm_gemm_f32_workspace_bytes(int mode, int64_t M, int64_t N, int64_t K) {
   int splits; int64_t kps;

@@ -16,8 +16,6 @@
 
 namespace gnm {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
 constexpr int PH = 128;          // edge feature width
 constexpr int PS = 64;           // hidden_edge_scores
 constexpr int PT = 64;           // rows per tile

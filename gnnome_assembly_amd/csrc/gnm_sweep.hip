@@ -21,7 +21,6 @@
 
 namespace gnm {
 
-int gate2_wg();          // gnm_fused.hip: gnm_debug_set_variant("gate2_wg", 1 | 2)
 constexpr int GT = 512;                     // threads per workgroup (8 waves), two workgroups per CU
 constexpr int GR = kSweepTileRows;          // rows per tile
 typedef unsigned int u32x4g_ __attribute__((ext_vector_type(4)));

@@ -24,7 +24,6 @@
 
 namespace gnm {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 tr_bf16x4;   // operand type of the tr builtin
@@ -266,6 +265,19 @@ struct TnConv {
   float* Xw; int64_t ldxw;                                                            // the formed groups go to Xw[r][cg*128 + c]
 };
 
+// ---- host entry points of gnm_tr.hip (called from gnm_fused.hip) --------------------------------
+int tn_tr_rows_per_tile();
+int tn_tr_occupancy(bool conv = false, bool h2 = false);
+// cv: the A operand is formed from raw sums (ncg = 2, ncgb = 1);  h2: the f16x2 form
+void tn_tr_launch(int64_t M, const float* A, int64_t lda, int ncg, const void* B, int64_t ldb, int ncgb, float* slab,
+                  double* partials, int nslot, int64_t tiles_per_slot, hipStream_t st, const TnConv* cv = nullptr, bool h2 = false);
+size_t edge_bwd_tr_pack_bytes();
+// returns the grid size (= number of slabs / partial rows written)
+int edge_bwd_tr_launch(int64_t E, const float* ge, float* ge_out, const float* t, const float* e_in, const float* stat_e,
+                       const float* bstat_e, const float* gamma_e, const float* W3, void* wpack, float* slab,
+                       double* partials, hipStream_t st, bool h2 = false, bool given = false);
+// returns the grid size (= number of gW3 slabs / partial rows of both kinds), or -1: no kernel for this configuration
+int edge_bwd_chain_launch(const ChainArgs& in, const float* W3, void* wpack, hipStream_t st, bool h2 = false);
 
 constexpr int kSweepTileRows = 16;      // rows per tile of the sweep kernels (= ER of gnm_tr.hip)
 constexpr int kSweepSlots = 32;         // accumulator slots per workgroup (<= 28 are ever live on the chr19-scale graph)

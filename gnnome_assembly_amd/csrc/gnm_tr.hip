@@ -680,9 +680,7 @@ __global__ __launch_bounds__(kBlock, 2) void edge_bwd_tr_k(
   }
 }
 
-int eb_variant();   // gnm_fused.hip
 size_t edge_bwd_tr_pack_bytes() { return (size_t)(SW / 16) * (SW / 32) * 3 * 64 * sizeof(bf16x8); }
-// returns the grid size (= number of slabs / partial rows written)
 int edge_bwd_tr_launch(int64_t E, const float* ge, float* ge_out, const float* t, const float* e_in, const float* stat_e,
                        const float* bstat_e, const float* gamma_e, const float* W3, void* wpack, float* slab,
                        double* partials, hipStream_t st, bool h2, bool given) {
@@ -1350,7 +1348,6 @@ __global__ __launch_bounds__(256) void zero_empty_segments_k(int64_t N, const in
   }
 }
 
-// returns the grid size (= number of gW3 slabs / partial rows of both kinds)
 int edge_bwd_chain_launch(const ChainArgs& in, const float* W3, void* wpack, hipStream_t st, bool h2) {
   if (W3 && h2) {
     hipLaunchKernelGGL(pack_w2_nn16_k, dim3(SW / 16), dim3(256), 0, st, W3, (int64_t)SW, (unsigned char*)wpack);
@@ -1411,7 +1408,6 @@ int tn_tr_occupancy(bool conv, bool h2) {
   if (h2) return conv ? occ_blocks<tn_tr_k<true, 2, true>>() : occ_blocks<tn_tr_k<false, 2, true>>();
   return conv ? occ_blocks<tn_tr_k<true, 2>>() : occ_blocks<tn_tr_k<false, 2>>();
 }
-// cv: the A operand is formed from raw sums (ncg = 2, ncgb = 1);  h2: the f16x2 form
 void tn_tr_launch(int64_t M, const float* A, int64_t lda, int ncg, const void* B, int64_t ldb, int ncgb, float* slab,
                   double* partials, int nslot, int64_t tiles_per_slot, hipStream_t st, const TnConv* cv, bool h2) {
   const TnConv none{};
