@@ -153,6 +153,17 @@ SIGNATURES = {
     "gnm_resolve_rounds": (_i32, [_i64] * 4 + [_p] * 4 + [_i64] * 3 + [_p] * 3 + [_sz, _p]),
     "gnm_resolve_layout": (_i32, [_i64] * 4 + [_p] * 4 + [_i64] + [_p] * 10 + [_sz, _p]),
     "gnm_overlap_align_host": (_i32, [_i64] + [_p] * 4 + [_i64, _p, _p, _i64, _i64, _i32] + [_p] * 4 + [_i32]),
+    "gnm_overlap_scan_workspace_bytes": (_sz, [_i64]),
+    "gnm_sketch_tile_bound": (_i64, [_i64, _i64]),
+    "gnm_sketch_count": (_i32, [_p, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _i64, _p, _p, _sz, _p]),
+    "gnm_sketch_emit": (_i32, [_p, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _i64, _i64] + [_p] * 5),
+    "gnm_sketch_host": (_i32, [_p, _i64, _p, _p, _i64, _i32, _i32, _i64] + [_p] * 6 + [_i32]),
+    "gnm_seed_pairs_count": (_i32, [_i64, _p, _p, _i32, _p, _p, _p, _sz, _p]),
+    "gnm_seed_pairs_emit": (_i32, [_i64] + [_p] * 5 + [_i64, _i32, _i32, _p, _i64, _p, _p, _p]),
+    "gnm_seed_pairs_host": (_i32, [_i64] + [_p] * 5 + [_i64, _i32, _i32, _i64] + [_p] * 4 + [_i32]),
+    "gnm_chain_count": (_i32, [_i64, _p, _p, _p, _p, _sz, _p]),
+    "gnm_chain_pairs": (_i32, [_i64, _p, _p, _p, _i64, _p] + [_i64] * 4 + [_p] * 8),
+    "gnm_chain_pairs_host": (_i32, [_i64, _p, _p, _p] + [_i64] * 5 + [_p] * 8 + [_i32]),
 }
 
 

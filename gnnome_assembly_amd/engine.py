@@ -2630,6 +2630,134 @@ def overlap_align_host(src, dst, prefix_length, n: int, base_off, length, packed
                                           hp(similarity), hp(rec), int(threads)), "gnm_overlap_align_host")
 
 
+OVERLAP_COUNTERS = ("reads", "kmers_valid", "minimizers", "runs", "skipped_runs", "skipped_entries", "hits", "same_read", "groups",
+                    "few_hits", "short", "contained_groups", "links", "calls")
+OVERLAP_RECORD_WORDS = len(OVERLAP_COUNTERS)   # the int64 words of a gnm_overlap_record (include/gnm.h), in order (`short`: too_short)
+SKETCH_TILE = 512                              # GNM_SKETCH_TILE: k-mer positions one workgroup of the sketch kernels owns at a time
+SKETCH_K, SKETCH_W, OVERLAP_MAX_OCC = (8, 31), (1, 64), 4096
+
+
+def _int_in(fn: str, name: str, v, lo: int, hi: int) -> int:
+    """v as an int in [lo, hi]; a bool or a float is no count."""
+    if isinstance(v, bool) or type(v).__name__ == "bool_" or not hasattr(v, "__index__") or not lo <= operator.index(v) <= hi:
+        raise ValueError(f"{fn}: {name}={v!r}: expected an integer in [{lo}, {hi}]")
+    return operator.index(v)
+
+
+def _hp(t):
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _overlap_host(fn: str, *ts):
+    if any(t is not None and t.device.type != "cpu" for t in ts):
+        raise ValueError(f"{fn}: every tensor must be a CPU tensor")
+
+
+def _new(dev, n, dt):
+    return torch.empty(int(n), dtype=dt, device=dev)
+
+
+def sketch(base_off, length, packed, k: int, w: int, rec, threads: int = 1):
+    """The minimizer sketch of every read of a packed store (include/gnm.h, "overlap graph", stage 1): (hash int64, read int32, pos
+    int32, strand uint8), ordered by read and position, on the store's device.  Device tensors: gnm_sketch_count, one read-back of
+    the size, gnm_sketch_emit.  CPU tensors: gnm_sketch_host on `threads` host threads (the same header).  rec: a contiguous int64
+    [OVERLAP_RECORD_WORDS] tensor on that device the call ADDS to."""
+    lib = _lib.load()
+    R = _seq_store_args("sketch", base_off, length, packed)
+    k, w = _int_in("sketch", "k", k, *SKETCH_K), _int_in("sketch", "w", w, *SKETCH_W)
+    _chk_record("sketch", rec, OVERLAP_RECORD_WORDS, "rec")
+    dev, nbytes = packed.device, int(packed.numel())
+    outs = lambda m: (_new(dev, m, torch.int64), _new(dev, m, torch.int32), _new(dev, m, torch.int32), _new(dev, m, torch.uint8))  # noqa: E731
+    if dev.type == "cpu":
+        _overlap_host("sketch", base_off, length, rec)
+        total = C.c_int64(0)
+        head = (_hp(packed), nbytes, _hp(base_off), _hp(length), R, k, w)
+        _lib.check(lib.gnm_sketch_host(*head, -1, None, None, None, None, C.byref(total), _hp(rec), int(threads)), "gnm_sketch_host")
+        out = outs(total.value)
+        _lib.check(lib.gnm_sketch_host(*head, total.value, *[C.c_void_p(t.data_ptr()) for t in out], C.byref(total), _hp(rec),
+                                       int(threads)), "gnm_sketch_host")
+        return out
+    _chk_dev(base_off, length, packed, rec)
+    with torch.cuda.device(dev):
+        tb = int(lib.gnm_sketch_tile_bound(R, nbytes))
+        tile_ptr, tile_off = _new(dev, R + 1, torch.int64), _new(dev, tb + 1, torch.int64)
+        need = lib.gnm_overlap_scan_workspace_bytes(max(R, tb))
+        ws = scratch(dev).ws(need)
+        head = (_ptr(packed), nbytes, _ptr(base_off), _ptr(length), R, k, w, _ptr(tile_ptr), _ptr(tile_off), tb)
+        _call("gnm_sketch_count", *head, _ptr(rec), _ptr(ws), need, _stream())
+        out = outs(int(tile_off[tb]))                        # the scan's total: the one synchronisation of the stage
+        _call("gnm_sketch_emit", *head, out[0].numel(), *[_ptr(t) for t in out], _stream())
+    return out
+
+
+def seed_pairs(hash_, read, pos, strand, length, k: int, max_occ: int, rec, threads: int = 1):
+    """The seed hits of a sketch sorted by hash (stage 2): (key int64, diag int32).  hash_ int64, read, pos int32, strand uint8 [M]
+    sorted stably by hash_; length int64 [R]: the reads' lengths.  Device or CPU tensors, as for `sketch`."""
+    lib = _lib.load()
+    M, R = int(hash_.numel()), int(length.numel())
+    k, max_occ = _int_in("seed_pairs", "k", k, *SKETCH_K), _int_in("seed_pairs", "max_occ", max_occ, 1, OVERLAP_MAX_OCC)
+    _chk_record("seed_pairs", rec, OVERLAP_RECORD_WORDS, "rec")
+    _chk_args("seed_pairs", ("hash", hash_, torch.int64, M), ("read", read, torch.int32, M), ("pos", pos, torch.int32, M),
+              ("strand", strand, torch.uint8, M), ("length", length, torch.int64, R))
+    dev = hash_.device
+    outs = lambda m: (_new(dev, m, torch.int64), _new(dev, m, torch.int32))  # noqa: E731
+    if dev.type == "cpu":
+        _overlap_host("seed_pairs", read, pos, strand, length, rec)
+        total = C.c_int64(0)
+        head = (M, _hp(hash_), _hp(read), _hp(pos), _hp(strand), _hp(length), R, k, max_occ)
+        _lib.check(lib.gnm_seed_pairs_host(*head, -1, None, None, C.byref(total), _hp(rec), int(threads)), "gnm_seed_pairs_host")
+        out = outs(total.value)
+        _lib.check(lib.gnm_seed_pairs_host(*head, total.value, *[C.c_void_p(t.data_ptr()) for t in out], C.byref(total), _hp(rec),
+                                           int(threads)), "gnm_seed_pairs_host")
+        return out
+    _chk_dev(hash_, read, pos, strand, length, rec)
+    with torch.cuda.device(dev):
+        off = _new(dev, M + 1, torch.int64)
+        need = lib.gnm_overlap_scan_workspace_bytes(M)
+        ws = scratch(dev).ws(need)
+        _call("gnm_seed_pairs_count", M, _ptr(hash_), _ptr(read), max_occ, _ptr(off), _ptr(rec), _ptr(ws), need, _stream())
+        out = outs(int(off[M]))                              # the scan's total: the one synchronisation of the stage
+        _call("gnm_seed_pairs_emit", M, _ptr(hash_), _ptr(read), _ptr(pos), _ptr(strand), _ptr(length), R, k, max_occ, _ptr(off),
+              out[0].numel(), _ptr(out[0]), _ptr(out[1]), _stream())
+    return out
+
+
+def chain_pairs(key, diag, length, band: int, min_hits: int, min_overlap: int, rec, threads: int = 1):
+    """The chains of the seed hits sorted by diag, then stably by key (stage 3): (src int32, dst int32, prefix_length int64,
+    overlap_length int64, valid uint8) [2 G] -- group g owns slots 2g (the edge) and 2g + 1 (its twin) -- and contained uint8 [R]."""
+    lib = _lib.load()
+    N, R = int(key.numel()), int(length.numel())
+    band, min_hits = _int_in("chain_pairs", "band", band, 0, 2 ** 31 - 2), _int_in("chain_pairs", "min_hits", min_hits, 1, 2 ** 31 - 2)
+    min_overlap = _int_in("chain_pairs", "min_overlap", min_overlap, 0, 2 ** 62)
+    _chk_record("chain_pairs", rec, OVERLAP_RECORD_WORDS, "rec")
+    _chk_args("chain_pairs", ("key", key, torch.int64, N), ("diag", diag, torch.int32, N), ("length", length, torch.int64, R))
+    dev = key.device
+    outs = lambda g: (_new(dev, 2 * g, torch.int32), _new(dev, 2 * g, torch.int32), _new(dev, 2 * g, torch.int64),  # noqa: E731
+                      _new(dev, 2 * g, torch.int64), _new(dev, 2 * g, torch.uint8))
+    contained = torch.zeros(R, dtype=torch.uint8, device=dev)
+    if dev.type == "cpu":
+        _overlap_host("chain_pairs", diag, length, rec)
+        total = C.c_int64(0)
+        head = (N, _hp(key), _hp(diag), _hp(length), R, band, min_hits, min_overlap)
+        _lib.check(lib.gnm_chain_pairs_host(*head, -1, None, None, None, None, None, None, C.byref(total), _hp(rec), int(threads)),
+                   "gnm_chain_pairs_host")
+        out = outs(total.value)
+        _lib.check(lib.gnm_chain_pairs_host(*head, total.value, *[C.c_void_p(t.data_ptr()) for t in out],
+                                            C.c_void_p(contained.data_ptr()), C.byref(total), _hp(rec), int(threads)),
+                   "gnm_chain_pairs_host")
+        return out + (contained,)
+    _chk_dev(key, diag, length, rec)
+    with torch.cuda.device(dev):
+        off = _new(dev, N + 1, torch.int64)
+        need = lib.gnm_overlap_scan_workspace_bytes(N)
+        ws = scratch(dev).ws(need)
+        _call("gnm_chain_count", N, _ptr(key), _ptr(off), _ptr(rec), _ptr(ws), need, _stream())
+        out = outs(int(off[N]))                              # the scan's total: the one synchronisation of the stage
+        _call("gnm_chain_pairs", N, _ptr(key), _ptr(diag), _ptr(off), out[0].numel() // 2, _ptr(length), R, band, min_hits,
+              min_overlap, *[_ptr(t) for t in out], _ptr(contained), _ptr(rec), _stream())
+    return out + (contained,)
+
+
 def optim_workspace(n: int, device) -> torch.Tensor:
     """The workspace of optim_step for flat buffers of n elements (gnm_optim_workspace_bytes), as int64 words: 8-byte aligned."""
     return torch.empty((_lib.load().gnm_optim_workspace_bytes(int(n)) + 7) // 8, dtype=torch.int64, device=device)

@@ -1023,6 +1023,83 @@ int gnm_resolve_layout(int64_t C, int64_t P, int64_t n, int64_t E, const int32_t
                        const int64_t* read_length, const float* y, void* record, int32_t* out_ptr, int32_t* out_nodes,
                        int32_t* out_edges, int64_t* out_bases, int32_t* out_wrong, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- overlap graph: all-versus-all overlaps of the reads of a packed store -- minimizer sketch, seed hits, chains ---------------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: eleven new symbols, no existing signature changes.)
+ * What the reference gets from an external overlapper (graph_dataset.py:120) and graph_parser.py: the edges of the assembly graph,
+ * for accurate long reads (errors of about 1 %), by exact minimizer matches.  Integers only; csrc/gnm_overlap.h is the arithmetic,
+ * run by the kernels and by the *_host entries alike.  The store (packed .. R) as for "contig sequences"; node 2r is read r, node
+ * 2r + 1 its reverse complement.  Between the stages the CALLER sorts (stable sorts; the package uses torch.sort).
+ *
+ * Stage 1, sketch.  A, C, G, T (codes 1, 2, 4, 8) are 0 .. 3; a k-mer that holds any other code is invalid.  k in [8, 31].  For
+ *   a valid k-mer at position p of the + strand, f is its 2k-bit value, first base most significant, r the value of its reverse
+ *   complement; f == r: skipped.  c = min(f, r), strand bit s = (r < f), h = fmix64(c) (the murmur3 64-bit finaliser, constants
+ *   0xff51afd7ed558ccd and 0xc4ceb9fe1a85ec53; a bijection).  Order key: (h, p), h unsigned.  nk = L - k + 1 (<= 0: nothing);
+ *   w in [1, 64], W = min(w, nk); every window [j, j + W), 0 <= j <= nk - W, selects its valid k-mer of smallest key, if it has
+ *   one; the read's sketch is the set of selected positions.  Output: hash (h's bit pattern as int64), read, pos int32, strand
+ *   uint8, ordered by read, then position.  A read that lies outside the store or has 2^31 - 1 bases or more gives nothing on the
+ *   device (gnm_sketch_host, which can see the lengths, refuses the latter).
+ *   gnm_sketch_count: the tile table (tiles of GNM_SKETCH_TILE k-mer positions; tile_ptr int64 [R + 1]), the entries of every tile
+ *   and their scan (tile_off int64 [tile_bound + 1], tile_bound = gnm_sketch_tile_bound(R, packed_bytes)); record ADDS reads (R),
+ *   kmers_valid, minimizers, calls (+1).  The caller reads `minimizers` (M), sizes the outputs, calls gnm_sketch_emit.
+ * Stage 2, seed hits.  Input: the M entries sorted by hash AS SIGNED int64, stably.  A run of equal hash longer than max_occ
+ *   (1 .. 4096) is skipped (skipped_runs, skipped_entries).  Otherwise every pair of its entries j < i is a hit unless both are of
+ *   one read (same_read).  With a the entry of the lower read id, b the other: rel = s_a ^ s_b; q = p_b when rel == 0, else
+ *   L_b - k - p_b; diag = p_a - q (int32): node 2a is compared with node 2b + rel, whose first base falls at diag in a.
+ *   key = a << 32 | b << 1 | rel (int64).  Order of the hits: by i, then by j ascending.
+ *   gnm_seed_pairs_count: off int64 [M + 1]; record ADDS runs, skipped_runs, skipped_entries, same_read, hits.  The caller reads
+ *   `hits` (N), calls gnm_seed_pairs_emit.
+ * Stage 3, chains.  Input: the N hits sorted by diag, then stably by key: group (a, b, rel) holds its diagonals ascending, d_0 ..
+ *   d_{g-1}.  c_i = #{j >= i : d_j <= d_i + band}; the window is the i of largest c_i, the lowest among equals; hits = c_i,
+ *   D = d_{i + (c_i - 1) / 2}.  hits < min_hits: rejected (few_hits).  With la, lb the reads' lengths:
+ *     D > 0 and D + lb > la: forward, ov = la - D: edge 2a -> 2b+rel, prefix D; twin (2b+rel)^1 -> 2a+1, prefix lb - ov;
+ *     D < 0 and D + lb < la: backward, ov = lb + D: edge 2b+rel -> 2a, prefix -D; twin 2a+1 -> (2b+rel)^1, prefix la - ov;
+ *     otherwise containment: b is contained when D >= 0 and D + lb <= la, else a; contained[read] = 1 (a plain store of the same
+ *     value by every writer; the caller zeroes the array); no edge (contained_groups).
+ *   An edge with ov < min_overlap is rejected (too_short).  Group g (in sorted order) owns slots 2g (the edge) and 2g + 1 (the
+ *   twin) of src, dst int32, prefix_length, overlap_length int64, valid uint8; a rejected group's slots read -1, -1, 0, 0, 0.  A
+ *   key that names a read outside [0, R) -- none of gnm_seed_pairs does -- is rejected under few_hits.
+ *   gnm_chain_count: off int64 [N + 1] (the group number of every group's first hit); record ADDS groups.  The caller reads
+ *   `groups` (G), calls gnm_chain_pairs, which ADDS few_hits, too_short, contained_groups, links.
+ *   One lane walks a whole group: a launch takes as long as its longest group (at most max_occ^2 hits per pair of k-mer runs).
+ * Every emit call writes nothing at or past the size it is given.  ws: gnm_overlap_scan_workspace_bytes(items) bytes, 16-byte
+ * aligned (sketch: items = max(R, tile_bound)).  *_host: HOST pointers; with capacity < 0 only *total is written (the
+ * size to allocate) and the record stays as it is; otherwise capacity >= *total is required and the record is added to as by the
+ * device calls of the stage.  One integer atomic per record word and workgroup; no workgroup waits for another: outputs and
+ * record depend on the inputs alone, not on the grid or gnm_set_occupancy_cap.  k, w, max_occ, band, min_hits out of range,
+ * counts negative or too large, a NULL or misaligned record / ws / packed, NULL arrays that the sizes need and (host) threads
+ * outside [1, 1024] are errors, returned before anything runs.                                                                      */
+#define GNM_SKETCH_TILE 512
+typedef struct gnm_overlap_record {
+  int64_t reads, kmers_valid, minimizers, runs, skipped_runs, skipped_entries, hits, same_read, groups, few_hits, too_short,
+      contained_groups, links, calls;
+} gnm_overlap_record;
+size_t gnm_overlap_scan_workspace_bytes(int64_t items);
+int64_t gnm_sketch_tile_bound(int64_t R, int64_t packed_bytes);
+int gnm_sketch_count(const uint8_t* packed, int64_t packed_bytes, const int64_t* base_off, const int64_t* length, int64_t R, int k,
+                     int w, int64_t* tile_ptr, int64_t* tile_off, int64_t tile_bound, void* record, void* ws, size_t ws_bytes,
+                     void* stream);
+int gnm_sketch_emit(const uint8_t* packed, int64_t packed_bytes, const int64_t* base_off, const int64_t* length, int64_t R, int k,
+                    int w, const int64_t* tile_ptr, const int64_t* tile_off, int64_t tile_bound, int64_t M, int64_t* hash,
+                    int32_t* read, int32_t* pos, uint8_t* strand, void* stream);
+int gnm_sketch_host(const uint8_t* packed, int64_t packed_bytes, const int64_t* base_off, const int64_t* length, int64_t R, int k,
+                    int w, int64_t capacity, int64_t* hash, int32_t* read, int32_t* pos, uint8_t* strand, int64_t* total,
+                    void* record, int threads);
+int gnm_seed_pairs_count(int64_t M, const int64_t* hash, const int32_t* read, int max_occ, int64_t* off, void* record, void* ws,
+                         size_t ws_bytes, void* stream);
+int gnm_seed_pairs_emit(int64_t M, const int64_t* hash, const int32_t* read, const int32_t* pos, const uint8_t* strand,
+                        const int64_t* length, int64_t R, int k, int max_occ, const int64_t* off, int64_t N, int64_t* key,
+                        int32_t* diag, void* stream);
+int gnm_seed_pairs_host(int64_t M, const int64_t* hash, const int32_t* read, const int32_t* pos, const uint8_t* strand,
+                        const int64_t* length, int64_t R, int k, int max_occ, int64_t capacity, int64_t* key, int32_t* diag,
+                        int64_t* total, void* record, int threads);
+int gnm_chain_count(int64_t N, const int64_t* key, int64_t* off, void* record, void* ws, size_t ws_bytes, void* stream);
+int gnm_chain_pairs(int64_t N, const int64_t* key, const int32_t* diag, const int64_t* off, int64_t G, const int64_t* length, int64_t R,
+                    int64_t band, int64_t min_hits, int64_t min_overlap, int32_t* src, int32_t* dst, int64_t* prefix_length,
+                    int64_t* overlap_length, uint8_t* valid, uint8_t* contained, void* record, void* stream);
+int gnm_chain_pairs_host(int64_t N, const int64_t* key, const int32_t* diag, const int64_t* length, int64_t R, int64_t band,
+                         int64_t min_hits, int64_t min_overlap, int64_t capacity, int32_t* src, int32_t* dst, int64_t* prefix_length,
+                         int64_t* overlap_length, uint8_t* valid, uint8_t* contained, int64_t* total, void* record, int threads);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
