@@ -2245,7 +2245,7 @@ int gnm::gemm_b3_try(int mode, int64_t M, int64_t N, int64_t K, const float* A, 
   auto al = [](const void* p, int64_t ld) { return (uintptr_t)p % 16 == 0 && ld % 4 == 0; };
   if (!al(A, lda) || !ws || ws_bytes < gemm_b3_workspace_bytes(mode, M, N, K)) return 0;
   if (mode == GNM_GEMM_TN) {            // C[M,N] = A[K,M]^T B[K,N]
-    if (bias || resid || relu || !al(B, ldb)) return 0;
+    if (bias || resid || relu || !al(B, ldb) || !al(C, ldc)) return 0;   // slab_reduce_ld_k stores float4 rows of C
     const int ncga = (int)(M / FH), ncgb = (int)(N / FH), ncls = ncga * ncgb;
     const int nslot = gemm_b3_tn_slots(K, ncls);
     const int64_t ntiles = cdiv_(K, tn_tr_rows_per_tile());

@@ -206,7 +206,7 @@ __global__ void splitk_reduce_k(GemmArgs a, int splits) {
 static void plan_split(int mode, int64_t M, int64_t N, int64_t K, int* splits, int64_t* kps) {
   *splits = 1;
   *kps = (K + BK - 1) / BK * BK;
-  if (mode != GNM_GEMM_TN) return;
+  if (mode != GNM_GEMM_TN || K == 0) return;   // K == 0: one split of no k-tiles (the epilogue of a zero product)
   const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   const int64_t ktiles = (K + BK - 1) / BK;
   int64_t want = ((int64_t)num_cus() * 4 + tiles - 1) / tiles;  // ~4 workgroups per CU

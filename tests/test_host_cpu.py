@@ -414,3 +414,11 @@ def test_any_hidden_edge_scores_runs_as_zero_padded_pieces():
         assert torch.allclose(got, want, rtol=1e-12, atol=1e-12)
     m = G.GraphGatedGCNModel(1, 2, 32, 16, 1, 300, False, 16)
     assert m.predictor.W1.weight.shape == (300, 96) and m.predictor.W2.weight.shape == (1, 300)
+
+
+def test_gemm_workspace_planning_accepts_k_zero(lib):
+    """K = 0 is a legal extent of gnm_gemm_f32 (the epilogue of a zero product): planning the k-splits of a TN product must not
+    divide by its zero k-tiles."""
+    for mode in (0, 1, 2):
+        assert lib.gnm_gemm_f32_workspace_bytes(mode, 128, 128, 0) == 0
+    assert lib.gnm_gemm_tn_colsum_workspace_bytes(128, 128, 0) == lib.gnm_colsum_workspace_bytes(0, 128)
