@@ -164,6 +164,12 @@ SIGNATURES = {
     "gnm_chain_count": (_i32, [_i64, _p, _p, _p, _p, _sz, _p]),
     "gnm_chain_pairs": (_i32, [_i64, _p, _p, _p, _i64, _p] + [_i64] * 4 + [_p] * 8),
     "gnm_chain_pairs_host": (_i32, [_i64, _p, _p, _p] + [_i64] * 5 + [_p] * 8 + [_i32]),
+    "gnm_gt_workspace_bytes": (_sz, [_i64, _i64]),
+    "gnm_gt_sweeps": (_i32, []),
+    "gnm_gt_prepare": (_i32, [_i64, _i64] + [_p] * 9 + [_p] * 4 + [_p, _sz, _p]),
+    "gnm_gt_rounds": (_i32, [_i64, _i64] + [_p] * 9 + [_i32, _i64, _i64, _p] + [_p, _sz, _p]),
+    "gnm_gt_emit": (_i32, [_i64, _i64] + [_p] * 9 + [_p] * 9 + [_p, _sz, _p]),
+    "gnm_gt_labels_host": (_i32, [_i64, _i64] + [_p] * 12),
 }
 
 

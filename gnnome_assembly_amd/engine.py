@@ -2758,6 +2758,92 @@ def chain_pairs(key, diag, length, band: int, min_hits: int, min_overlap: int, r
     return out + (contained,)
 
 
+GT_COUNTERS = ("edges", "valid", "wrong_strand", "self_loops", "gap", "backward", "components", "singletons", "backbone", "positives",
+               "twin_missing", "invalid", "calls")
+GT_RECORD_WORDS = len(GT_COUNTERS)         # the int64 words of a gnm_gt_record (include/gnm.h), in order
+GT_ROUNDS_PER_BATCH = 8                    # rounds enqueued per read-back of their `changed` words
+_GT_INDEX_KEYS = ("perm", "isrc", "idst", "in_ptr", "out_ptr", "out_pos", "out_dst")
+_GT_STAGES = ("components", "fwd", "bwd")
+
+
+def gt_sweeps() -> int:
+    """gnm_gt_sweeps: the sweeps a workgroup makes over its nodes per fwd / bwd round."""
+    return int(_lib.load().gnm_gt_sweeps())
+
+
+def _gt_args(fn, n, E, start, end, strand, twin, y, valid, backbone, component, top, rec):
+    """The argument rules gt_labels and gt_labels_host share."""
+    _chk_record(fn, rec, GT_RECORD_WORDS, "rec")
+    _chk_args(fn, ("read_start", start, torch.int64, n), ("read_end", end, torch.int64, n), ("read_strand", strand, torch.int64, n),
+              ("twin", twin, torch.int64, E), ("y", y, torch.float32, E), ("valid", valid, torch.uint8, E),
+              ("backbone", backbone, torch.uint8, n), ("component", component, torch.int32, n), ("top", top, torch.int32, n),
+              optional=("twin",))
+
+
+_GT_INVALID = "every node needs 0 <= read_start < read_end < 2^32 and read_strand +1 or -1"
+
+
+@on_device_of(lambda idx, src, dst, start, end, strand, twin, y, *a, **k: y)
+def gt_labels(idx, src, dst, start, end, strand, twin, y, valid, backbone, component, top, rec, rounds_per_batch=None):
+    """Ground-truth labels of one graph on the device (include/gnm.h, "ground-truth labels"): gnm_gt_prepare, then the three stages
+    of gnm_gt_rounds in batches of `rounds_per_batch` rounds (default GT_ROUNDS_PER_BATCH) with one read-back of the batch's
+    `changed` words each, then gnm_gt_emit.  idx: the graph's index (dict of graph.index(device)); src, dst int32 [E]: the caller's
+    edge list (read only to check `twin`); start, end, strand int64 [n] in the caller's numbering; twin: None or int64 [E];
+    y fp32 [E], valid uint8 [E], backbone uint8 [n], component, top int32 [n]: the outputs; rec: a contiguous int64
+    [GT_RECORD_WORDS] device tensor the call ADDS to.  Returns the rounds every stage took, the confirming round included (they
+    depend on the schedule; nothing else does).  Unusable node values raise ValueError before any output is written."""
+    lib = _lib.load()
+    n, E = int(idx["in_ptr"].numel()) - 1, int(idx["perm"].numel())
+    nperm, nrank = idx.get("nperm"), idx.get("nrank")
+    _chk_dev(src, dst, start, end, strand, twin, y, valid, backbone, component, top, rec, nperm, nrank, *[idx[k] for k in _GT_INDEX_KEYS])
+    _gt_args("gt_labels", n, E, start, end, strand, twin, y, valid, backbone, component, top, rec)
+    _chk_args("gt_labels", ("src", src, torch.int32, E), ("dst", dst, torch.int32, E), ("nrank", nrank, torch.int32, n),
+              optional=("nrank",))
+    _chk_index("gt_labels", idx, _GT_INDEX_KEYS, n)
+    if (nperm is None) != (nrank is None):
+        raise ValueError("gt_labels: the index carries nperm without nrank (graph.index())")
+    batch = _int_in("gt_labels", "rounds_per_batch", GT_ROUNDS_PER_BATCH if rounds_per_batch is None else rounds_per_batch, 1, 4096)
+    dev = y.device
+    need = int(lib.gnm_gt_workspace_bytes(n, E))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    head = (n, E, *[_ptr(idx[k]) for k in _GT_INDEX_KEYS], _ptr(nperm), _ptr(nrank))
+    tail = (_ptr(ws), need, _stream())
+    _call("gnm_gt_prepare", *head, _ptr(start), _ptr(end), _ptr(strand), _ptr(rec), *tail)
+    changed = torch.empty(batch, dtype=torch.int64, device=dev)
+    rounds = {}
+    for stage, name in enumerate(_GT_STAGES):
+        done = 0
+        while True:
+            _call("gnm_gt_rounds", *head, stage, done, batch, _ptr(changed), *tail)
+            got = changed.tolist()                           # the batch's one read-back
+            if got[0] < 0:
+                raise ValueError(f"gt_labels: {_GT_INVALID}")
+            if 0 in got:
+                done += got.index(0) + 1
+                break
+            done += batch
+        rounds[name] = done
+    _call("gnm_gt_emit", *head, _ptr(twin), _ptr(src), _ptr(dst), _ptr(y), _ptr(valid), _ptr(backbone), _ptr(component), _ptr(top),
+          _ptr(rec), *tail)
+    return rounds
+
+
+def gt_labels_host(src, dst, n: int, start, end, strand, twin, y, valid, backbone, component, top, rec):
+    """gt_labels on CPU tensors over the caller's edge list (gnm_gt_labels_host: the same header, union-find and queues; no index).
+    Unusable node values raise ValueError and write nothing but rec's `invalid` word."""
+    lib = _lib.load()
+    n, E = int(n), int(src.numel())
+    _overlap_host("gt_labels_host", src, dst, start, end, strand, twin, y, valid, backbone, component, top, rec)
+    _gt_args("gt_labels_host", n, E, start, end, strand, twin, y, valid, backbone, component, top, rec)
+    _chk_args("gt_labels_host", ("src", src, torch.int32, E), ("dst", dst, torch.int32, E))
+    rc = lib.gnm_gt_labels_host(n, E, _hp(src), _hp(dst), _hp(start), _hp(end), _hp(strand), _hp(twin), _hp(y), _hp(valid),
+                                _hp(backbone), _hp(component), _hp(top), _hp(rec))
+    if rc != 0 and b"unusable" in lib.gnm_last_error():
+        raise ValueError(f"gt_labels_host: {_GT_INVALID}, and every edge two nodes below n")
+    _lib.check(rc, "gnm_gt_labels_host")
+    return {name: 0 for name in _GT_STAGES}
+
+
 def optim_workspace(n: int, device) -> torch.Tensor:
     """The workspace of optim_step for flat buffers of n elements (gnm_optim_workspace_bytes), as int64 words: 8-byte aligned."""
     return torch.empty((_lib.load().gnm_optim_workspace_bytes(int(n)) + 7) // 8, dtype=torch.int64, device=device)

@@ -1100,6 +1100,57 @@ int gnm_chain_pairs_host(int64_t N, const int64_t* key, const int32_t* diag, con
                          int64_t min_hits, int64_t min_overlap, int64_t capacity, int32_t* src, int32_t* dst, int64_t* prefix_length,
                          int64_t* overlap_length, uint8_t* valid, uint8_t* contained, int64_t* total, void* record, int threads);
 
+/* ---- ground-truth labels: y per edge from the reads' positions -- components, forward and backward reachability, emit ----------------
+ * (Added without raising GNM_ABI_VERSION, which stays 7: six new symbols, no existing signature changes.)
+ * What the reference computes with algorithms.get_gt_graph (graph_parser.py:307-309), restated so that it does not depend on a walk
+ * order.  Per node (the caller's numbering; v and v^1 are the two strands of a read) start, end, strand int64 with
+ * 0 <= start < end < 2^32 and strand +1 or -1.  Edge s -> d is VALID when strand[s] == strand[d] == +1, s != d and
+ * start[s] <= start[d] < end[s]; every other edge falls under the first that applies of wrong_strand, self_loops, gap
+ * (start[d] >= end[s]), backward (start[d] < start[s]).  Over the + strand nodes and the valid edges: the weakly connected
+ * components, the ROOT of each the node of smallest (start, id); fwd = what a root reaches; the TOP of a component = the node of fwd
+ * with the largest end, the smallest id among equals; bwd = what reaches the top; backbone = fwd and bwd (a component of one node
+ * is its own backbone and labels nothing).  y = 1 for every valid edge with both ends on the backbone and for every copy of its
+ * mirror d^1 -> s^1, else 0.  twin_missing counts the copies of such edges whose mirror the graph does not hold.
+ * Device calls, over the index of gnm_graph_build_index (nperm / nrank: both NULL, or the internal numbering and its inverse):
+ * gnm_gt_prepare (a memset and 2 launches): checks the nodes, classifies the edges; record ADDS edges, valid, wrong_strand,
+ *   self_loops, gap, backward, invalid (unusable nodes; everything later then does nothing), calls (+1).
+ * gnm_gt_rounds (1 - 3 + rounds launches): rounds first_round .. first_round + rounds - 1 of stage 0 (components: min-label hooking
+ *   with pointer jumping over the valid edges, 64-bit atomicMin), 1 (fwd) or 2 (bwd; its first round selects the tops by a 64-bit
+ *   atomicMax); changed[j] (int64 [rounds]) = what round first_round + j lowered or reached, -1 for invalid input.  The caller runs a
+ *   stage until a round reports 0 and the stages in order; a round on a finished stage changes nothing.  How many rounds a stage
+ *   takes depends on the schedule; what it ends in does not.
+ * gnm_gt_emit (2 launches), after stage 2: y fp32, valid uint8 [E] in edge-id order; backbone uint8, component (the root's id),
+ *   top int32 [n] (-1 on - strand nodes); record ADDS components, singletons, backbone, positives, twin_missing.  twin: NULL (the
+ *   mirror is searched in the out-row), or int64 [E] mirror edge ids with src, dst the caller's edge list: an entry is believed only
+ *   when it names the mirrored pair.
+ * ws: gnm_gt_workspace_bytes(n, E) bytes, 16-byte aligned, the same for all calls of one graph and untouched in between.
+ * gnm_gt_sweeps(): the sweeps a workgroup makes over its nodes per fwd / bwd round.
+ * gnm_gt_labels_host: all of it on HOST pointers over the caller's edge list (union-find and queues over the same header,
+ *   csrc/gnm_labels.h); invalid input is an error and writes nothing but record.invalid.
+ * Integers only; the outputs and the record depend on the inputs alone, not on the grid or gnm_set_occupancy_cap.  Counts negative
+ * or >= 2^31 - 1, a NULL or misaligned record / ws / changed and NULL arrays that the sizes need are errors, returned before
+ * anything is launched.                                                                                                            */
+typedef struct gnm_gt_record {
+  int64_t edges, valid, wrong_strand, self_loops, gap, backward, components, singletons, backbone, positives, twin_missing, invalid,
+      calls;
+} gnm_gt_record;
+size_t gnm_gt_workspace_bytes(int64_t n, int64_t E);
+int gnm_gt_sweeps(void);
+int gnm_gt_prepare(int64_t n, int64_t E, const int32_t* perm, const int32_t* isrc, const int32_t* idst, const int32_t* in_ptr,
+                   const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, const int32_t* nperm, const int32_t* nrank,
+                   const int64_t* start, const int64_t* end, const int64_t* strand, void* record, void* ws, size_t ws_bytes,
+                   void* stream);
+int gnm_gt_rounds(int64_t n, int64_t E, const int32_t* perm, const int32_t* isrc, const int32_t* idst, const int32_t* in_ptr,
+                  const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, const int32_t* nperm, const int32_t* nrank,
+                  int stage, int64_t first_round, int64_t rounds, int64_t* changed, void* ws, size_t ws_bytes, void* stream);
+int gnm_gt_emit(int64_t n, int64_t E, const int32_t* perm, const int32_t* isrc, const int32_t* idst, const int32_t* in_ptr,
+                const int32_t* out_ptr, const int32_t* out_pos, const int32_t* out_dst, const int32_t* nperm, const int32_t* nrank,
+                const int64_t* twin, const int32_t* src, const int32_t* dst, float* y, uint8_t* valid, uint8_t* backbone,
+                int32_t* component, int32_t* top, void* record, void* ws, size_t ws_bytes, void* stream);
+int gnm_gt_labels_host(int64_t n, int64_t E, const int32_t* src, const int32_t* dst, const int64_t* start, const int64_t* end,
+                       const int64_t* strand, const int64_t* twin, float* y, uint8_t* valid, uint8_t* backbone, int32_t* component,
+                       int32_t* top, void* record);
+
 /* ---- composite entry points (ABI 5): the measured path's launch sequences behind one call each -------------------------
  * For hosts that do not want to schedule the kernels themselves (a C++ trainer, a Go / Rust / Java binding).  Host code only:
  * every arithmetic step is one of the entry points above, called in the order the Python engine calls them on ONE stream, so
