@@ -2187,7 +2187,8 @@ extern "C" int gnm_edge_bwd_fused_gt(int64_t E, int H, const float* ge, float* g
 static int tn_colgroups(int64_t N, const float* A, int64_t lda, int ncg, const float* B, float* gW, float* gb,
                         double* partials, float* slab, void* stream, int max_blocks_per_cu = 0, const TnConv* cv = nullptr) {
   hipStream_t st = (hipStream_t)stream;
-  const bool tr = g_matmul_mode || cv;                   // split mode: tn_tr_k (transpose reads); fp32-MFMA mode: tn_colgroup_k
+  // split mode: tn_tr_k (transpose reads); fp32-MFMA mode, and fewer rows than one tile of tn_tr_k in any mode: tn_colgroup_k
+  const bool tr = cv || (g_matmul_mode && N >= tn_tr_rows_per_tile());
   const int64_t ntiles = cdiv_(N, tr ? tn_tr_rows_per_tile() : FTR);
   const bool h2 = g_matmul_mode == 2;                    // f16x2 (tn_tr_k<., ., true>)
   int occ = tr ? tn_tr_occupancy(cv != nullptr, h2) : occ_blocks<tn_colgroup_k<MmF32>>();
@@ -2380,6 +2381,8 @@ extern "C" int gnm_node_proj_bwd(int64_t N, int H, int ncols, const float* gP, c
                                  const float* gh_out, float* gh_in, float* gW, float* gb, double* partials,
                                  void* ws, size_t ws_bytes, void* stream) {
   GNM_CHECK_ARG(ws && ws_bytes >= gnm_node_proj_bwd_workspace_bytes(ncols), "node_proj_bwd: workspace too small");
+  // the second half's own pointers, before the first half launches: a refused call writes nothing
+  GNM_CHECK_ARG(h_in && gW && gb && partials, "node_proj_bwd: bad argument");
   const int rc = gnm_node_proj_bwd_nn(N, H, ncols, gP, W, gh_out, gh_in, ws, ws_bytes, stream);
   return rc ? rc : gnm_node_proj_bwd_tn(N, H, ncols, gP, h_in, gW, gb, partials, ws, ws_bytes, 0, stream);
 }
@@ -2409,6 +2412,10 @@ extern "C" int gnm_tn128_bgrad(int64_t M, int H, const float* UT, const float* U
   GNM_CHECK_ARG(M > 0 && UT && Ud && Td && (ud_pitch == H || ud_pitch == 2 * H) && stat_e && bstat_e && gamma_e && in_ptr &&
                     out_ptr && gP && B && out && colsum && partials, "tn128_bgrad: bad argument");
   GNM_CHECK_ARG(ws && ws_bytes >= gnm_tn128_workspace_bytes(), "tn128_bgrad: workspace too small");
+  if (M < tn_tr_rows_per_tile()) {     // shorter than one tile (see tn_colgroups): the groups by gnm_node_bgrad, then the fp32-MFMA kernel
+    const int rc = gnm_node_bgrad(M, H, stat_e, bstat_e, gamma_e, in_ptr, out_ptr, UT, Ud, Td, ud_pitch, gP, stream);
+    return rc ? rc : tn_colgroups(M, gP + 3 * H, (int64_t)5 * H, 2, B, out, colsum, partials, (float*)ws, stream);
+  }
   const TnConv cv{{UT, Ud}, {UT + H, Td}, {(int64_t)2 * H, ud_pitch}, {out_ptr, in_ptr}, stat_e, bstat_e, gamma_e,
                   gP + 3 * H, (int64_t)5 * H};
   return tn_colgroups(M, nullptr, 0, 2, B, out, colsum, partials, (float*)ws, stream, 0, &cv);

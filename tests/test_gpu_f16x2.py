@@ -5,7 +5,7 @@ driven with operands that would leave the fp16 exponent range under a fixed scal
 columns spread over many decades, gradients of 1e-7, zero rows, a row 1e12 above all others, magnitudes that jump by 1e8 from
 one tile to the next) and must stay as close to an fp64 evaluation as the fp32-MFMA mode does: rel-L2 <= 2e-6 and no worse
 than 1.5x the fp32 mode's + 1e-7, componentwise |err| <= 4e-6 (|x| |W| + |other terms|) where the kernel scales per row, finite
-everywhere."""
+everywhere.  (Sizes and tile edges of the node projection kernels, per element against fp64: tests/test_gpu_node_proj_kernels.py.)"""
 import ctypes as C
 
 import numpy as np
