@@ -16,9 +16,9 @@
 //                     off = prefix_length[pedge]).
 //   bog_rank_k  x K   round: a node whose ptr is live adds the record of ptr[v] to its own and takes over its ptr (a further
 //                     pointer, or the finished ~head).  The last round also stores the path's length at its head.
-//   bog_bsum_k, bog_scan_k, bog_apply_k   exclusive prefix sums in NODE order of the head flags (-> contig number) and of the
-//                     lengths stored at the heads (-> contig_ptr), in three phases over fixed blocks of kBogBlk nodes: their
-//                     sums, one workgroup per sequence over the block sums, in-block scan (gnm_group.h).
+//   scan_launch       exclusive prefix sums in NODE order of the head flags (-> contig number) and of the lengths stored at the
+//                     heads (-> contig_ptr): the three launches of gnm_scan.h over blocks of 4 kBlock nodes, a thread owning four
+//                     consecutive nodes (BogScan).
 //   bog_layout_k      walk_nodes / walk_edges at contig_ptr[c] + rank, contig_bases / contig_wrong from the tails, the counters.
 // Every round reads one generation and writes the other (ping-pong): no kernel reads what the same launch writes, no workgroup
 // waits for another, there is no flag, no cooperative launch and no read-back between the launches.  A node's state is one
@@ -29,20 +29,19 @@
 // Bounds.  A table entry outside [0, E) and a src / dst entry outside [0, n) drop the candidate before they address anything;
 // pointers kept in the workspace are built from checked values and are checked again where they address a caller's array.
 #include "gnm_common.h"
-#include "gnm_group.h"
+#include "gnm_scan.h"
 
 namespace gnm {
 
-constexpr int kBogBlk = 4 * kBlock;      // nodes per scan block: thread t owns the four consecutive nodes 4t .. 4t+3
 enum { kBogContigs = 0, kBogLinks, kBogCyclesCut, kBogDropped, kBogWrongLinks, kBogMultiNodes, kBogMultiContigs, kBogCalls };
 
 struct BogArgs {
-  int64_t n, E, nb;                      // nb: scan blocks
+  int64_t n, E;
   const int32_t *src, *dst, *best_succ, *best_pred;
   const float *scores, *y;
   const int64_t *prefix_length, *read_length;
   float min_logit;
-  int32_t *next, *prev, *pedge, *plen, *pre_f, *pre_l, *bsum[2];
+  int32_t *next, *prev, *pedge, *plen, *pre_f, *pre_l;
   int2* mn[2];                           // cycle pass: (ptr, min); lives in ra[1], which the ranking pass writes only later
   int4* ra[2];                           // ranking pass: (ptr or ~head, rank, wrong, 0)
   int64_t* ro[2];                        // ... and off
@@ -151,60 +150,36 @@ __global__ __launch_bounds__(kBlock) void bog_rank_k(BogArgs a, int g, int last)
   }
 }
 
-// four consecutive values of the two scanned sequences: head flags, lengths kept at the heads
-__device__ __forceinline__ void bog_ld4_(const BogArgs& a, int64_t k0, int f[4], int l[4]) {
-  if (k0 + 3 < a.n) {
-    const int4 p = *reinterpret_cast<const int4*>(a.prev + k0), q = *reinterpret_cast<const int4*>(a.plen + k0);
-    f[0] = p.x < 0; f[1] = p.y < 0; f[2] = p.z < 0; f[3] = p.w < 0;
-    l[0] = q.x; l[1] = q.y; l[2] = q.z; l[3] = q.w;
-  } else {
+// The two scanned sequences, in node order: head flags (-> contig number, pre_f) and the lengths kept at the heads (-> pre_l).
+struct BogScan : ScanUser<int32_t, 2> {
+  BogArgs a;
+  __device__ __forceinline__ void load(const Arrays& x, int64_t k0, bool, int32_t (&v)[2][4]) const {
+    int32_t f[4], l[4];                                  // (written straight into v, the rows end up in scratch memory)
+    if (k0 + 3 < x.n) {
+      const int4 p = *reinterpret_cast<const int4*>(a.prev + k0), q = *reinterpret_cast<const int4*>(a.plen + k0);
+      f[0] = p.x < 0; f[1] = p.y < 0; f[2] = p.z < 0; f[3] = p.w < 0;
+      l[0] = q.x; l[1] = q.y; l[2] = q.z; l[3] = q.w;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        f[i] = k0 + i < x.n ? a.prev[k0 + i] < 0 : 0;
+        l[i] = k0 + i < x.n ? a.plen[k0 + i] : 0;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      f[i] = k0 + i < a.n ? a.prev[k0 + i] < 0 : 0;
-      l[i] = k0 + i < a.n ? a.plen[k0 + i] : 0;
+      v[0][i] = f[i];
+      v[1][i] = l[i];
     }
   }
-}
-
-__global__ __launch_bounds__(kBlock) void bog_bsum_k(BogArgs a) {
-  __shared__ int red[kWavesPerBlock];
-  for (int64_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
-    int f[4], l[4];
-    bog_ld4_(a, b * kBogBlk + 4 * (int64_t)threadIdx.x, f, l);
-    const int sf = block_sum(f[0] + f[1] + f[2] + f[3], red), sl = block_sum(l[0] + l[1] + l[2] + l[3], red);
-    if (threadIdx.x == 0) {
-      a.bsum[0][b] = sf;
-      a.bsum[1][b] = sl;
-    }
-  }
-}
-
-// Workgroup s turns the block sums of sequence s into their exclusive prefix, in place (scan_block_sums).  The flag
-// sequence's total is the contig count C: contig_ptr[C] = n (every node lies on one path), record.contigs += C, calls += 1.
-__global__ __launch_bounds__(kBlock) void bog_scan_k(BogArgs a) {
-  __shared__ int lds[kWavesPerBlock];
-  const int s = blockIdx.x;
-  int total;
-  scan_block_sums(a.bsum[s], a.nb, lds, total);
-  if (s == 0 && threadIdx.x == 0) {
+  // The flag sequence's total is the contig count C: contig_ptr[C] = n (every node lies on one path), record.contigs += C, calls += 1.
+  __device__ __forceinline__ void total(const Arrays&, int s, int32_t total) const {
+    if (s != 0) return;
     if (a.contig_ptr && total >= 0 && (int64_t)total <= a.n) a.contig_ptr[total] = (int32_t)a.n;
     if (total > 0) atomicAdd(a.rec + kBogContigs, (unsigned long long)total);
     atomicAdd(a.rec + kBogCalls, 1ull);
   }
-}
-
-__global__ __launch_bounds__(kBlock) void bog_apply_k(BogArgs a) {
-  __shared__ int lds[kWavesPerBlock];
-  for (int64_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
-    const int64_t k0 = b * kBogBlk + 4 * (int64_t)threadIdx.x;
-    int f[4], l[4], total;
-    bog_ld4_(a, k0, f, l);
-    const int x0 = a.bsum[0][b] + block_scan_excl(f[0] + f[1] + f[2] + f[3], lds, total);
-    const int y0 = a.bsum[1][b] + block_scan_excl(l[0] + l[1] + l[2] + l[3], lds, total);
-    store4_excl(a.pre_f, k0, a.n, x0, f);
-    store4_excl(a.pre_l, k0, a.n, y0, l);
-  }
-}
+};
 
 __global__ __launch_bounds__(kBlock) void bog_layout_k(BogArgs a, int g) {
   __shared__ unsigned lds[kWavesPerBlock];
@@ -257,11 +232,10 @@ struct BogLayout {
 static BogLayout bog_layout(int64_t n) {
   BogLayout l;
   size_t off = 0;
-  const size_t nb = (size_t)((n + kBogBlk - 1) / kBogBlk);
   for (int g = 0; g < 2; ++g) { l.ra[g] = off; off += ws_pad((size_t)n * 16); }
   for (int g = 0; g < 2; ++g) { l.ro[g] = off; off += ws_pad((size_t)n * 8); }
   for (int i = 0; i < 6; ++i) { l.i32[i] = off; off += ws_pad((size_t)n * 4); }
-  for (int s = 0; s < 2; ++s) { l.bsum[s] = off; off += ws_pad(nb * 4); }
+  for (int s = 0; s < 2; ++s) { l.bsum[s] = off; off += scan_bsum_bytes<int32_t, 4>(n); }
   l.bytes = off;
   return l;
 }
@@ -289,35 +263,31 @@ extern "C" int gnm_bog_contigs(int64_t n, int64_t E, const int32_t* src, const i
   hipStream_t st = (hipStream_t)stream;
   char* w = (char*)ws;
   BogArgs a;
-  a.n = n; a.E = E; a.nb = (n + kBogBlk - 1) / kBogBlk;
+  a.n = n; a.E = E;
   a.src = src; a.dst = dst; a.best_succ = best_succ; a.best_pred = best_pred; a.scores = scores; a.y = y;
   a.prefix_length = prefix_length; a.read_length = read_length; a.min_logit = min_logit;
   for (int g = 0; g < 2; ++g) {
     a.ra[g] = (int4*)(w + l.ra[g]);
     a.ro[g] = (int64_t*)(w + l.ro[g]);
     a.mn[g] = (int2*)(w + l.ra[1] + (size_t)g * (size_t)n * 8);               // both inside ra[1]: 2 x 8 n = 16 n bytes
-    a.bsum[g] = (int32_t*)(w + l.bsum[g]);
   }
   a.next = (int32_t*)(w + l.i32[0]); a.prev = (int32_t*)(w + l.i32[1]); a.pedge = (int32_t*)(w + l.i32[2]);
   a.plen = (int32_t*)(w + l.i32[3]); a.pre_f = (int32_t*)(w + l.i32[4]); a.pre_l = (int32_t*)(w + l.i32[5]);
   a.contig_ptr = contig_ptr; a.walk_nodes = walk_nodes; a.walk_edges = walk_edges; a.contig_wrong = contig_wrong;
   a.contig_bases = contig_bases;
   a.rec = (unsigned long long*)record;
+  int K = 1;
+  while (((int64_t)1 << K) < n) ++K;                    // ceil(log2(max(n, 2)))
+  const dim3 grid(persistent_grid(n, kBlock, 8)), blk(kBlock);
   if (n > 0) {
-    int K = 1;
-    while (((int64_t)1 << K) < n) ++K;                  // ceil(log2(max(n, 2)))
-    const dim3 grid(persistent_grid(n, kBlock, 8)), sgrid(persistent_grid(a.nb, 1, 8)), blk(kBlock);
     hipLaunchKernelGGL(bog_link_k, grid, blk, 0, st, a);
     for (int r = 0; r < K; ++r) hipLaunchKernelGGL(bog_min_k, grid, blk, 0, st, a, r & 1);
     hipLaunchKernelGGL(bog_rank_init_k, grid, blk, 0, st, a, K & 1);
     for (int r = 0; r < K; ++r) hipLaunchKernelGGL(bog_rank_k, grid, blk, 0, st, a, r & 1, r == K - 1 ? 1 : 0);
-    hipLaunchKernelGGL(bog_bsum_k, sgrid, blk, 0, st, a);
-    hipLaunchKernelGGL(bog_scan_k, dim3(2), blk, 0, st, a);
-    hipLaunchKernelGGL(bog_apply_k, sgrid, blk, 0, st, a);
-    hipLaunchKernelGGL(bog_layout_k, grid, blk, 0, st, a, K & 1);
-  } else {
-    hipLaunchKernelGGL(bog_scan_k, dim3(2), dim3(kBlock), 0, st, a);          // contig_ptr[0] = 0, calls += 1
   }
+  // n == 0: the middle phase alone -- contig_ptr[0] = 0, calls += 1
+  scan_launch<int32_t, 4, 2>(BogScan{{}, a}, {n, {(int32_t*)(w + l.bsum[0]), (int32_t*)(w + l.bsum[1])}, {a.pre_f, a.pre_l}}, st);
+  if (n > 0) hipLaunchKernelGGL(bog_layout_k, grid, blk, 0, st, a, K & 1);
   GNM_LAUNCH_CHECK("bog_contigs");
   return 0;
 }

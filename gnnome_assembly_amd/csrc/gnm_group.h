@@ -1,6 +1,6 @@
-// Device helpers shared by the integer index kernels (gnm_decision, gnm_cover, gnm_reduce, gnm_bog, gnm_seq, gnm_align,
-// gnm_induce): wave and workgroup sums, the workgroup exclusive scan and the scan of block sums built on it, and the walk of
-// eight lanes per node over the graph index.  Integer only: sums and maxima commute, so every result is a function of the
+// Device helpers shared by the integer index kernels (gnm_decision, gnm_cover, gnm_reduce, gnm_align, gnm_induce, and through
+// gnm_scan.h -- the one three-phase prefix sum -- gnm_overlap, gnm_seq, gnm_bog, gnm_resolve): wave and workgroup sums, the workgroup
+// exclusive scan and the scan of block sums built on it, and the walk of eight lanes per node over the graph index.  Integer only: sums and maxima commute, so every result is a function of the
 // inputs alone, whatever the grid.  Workgroups are kBlock threads; "every thread calls it" means all kBlock of them.
 #pragma once
 #include "gnm_common.h"

@@ -1,8 +1,8 @@
 // Overlap graph from the reads on the device (include/gnm.h, "overlap graph"): minimizer sketch -> seed hits -> chains.  The
 // arithmetic is csrc/gnm_overlap.h; this file is the launches, the counters and the host twins.  Every stage is count / scan / emit:
-// the count pass leaves one int64 per item in `off`, the three-phase scan of gnm_group.h turns it into offsets IN PLACE
-// (ovl_bsum_k, ovl_scan_k by one workgroup, ovl_apply_k) and adds the total to one record word; the caller reads that word, sizes
-// the outputs and calls the emit pass, which writes nothing at or past the size it was given.
+// the count pass leaves one int64 per item in `off`, the three-phase scan of gnm_scan.h turns it into offsets IN PLACE (ovl_scan:
+// its three launches with OvlScan as their user) and adds the total to one record word; the caller reads that word, sizes the
+// outputs and calls the emit pass, which writes nothing at or past the size it was given.
 //
 // gnm_sketch_count / _emit: sk_ntiles_k (tiles of kSketchTile k-mer positions per read) + scan = the tile table; sk_tile_k, ONE
 //   WORKGROUP PER TILE, grid-stride: thread 0 finds the tile's read by binary search in the table; kSketchWords threads unpack 32
@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "gnm_common.h"
-#include "gnm_group.h"
+#include "gnm_scan.h"
 #include "gnm_overlap.h"
 
 namespace gnm {
@@ -29,32 +29,14 @@ static_assert(kSketchTile == 2 * kBlock, "sk_tile_k: every thread owns two conse
 static_assert(kSketchWords <= kBlock, "sk_tile_k: one thread per word of bases");
 
 // ---- the scan every stage shares: off[0 .. n) counts -> exclusive offsets in place, off[n] = the total ---------------------------
-__global__ __launch_bounds__(kBlock) void ovl_bsum_k(const int64_t* off, int64_t n, int64_t nb, int64_t* bsum) {
-  __shared__ int64_t lds64[kWavesPerBlock];
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const int64_t p = b * kBlock + threadIdx.x;
-    const int64_t t = block_sum<int64_t>(p < n ? off[p] : 0, lds64);
-    if (threadIdx.x == 0) bsum[b] = t;
-  }
-}
-__global__ __launch_bounds__(kBlock) void ovl_scan_k(int64_t* bsum, int64_t nb, int64_t* total_out, unsigned long long* rec_word) {
-  __shared__ int64_t lds64[kWavesPerBlock];
-  int64_t total;
-  scan_block_sums(bsum, nb, lds64, total);
-  if (threadIdx.x == 0) {
-    *total_out = total;
+struct OvlScan : ScanUser<int64_t, 1> {
+  unsigned long long* rec_word;          // the record word the total is added to, or null
+  __device__ __forceinline__ void load(const Arrays& x, int64_t p, bool, int64_t (&v)[1][1]) const { v[0][0] = p < x.n ? x.out[0][p] : 0; }
+  __device__ __forceinline__ void total(const Arrays& x, int, int64_t total) const {
+    x.out[0][x.n] = total;
     if (rec_word && total > 0) atomicAdd(rec_word, (unsigned long long)total);
   }
-}
-__global__ __launch_bounds__(kBlock) void ovl_apply_k(int64_t* off, int64_t n, int64_t nb, const int64_t* bsum) {
-  __shared__ int64_t lds64[kWavesPerBlock];
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const int64_t p = b * kBlock + threadIdx.x;
-    int64_t total;
-    const int64_t x = bsum[b] + block_scan_excl<int64_t>(p < n ? off[p] : 0, lds64, total);
-    if (p < n) off[p] = x;
-  }
-}
+};
 __global__ void ovl_rec_add_k(unsigned long long* rec, int w0, unsigned long long v0, int w1, unsigned long long v1) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     if (v0) atomicAdd(rec + w0, v0);
@@ -62,12 +44,8 @@ __global__ void ovl_rec_add_k(unsigned long long* rec, int w0, unsigned long lon
   }
 }
 
-static void scan_launch(int64_t* off, int64_t n, int64_t* bsum, unsigned long long* rec_word, hipStream_t st) {
-  const int64_t nb = (n + kBlock - 1) / kBlock;
-  const dim3 blk(kBlock);
-  if (nb > 0) hipLaunchKernelGGL(ovl_bsum_k, dim3(persistent_grid(nb, 1, 8)), blk, 0, st, off, n, nb, bsum);
-  hipLaunchKernelGGL(ovl_scan_k, dim3(1), blk, 0, st, bsum, nb, off + n, rec_word);
-  if (nb > 0) hipLaunchKernelGGL(ovl_apply_k, dim3(persistent_grid(nb, 1, 8)), blk, 0, st, off, n, nb, bsum);
+static void ovl_scan(int64_t* off, int64_t n, int64_t* bsum, unsigned long long* rec_word, hipStream_t st) {
+  scan_launch<int64_t, 1, 1>(OvlScan{{}, rec_word}, {n, {bsum}, {off}}, st);
 }
 
 // ---- stage 1 -------------------------------------------------------------------------------------------------------------------
@@ -328,7 +306,7 @@ static int threads_check(const char* what, int threads) {
 
 extern "C" size_t gnm_overlap_scan_workspace_bytes(int64_t n) {
   if (n < 0) return 0;
-  return ws_pad((size_t)((n + kBlock - 1) / kBlock + 1) * 8);
+  return ws_pad((size_t)(scan_blocks<1>(n) + 1) * 8);
 }
 
 extern "C" int64_t gnm_sketch_tile_bound(int64_t R, int64_t packed_bytes) {
@@ -368,9 +346,9 @@ extern "C" int gnm_sketch_count(const uint8_t* packed, int64_t packed_bytes, con
   a.k = k; a.w = w; a.TB = tile_bound; a.tile_ptr = tile_ptr; a.tile_off = tile_off; a.rec = (unsigned long long*)record;
   const dim3 blk(kBlock);
   if (R > 0) hipLaunchKernelGGL(sk_ntiles_k, dim3(persistent_grid(R, kBlock, 8)), blk, 0, st, a);
-  scan_launch(tile_ptr, R, (int64_t*)ws, nullptr, st);
+  ovl_scan(tile_ptr, R, (int64_t*)ws, nullptr, st);
   if (tile_bound > 0) hipLaunchKernelGGL(sk_tile_k<false>, dim3(persistent_grid(tile_bound, 1, 8)), blk, 0, st, a);
-  scan_launch(tile_off, tile_bound, (int64_t*)ws, a.rec + kOvlMinimizers, st);
+  ovl_scan(tile_off, tile_bound, (int64_t*)ws, a.rec + kOvlMinimizers, st);
   hipLaunchKernelGGL(ovl_rec_add_k, dim3(1), dim3(64), 0, st, a.rec, (int)kOvlReads, (unsigned long long)R, (int)kOvlCalls, 1ull);
   GNM_LAUNCH_CHECK("sketch_count");
   return 0;
@@ -469,7 +447,7 @@ extern "C" int gnm_seed_pairs_count(int64_t M, const int64_t* hash, const int32_
   a.M = M; a.hash = hash; a.read = read; a.max_occ = max_occ; a.off = off;
   unsigned long long* rec = (unsigned long long*)record;
   if (M > 0) hipLaunchKernelGGL(pair_k<false>, dim3(persistent_grid((M + kBlock - 1) / kBlock, 1, 8)), dim3(kBlock), 0, st, a, rec);
-  scan_launch(off, M, (int64_t*)ws, rec + kOvlHits, st);
+  ovl_scan(off, M, (int64_t*)ws, rec + kOvlHits, st);
   GNM_LAUNCH_CHECK("seed_pairs_count");
   return 0;
 }
@@ -548,7 +526,7 @@ extern "C" int gnm_chain_count(int64_t N, const int64_t* key, int64_t* off, void
   ChainArgs a = {};
   a.N = N; a.key = key; a.off = off;
   if (N > 0) hipLaunchKernelGGL(chain_head_k, dim3(persistent_grid(N, kBlock, 8)), dim3(kBlock), 0, st, a);
-  scan_launch(off, N, (int64_t*)ws, (unsigned long long*)record + kOvlGroups, st);
+  ovl_scan(off, N, (int64_t*)ws, (unsigned long long*)record + kOvlGroups, st);
   GNM_LAUNCH_CHECK("chain_count");
   return 0;
 }

@@ -24,8 +24,9 @@
 //                                    grows and positions are unique, so a token is never used twice).
 //                   Both leave run[p] = 0 (not kept), 1 (kept) or 2 (kept, first node of its piece), kn[c] / kp[c] = kept nodes /
 //                   pieces, done[c] = r.  The contigs still undecided are counted into undecided[j]: one atomic per workgroup.
-//   res_bsum_k, res_scan_k, res_apply_k   exclusive prefix sums of kn and kp in PRIORITY order (through `order`), three phases
-//                   over fixed blocks of kResBlk contigs (gnm_group.h): where every contig's pieces and nodes start.
+//   scan_launch     exclusive prefix sums of kn and kp in PRIORITY order (through `order`): the three launches of gnm_scan.h over
+//                   blocks of 4 kBlock contigs, a thread owning four consecutive ranks (ResScan): where every contig's pieces and
+//                   nodes start.
 //   res_gather_k    the kept positions to out_nodes / out_edges (-1 at a piece's first node), out_ptr at the piece starts: wave
 //                   scans of the two flags, carried across chunks.
 //   res_piece_k     one wave per piece: bases = the sum of prefix_length over its inner links + read_length of its last node,
@@ -37,17 +38,16 @@
 // Bounds.  contig_ptr rows are clamped to 0 <= lo <= hi <= P (a row that needed it is counted invalid and emptied); a node is
 // checked against n and an edge id against E before they address anything; contig_of / rank hold values this file wrote.
 #include "gnm_common.h"
-#include "gnm_group.h"
+#include "gnm_scan.h"
 
 namespace gnm {
 
-constexpr int kResBlk = 4 * kBlock;      // contigs per scan block: thread t owns the four consecutive ranks 4t .. 4t+3
 constexpr int kResUndecided = INT32_MAX;
 enum { kResContigs = 0, kResEligible, kResPieces, kResDropped, kResNodes, kResSerial, kResInvalid, kResCalls };
 enum { kTotInvalid = 0, kTotNodes, kTotPieces, kTotWords = 4 };
 
 struct ResArgs {
-  int64_t C, P, n, E, R, nb;             // R = n / 2 + 1 reads; nb: scan blocks
+  int64_t C, P, n, E, R;                 // R = n / 2 + 1 reads
   int thr;
   const int32_t *contig_ptr, *walk_nodes, *walk_edges, *order;
   const int64_t *prefix_length, *read_length;
@@ -285,61 +285,29 @@ __global__ __launch_bounds__(kBlock) void res_round_k(ResArgs a, int r, unsigned
   block_count_add(dropped, lds, a.rec + kResDropped);
 }
 
-// four consecutive values, in priority order, of the two scanned sequences: kept nodes and kept pieces per contig
-__device__ __forceinline__ void res_ld4_(const ResArgs& a, int64_t k0, int f[4], int l[4]) {
+// The two scanned sequences, in priority order: kept nodes (-> noff) and kept pieces (-> poff) per contig; one look-up of `order`
+// feeds both.  Nothing runs on invalid input.
+struct ResScan : ScanUser<int32_t, 2> {
+  ResArgs a;
+  __device__ __forceinline__ bool skip() const { return a.tot[kTotInvalid] != 0ull; }
+  __device__ __forceinline__ void load(const Arrays& x, int64_t k0, bool, int32_t (&v)[2][4]) const {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[i] = l[i] = 0;
-    if (k0 + i < a.C) {
-      const unsigned c = (unsigned)a.order[k0 + i];
-      if (c < (unsigned)a.C) {
-        f[i] = a.kn[c];
-        l[i] = a.kp[c];
+    for (int i = 0; i < 4; ++i) {
+      v[0][i] = v[1][i] = 0;
+      if (k0 + i < x.n) {
+        const unsigned c = (unsigned)a.order[k0 + i];
+        if (c < (unsigned)a.C) {
+          v[0][i] = a.kn[c];
+          v[1][i] = a.kp[c];
+        }
       }
     }
   }
-}
-
-__global__ __launch_bounds__(kBlock) void res_bsum_k(ResArgs a) {
-  __shared__ int red[kWavesPerBlock];
-  if (a.tot[kTotInvalid] != 0ull) return;
-  for (int64_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
-    int f[4], l[4];
-    res_ld4_(a, b * kResBlk + 4 * (int64_t)threadIdx.x, f, l);
-    const int sf = block_sum(f[0] + f[1] + f[2] + f[3], red), sl = block_sum(l[0] + l[1] + l[2] + l[3], red);
-    if (threadIdx.x == 0) {
-      a.bsum[0][b] = sf;
-      a.bsum[1][b] = sl;
-    }
-  }
-}
-
-// Workgroup s turns the block sums of sequence s into their exclusive prefix, in place; the totals are the kept nodes / pieces.
-__global__ __launch_bounds__(kBlock) void res_scan_k(ResArgs a) {
-  __shared__ int lds[kWavesPerBlock];
-  if (a.tot[kTotInvalid] != 0ull) return;
-  const int s = blockIdx.x;
-  int total;
-  scan_block_sums(a.bsum[s], a.nb, lds, total);
-  if (threadIdx.x == 0) {
+  __device__ __forceinline__ void total(const Arrays&, int s, int32_t total) const {   // the kept nodes / pieces
     a.tot[s == 0 ? kTotNodes : kTotPieces] = (unsigned long long)total;
     if (total > 0) atomicAdd(a.rec + (s == 0 ? kResNodes : kResPieces), (unsigned long long)total);
   }
-}
-
-__global__ __launch_bounds__(kBlock) void res_apply_k(ResArgs a) {
-  __shared__ int lds[kWavesPerBlock];
-  if (a.tot[kTotInvalid] != 0ull) return;
-  for (int64_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
-    const int64_t k0 = b * kResBlk + 4 * (int64_t)threadIdx.x;
-    int f[4], l[4], total;
-    res_ld4_(a, k0, f, l);
-    const int x0 = a.bsum[0][b] + block_scan_excl(f[0] + f[1] + f[2] + f[3], lds, total);
-    const int y0 = a.bsum[1][b] + block_scan_excl(l[0] + l[1] + l[2] + l[3], lds, total);
-    store4_excl(a.noff, k0, a.C, x0, f);
-    store4_excl(a.poff, k0, a.C, y0, l);
-  }
-}
+};
 
 __global__ __launch_bounds__(kBlock) void res_gather_k(ResArgs a) {
   if (a.tot[kTotInvalid] != 0ull) return;
@@ -418,12 +386,11 @@ struct ResLayout {
 static ResLayout res_layout(int64_t C, int64_t P, int64_t n) {
   ResLayout l;
   size_t off = 0;
-  const size_t nb = (size_t)((C + kResBlk - 1) / kResBlk);
   for (int i = 0; i < 2; ++i) { l.node[i] = off; off += ws_pad((size_t)n * 4); }
   for (int i = 0; i < 2; ++i) { l.read[i] = off; off += ws_pad((size_t)(n / 2 + 1) * 4); }
   for (int i = 0; i < 7; ++i) { l.contig[i] = off; off += ws_pad((size_t)C * 4); }
   for (int i = 0; i < 2; ++i) { l.pos[i] = off; off += ws_pad((size_t)P * 4); }
-  for (int i = 0; i < 2; ++i) { l.bsum[i] = off; off += ws_pad(nb * 4); }
+  for (int i = 0; i < 2; ++i) { l.bsum[i] = off; off += scan_bsum_bytes<int32_t, 4>(C); }
   l.tot = off; off += ws_pad(kTotWords * 8);
   l.bytes = off;
   return l;
@@ -455,7 +422,7 @@ static int res_args(const char* what, int64_t C, int64_t P, int64_t n, int64_t E
   if (ws_check(what, "gnm_resolve_workspace_bytes", ws, ws_bytes, l.bytes)) return -1;
   char* w = (char*)ws;
   a = ResArgs{};
-  a.C = C; a.P = P; a.n = n; a.E = E; a.R = n / 2 + 1; a.nb = (C + kResBlk - 1) / kResBlk;
+  a.C = C; a.P = P; a.n = n; a.E = E; a.R = n / 2 + 1;
   a.thr = (int)len_threshold;
   a.contig_ptr = contig_ptr; a.walk_nodes = walk_nodes; a.walk_edges = walk_edges; a.order = order;
   a.contig_of = (int32_t*)(w + l.node[0]); a.pos_of = (int32_t*)(w + l.node[1]);
@@ -528,10 +495,7 @@ extern "C" int gnm_resolve_layout(int64_t C, int64_t P, int64_t n, int64_t E, co
   hipStream_t st = (hipStream_t)stream;
   const dim3 blk(kBlock), wgrid(res_wave_grid(C > 0 ? C : 1));
   if (C > 0) {
-    const dim3 sgrid(persistent_grid(a.nb, 1, 8));
-    hipLaunchKernelGGL(res_bsum_k, sgrid, blk, 0, st, a);
-    hipLaunchKernelGGL(res_scan_k, dim3(2), blk, 0, st, a);
-    hipLaunchKernelGGL(res_apply_k, sgrid, blk, 0, st, a);
+    scan_launch<int32_t, 4, 2>(ResScan{{}, a}, {C, {a.bsum[0], a.bsum[1]}, {a.noff, a.poff}}, st);
   }
   hipLaunchKernelGGL(res_gather_k, wgrid, blk, 0, st, a);                   // C == 0: out_ptr[0] = 0
   if (P > 0) hipLaunchKernelGGL(res_piece_k, dim3(res_wave_grid(P / a.thr + 1)), blk, 0, st, a);

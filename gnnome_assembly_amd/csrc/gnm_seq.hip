@@ -2,11 +2,9 @@
 // bases as ASCII, back to back in one buffer.  The per-position and per-lane arithmetic is csrc/gnm_seq.h.
 //
 // gnm_seq_layout, four launches on one stream:
-//   seq_len_k     piece_len[p] of every walk position (the position's contig by binary search in contig_ptr, the node, read and
-//                 edge checked before they address anything), the sum of every block of kBlock positions, the counters.
-//   seq_scan_k    ONE workgroup: the block sums -> their exclusive prefix, in place (gnm_group.h's scan_block_sums, in int64);
-//                 piece_off[P] = the total; record: contigs, pieces, bases, calls.
-//   seq_apply_k   piece_off[p] = block prefix + in-block exclusive scan of piece_len.
+//   scan_launch   the three launches of gnm_scan.h (int64, one position per thread) with SeqScan as their user: the sums phase also
+//                 forms and stores piece_len[p] of every walk position and counts; the middle phase leaves piece_off[P] = the total
+//                 and the record's contigs, pieces, bases, calls; the apply phase piece_off[p].
 //   seq_cptr_k    contig_base_ptr[c] = piece_off[contig_ptr[c]].
 // gnm_seq_emit, one launch: a workgroup owns a run of consecutive chunks of kSeqChunkBases output bases.  Per chunk its first
 // thread finds the pieces of the chunk's first and last base in piece_off (binary search for the run's first chunk, a few steps
@@ -15,7 +13,7 @@
 // No workgroup waits for another, nothing is read back between the launches, no float arithmetic; integer atomics on the record
 // words only (one per counter and workgroup): bytes and record depend on the inputs alone, not on the grid or on timing.
 #include "gnm_common.h"
-#include "gnm_group.h"
+#include "gnm_scan.h"
 #include "gnm_seq.h"
 
 namespace gnm {
@@ -24,23 +22,24 @@ enum { kSeqContigs = 0, kSeqPieces, kSeqBases, kSeqClamped, kSeqEmpty, kSeqRever
 
 struct SeqArgs {
   SeqStore s;
-  int64_t C, P, E, nb;                   // nb: scan blocks of kBlock positions
+  int64_t C, P, E;
   const int32_t *contig_ptr, *walk_nodes, *walk_edges;
   const int64_t* prefix_length;
-  int64_t *piece_len, *piece_off, *contig_base_ptr, *bsum;
+  int64_t *piece_len, *piece_off, *contig_base_ptr;
   unsigned long long* rec;
   int64_t total;                         // emit: the bases the caller read from the record
   uint8_t* out;
 };
 
-__global__ __launch_bounds__(kBlock) void seq_len_k(SeqArgs a) {
-  __shared__ int64_t lds64[kWavesPerBlock];
-  __shared__ unsigned lds[kWavesPerBlock];
+// The scanned sequence: piece_len (-> piece_off).  The sums phase is its producer as well: it forms piece_len[p] (the position's contig
+// by binary search in contig_ptr; node, read and edge checked before they address anything), stores it and counts; apply reads it back.
+struct SeqScan : ScanUser<int64_t, 1> {
+  SeqArgs a;
   unsigned clamped = 0u, empty = 0u, reverse = 0u, invalid = 0u;
-  for (int64_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
-    const int64_t p = b * kBlock + threadIdx.x;
+  __device__ __forceinline__ void load(const Arrays& x, int64_t p, bool first, int64_t (&v)[1][1]) {
     int64_t k = 0;
-    if (p < a.P) {
+    if (p < x.n && !first) k = a.piece_len[p];
+    if (p < x.n && first) {
       unsigned f;
       k = seq_piece_len_(a.s, a.C, a.P, a.E, a.contig_ptr, a.walk_nodes, a.walk_edges, a.prefix_length, p, f);
       a.piece_len[p] = k;
@@ -49,37 +48,24 @@ __global__ __launch_bounds__(kBlock) void seq_len_k(SeqArgs a) {
       invalid += (f >> 2) & 1u;
       empty += (k == 0 && !(f & 4u)) ? 1u : 0u;
     }
-    const int64_t total = block_sum(k, lds64);
-    if (threadIdx.x == 0) a.bsum[b] = total;
+    v[0][0] = k;
   }
-  block_count_add(clamped, lds, a.rec + kSeqClamped);
-  block_count_add(empty, lds, a.rec + kSeqEmpty);
-  block_count_add(reverse, lds, a.rec + kSeqReverse);
-  block_count_add(invalid, lds, a.rec + kSeqInvalid);
-}
-
-__global__ __launch_bounds__(kBlock) void seq_scan_k(SeqArgs a) {
-  __shared__ int64_t lds64[kWavesPerBlock];
-  int64_t total;
-  scan_block_sums(a.bsum, a.nb, lds64, total);
-  if (threadIdx.x == 0) {
-    a.piece_off[a.P] = total;
+  __device__ __forceinline__ void sums_end(int64_t* lds64) {
+    unsigned* lds = reinterpret_cast<unsigned*>(lds64);
+    block_count_add(clamped, lds, a.rec + kSeqClamped);
+    block_count_add(empty, lds, a.rec + kSeqEmpty);
+    block_count_add(reverse, lds, a.rec + kSeqReverse);
+    block_count_add(invalid, lds, a.rec + kSeqInvalid);
+  }
+  // piece_off[P] = the total; record: contigs, pieces, bases, calls
+  __device__ __forceinline__ void total(const Arrays& x, int, int64_t total) const {
+    x.out[0][x.n] = total;
     if (a.C > 0) atomicAdd(a.rec + kSeqContigs, (unsigned long long)a.C);
     if (a.P > 0) atomicAdd(a.rec + kSeqPieces, (unsigned long long)a.P);
     if (total > 0) atomicAdd(a.rec + kSeqBases, (unsigned long long)total);
     atomicAdd(a.rec + kSeqCalls, 1ull);
   }
-}
-
-__global__ __launch_bounds__(kBlock) void seq_apply_k(SeqArgs a) {
-  __shared__ int64_t lds64[kWavesPerBlock];
-  for (int64_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
-    const int64_t p = b * kBlock + threadIdx.x;
-    int64_t total;
-    const int64_t x = a.bsum[b] + block_scan_excl<int64_t>(p < a.P ? a.piece_len[p] : 0, lds64, total);
-    if (p < a.P) a.piece_off[p] = x;
-  }
-}
+};
 
 __global__ __launch_bounds__(kBlock) void seq_cptr_k(SeqArgs a) {
   for (int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x; c <= a.C; c += (int64_t)gridDim.x * kBlock) {
@@ -129,7 +115,7 @@ static_assert(kSeqChunkBases == GNM_SEQ_CHUNK_BASES, "include/gnm.h states the c
 
 extern "C" size_t gnm_seq_workspace_bytes(int64_t P) {
   if (P < 0 || P >= INT32_MAX) return 0;
-  return ws_pad((size_t)((P + kBlock - 1) / kBlock) * 8);
+  return scan_bsum_bytes<int64_t, 1>(P);
 }
 
 extern "C" int gnm_seq_layout(int64_t C, int64_t P, int64_t E, int64_t n, int64_t R, const int32_t* contig_ptr,
@@ -148,15 +134,12 @@ extern "C" int gnm_seq_layout(int64_t C, int64_t P, int64_t E, int64_t n, int64_
   hipStream_t st = (hipStream_t)stream;
   SeqArgs a = {};
   a.s.packed = nullptr; a.s.base_off = base_off; a.s.length = length; a.s.nibbles = packed_bytes * 2; a.s.R = R; a.s.n = n;
-  a.C = C; a.P = P; a.E = E; a.nb = (P + kBlock - 1) / kBlock;
+  a.C = C; a.P = P; a.E = E;
   a.contig_ptr = contig_ptr; a.walk_nodes = walk_nodes; a.walk_edges = walk_edges; a.prefix_length = prefix_length;
-  a.piece_len = piece_len; a.piece_off = piece_off; a.contig_base_ptr = contig_base_ptr; a.bsum = (int64_t*)ws;
+  a.piece_len = piece_len; a.piece_off = piece_off; a.contig_base_ptr = contig_base_ptr;
   a.rec = (unsigned long long*)record;
-  const dim3 blk(kBlock);
-  if (P > 0) hipLaunchKernelGGL(seq_len_k, dim3(persistent_grid(a.nb, 1, 8)), blk, 0, st, a);
-  hipLaunchKernelGGL(seq_scan_k, dim3(1), blk, 0, st, a);                     // P == 0: piece_off[0] = 0, calls += 1
-  if (P > 0) hipLaunchKernelGGL(seq_apply_k, dim3(persistent_grid(a.nb, 1, 8)), blk, 0, st, a);
-  hipLaunchKernelGGL(seq_cptr_k, dim3(persistent_grid(C + 1, kBlock, 8)), blk, 0, st, a);
+  scan_launch<int64_t, 1, 1>(SeqScan{{}, a}, {P, {(int64_t*)ws}, {piece_off}}, st);       // P == 0: piece_off[0] = 0, calls += 1
+  hipLaunchKernelGGL(seq_cptr_k, dim3(persistent_grid(C + 1, kBlock, 8)), dim3(kBlock), 0, st, a);
   GNM_LAUNCH_CHECK("seq_layout");
   return 0;
 }

@@ -2590,8 +2590,7 @@ ALIGN_MAX_ERRORS = 255                     # the widest band: 2 K + 1 <= 512 dia
 def _align_args(name, src, dst, prefix_length, base_off, length, packed, max_errors, dist, overlap_length, similarity, rec):
     E = int(src.numel())
     R = _seq_store_args(name, base_off, length, packed)
-    if isinstance(max_errors, bool) or not hasattr(max_errors, "__index__") or not 0 <= operator.index(max_errors) <= ALIGN_MAX_ERRORS:
-        raise ValueError(f"{name}: max_errors={max_errors!r}: expected an integer in [0, {ALIGN_MAX_ERRORS}]")
+    _int_in(name, "max_errors", max_errors, 0, ALIGN_MAX_ERRORS)
     _chk_record(name, rec, ALIGN_RECORD_WORDS, "rec")
     _chk_args(name, ("src", src, torch.int32, E), ("dst", dst, torch.int32, E), ("prefix_length", prefix_length, torch.int64, E),
               ("dist", dist, torch.int32, E), ("overlap_length", overlap_length, torch.int64, E),
@@ -2619,15 +2618,12 @@ def overlap_align_host(src, dst, prefix_length, n: int, base_off, length, packed
     """overlap_align's arithmetic on the CPU (gnm_overlap_align_host: the same header routine, `threads` host threads): the same
     arguments as CPU tensors.  For tests and for scale; nothing on the product path calls it."""
     lib = _lib.load()
-    ts = (src, dst, prefix_length, base_off, length, packed, dist, overlap_length, similarity, rec)
-    if any(t.device.type != "cpu" for t in ts):
-        raise ValueError("overlap_align_host: every tensor must be a CPU tensor")
+    _cpu_tensors("overlap_align_host", src, dst, prefix_length, base_off, length, packed, dist, overlap_length, similarity, rec)
     E, R = _align_args("overlap_align_host", src, dst, prefix_length, base_off, length, packed, max_errors, dist, overlap_length,
                        similarity, rec)
-    hp = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
-    _lib.check(lib.gnm_overlap_align_host(E, hp(src), hp(dst), hp(prefix_length), hp(packed), int(packed.numel()), hp(base_off),
-                                          hp(length), R, int(n), operator.index(max_errors), hp(dist), hp(overlap_length),
-                                          hp(similarity), hp(rec), int(threads)), "gnm_overlap_align_host")
+    _lib.check(lib.gnm_overlap_align_host(E, _hp(src), _hp(dst), _hp(prefix_length), _hp(packed), int(packed.numel()), _hp(base_off),
+                                          _hp(length), R, int(n), operator.index(max_errors), _hp(dist), _hp(overlap_length),
+                                          _hp(similarity), _hp(rec), int(threads)), "gnm_overlap_align_host")
 
 
 OVERLAP_COUNTERS = ("reads", "kmers_valid", "minimizers", "runs", "skipped_runs", "skipped_entries", "hits", "same_read", "groups",
@@ -2648,7 +2644,7 @@ def _hp(t):
     return t.data_ptr() if t is not None and t.numel() else None
 
 
-def _overlap_host(fn: str, *ts):
+def _cpu_tensors(fn: str, *ts):
     if any(t is not None and t.device.type != "cpu" for t in ts):
         raise ValueError(f"{fn}: every tensor must be a CPU tensor")
 
@@ -2657,104 +2653,88 @@ def _new(dev, n, dt):
     return torch.empty(int(n), dtype=dt, device=dev)
 
 
+def _count_then_emit(fn: str, ts, rec, threads, head, outs, extra, table_sizes, count, emit):
+    """What sketch, seed_pairs and chain_pairs share: the outputs outs(m) of a stage whose size m only its count pass knows.
+    ts: the stage's tensors, the one that names its device first; head(p): the leading arguments of gnm_<fn>_host, pointers made
+    by p; extra: tensors of the caller's that follow the outputs there.
+    CPU tensors: gnm_<fn>_host with capacity -1 and nulls for the size, then again over the outputs.
+    Device tensors: count(tables, ws, need) enqueues the count pass over int64 tables of table_sizes entries and the scan workspace
+    of the longest; the scan's total is the last table's last entry: ONE read-back; emit(tables, out) enqueues the emit pass."""
+    lib = _lib.load()
+    dev = ts[0].device
+    if dev.type == "cpu":
+        _cpu_tensors(fn, *ts, rec)
+        host, total = getattr(lib, f"gnm_{fn}_host"), C.c_int64(0)
+        tail = (C.byref(total), _hp(rec), int(threads))
+        _lib.check(host(*head(_hp), -1, *[None] * (len(outs(0)) + len(extra)), *tail), f"gnm_{fn}_host")
+        out = outs(total.value)
+        _lib.check(host(*head(_hp), total.value, *[C.c_void_p(t.data_ptr()) for t in out + extra], *tail), f"gnm_{fn}_host")
+        return out
+    _chk_dev(*ts, rec)
+    with torch.cuda.device(dev):
+        tables = [_new(dev, m, torch.int64) for m in table_sizes]
+        need = lib.gnm_overlap_scan_workspace_bytes(max(table_sizes) - 1)
+        count([_ptr(t) for t in tables], _ptr(scratch(dev).ws(need)), need)
+        out = outs(int(tables[-1][-1]))                      # the scan's total: the one synchronisation of the stage
+        emit([_ptr(t) for t in tables], out)
+    return out
+
+
 def sketch(base_off, length, packed, k: int, w: int, rec, threads: int = 1):
     """The minimizer sketch of every read of a packed store (include/gnm.h, "overlap graph", stage 1): (hash int64, read int32, pos
     int32, strand uint8), ordered by read and position, on the store's device.  Device tensors: gnm_sketch_count, one read-back of
     the size, gnm_sketch_emit.  CPU tensors: gnm_sketch_host on `threads` host threads (the same header).  rec: a contiguous int64
     [OVERLAP_RECORD_WORDS] tensor on that device the call ADDS to."""
-    lib = _lib.load()
     R = _seq_store_args("sketch", base_off, length, packed)
     k, w = _int_in("sketch", "k", k, *SKETCH_K), _int_in("sketch", "w", w, *SKETCH_W)
     _chk_record("sketch", rec, OVERLAP_RECORD_WORDS, "rec")
     dev, nbytes = packed.device, int(packed.numel())
-    outs = lambda m: (_new(dev, m, torch.int64), _new(dev, m, torch.int32), _new(dev, m, torch.int32), _new(dev, m, torch.uint8))  # noqa: E731
-    if dev.type == "cpu":
-        _overlap_host("sketch", base_off, length, rec)
-        total = C.c_int64(0)
-        head = (_hp(packed), nbytes, _hp(base_off), _hp(length), R, k, w)
-        _lib.check(lib.gnm_sketch_host(*head, -1, None, None, None, None, C.byref(total), _hp(rec), int(threads)), "gnm_sketch_host")
-        out = outs(total.value)
-        _lib.check(lib.gnm_sketch_host(*head, total.value, *[C.c_void_p(t.data_ptr()) for t in out], C.byref(total), _hp(rec),
-                                       int(threads)), "gnm_sketch_host")
-        return out
-    _chk_dev(base_off, length, packed, rec)
-    with torch.cuda.device(dev):
-        tb = int(lib.gnm_sketch_tile_bound(R, nbytes))
-        tile_ptr, tile_off = _new(dev, R + 1, torch.int64), _new(dev, tb + 1, torch.int64)
-        need = lib.gnm_overlap_scan_workspace_bytes(max(R, tb))
-        ws = scratch(dev).ws(need)
-        head = (_ptr(packed), nbytes, _ptr(base_off), _ptr(length), R, k, w, _ptr(tile_ptr), _ptr(tile_off), tb)
-        _call("gnm_sketch_count", *head, _ptr(rec), _ptr(ws), need, _stream())
-        out = outs(int(tile_off[tb]))                        # the scan's total: the one synchronisation of the stage
-        _call("gnm_sketch_emit", *head, out[0].numel(), *[_ptr(t) for t in out], _stream())
-    return out
+    tb = int(_lib.load().gnm_sketch_tile_bound(R, nbytes))
+    head = lambda p: (p(packed), nbytes, p(base_off), p(length), R, k, w)  # noqa: E731
+    return _count_then_emit(
+        "sketch", (packed, base_off, length), rec, threads, head,
+        lambda m: tuple(_new(dev, m, dt) for dt in (torch.int64, torch.int32, torch.int32, torch.uint8)), (),
+        (R + 1, tb + 1),                                     # tile_ptr, tile_off
+        lambda tables, ws, need: _call("gnm_sketch_count", *head(_ptr), *tables, tb, _ptr(rec), ws, need, _stream()),
+        lambda tables, out: _call("gnm_sketch_emit", *head(_ptr), *tables, tb, out[0].numel(), *map(_ptr, out), _stream()))
 
 
 def seed_pairs(hash_, read, pos, strand, length, k: int, max_occ: int, rec, threads: int = 1):
     """The seed hits of a sketch sorted by hash (stage 2): (key int64, diag int32).  hash_ int64, read, pos int32, strand uint8 [M]
     sorted stably by hash_; length int64 [R]: the reads' lengths.  Device or CPU tensors, as for `sketch`."""
-    lib = _lib.load()
     M, R = int(hash_.numel()), int(length.numel())
     k, max_occ = _int_in("seed_pairs", "k", k, *SKETCH_K), _int_in("seed_pairs", "max_occ", max_occ, 1, OVERLAP_MAX_OCC)
     _chk_record("seed_pairs", rec, OVERLAP_RECORD_WORDS, "rec")
     _chk_args("seed_pairs", ("hash", hash_, torch.int64, M), ("read", read, torch.int32, M), ("pos", pos, torch.int32, M),
               ("strand", strand, torch.uint8, M), ("length", length, torch.int64, R))
     dev = hash_.device
-    outs = lambda m: (_new(dev, m, torch.int64), _new(dev, m, torch.int32))  # noqa: E731
-    if dev.type == "cpu":
-        _overlap_host("seed_pairs", read, pos, strand, length, rec)
-        total = C.c_int64(0)
-        head = (M, _hp(hash_), _hp(read), _hp(pos), _hp(strand), _hp(length), R, k, max_occ)
-        _lib.check(lib.gnm_seed_pairs_host(*head, -1, None, None, C.byref(total), _hp(rec), int(threads)), "gnm_seed_pairs_host")
-        out = outs(total.value)
-        _lib.check(lib.gnm_seed_pairs_host(*head, total.value, *[C.c_void_p(t.data_ptr()) for t in out], C.byref(total), _hp(rec),
-                                           int(threads)), "gnm_seed_pairs_host")
-        return out
-    _chk_dev(hash_, read, pos, strand, length, rec)
-    with torch.cuda.device(dev):
-        off = _new(dev, M + 1, torch.int64)
-        need = lib.gnm_overlap_scan_workspace_bytes(M)
-        ws = scratch(dev).ws(need)
-        _call("gnm_seed_pairs_count", M, _ptr(hash_), _ptr(read), max_occ, _ptr(off), _ptr(rec), _ptr(ws), need, _stream())
-        out = outs(int(off[M]))                              # the scan's total: the one synchronisation of the stage
-        _call("gnm_seed_pairs_emit", M, _ptr(hash_), _ptr(read), _ptr(pos), _ptr(strand), _ptr(length), R, k, max_occ, _ptr(off),
-              out[0].numel(), _ptr(out[0]), _ptr(out[1]), _stream())
-    return out
+    head = lambda p: (M, p(hash_), p(read), p(pos), p(strand), p(length), R, k, max_occ)  # noqa: E731
+    return _count_then_emit(
+        "seed_pairs", (hash_, read, pos, strand, length), rec, threads, head,
+        lambda m: (_new(dev, m, torch.int64), _new(dev, m, torch.int32)), (),
+        (M + 1,),                                            # off
+        lambda off, ws, need: _call("gnm_seed_pairs_count", M, _ptr(hash_), _ptr(read), max_occ, *off, _ptr(rec), ws, need, _stream()),
+        lambda off, out: _call("gnm_seed_pairs_emit", *head(_ptr), *off, out[0].numel(), *map(_ptr, out), _stream()))
 
 
 def chain_pairs(key, diag, length, band: int, min_hits: int, min_overlap: int, rec, threads: int = 1):
     """The chains of the seed hits sorted by diag, then stably by key (stage 3): (src int32, dst int32, prefix_length int64,
     overlap_length int64, valid uint8) [2 G] -- group g owns slots 2g (the edge) and 2g + 1 (its twin) -- and contained uint8 [R]."""
-    lib = _lib.load()
     N, R = int(key.numel()), int(length.numel())
     band, min_hits = _int_in("chain_pairs", "band", band, 0, 2 ** 31 - 2), _int_in("chain_pairs", "min_hits", min_hits, 1, 2 ** 31 - 2)
     min_overlap = _int_in("chain_pairs", "min_overlap", min_overlap, 0, 2 ** 62)
     _chk_record("chain_pairs", rec, OVERLAP_RECORD_WORDS, "rec")
     _chk_args("chain_pairs", ("key", key, torch.int64, N), ("diag", diag, torch.int32, N), ("length", length, torch.int64, R))
     dev = key.device
-    outs = lambda g: (_new(dev, 2 * g, torch.int32), _new(dev, 2 * g, torch.int32), _new(dev, 2 * g, torch.int64),  # noqa: E731
-                      _new(dev, 2 * g, torch.int64), _new(dev, 2 * g, torch.uint8))
     contained = torch.zeros(R, dtype=torch.uint8, device=dev)
-    if dev.type == "cpu":
-        _overlap_host("chain_pairs", diag, length, rec)
-        total = C.c_int64(0)
-        head = (N, _hp(key), _hp(diag), _hp(length), R, band, min_hits, min_overlap)
-        _lib.check(lib.gnm_chain_pairs_host(*head, -1, None, None, None, None, None, None, C.byref(total), _hp(rec), int(threads)),
-                   "gnm_chain_pairs_host")
-        out = outs(total.value)
-        _lib.check(lib.gnm_chain_pairs_host(*head, total.value, *[C.c_void_p(t.data_ptr()) for t in out],
-                                            C.c_void_p(contained.data_ptr()), C.byref(total), _hp(rec), int(threads)),
-                   "gnm_chain_pairs_host")
-        return out + (contained,)
-    _chk_dev(key, diag, length, rec)
-    with torch.cuda.device(dev):
-        off = _new(dev, N + 1, torch.int64)
-        need = lib.gnm_overlap_scan_workspace_bytes(N)
-        ws = scratch(dev).ws(need)
-        _call("gnm_chain_count", N, _ptr(key), _ptr(off), _ptr(rec), _ptr(ws), need, _stream())
-        out = outs(int(off[N]))                              # the scan's total: the one synchronisation of the stage
-        _call("gnm_chain_pairs", N, _ptr(key), _ptr(diag), _ptr(off), out[0].numel() // 2, _ptr(length), R, band, min_hits,
-              min_overlap, *[_ptr(t) for t in out], _ptr(contained), _ptr(rec), _stream())
+    out = _count_then_emit(
+        "chain_pairs", (key, diag, length), rec, threads,
+        lambda p: (N, p(key), p(diag), p(length), R, band, min_hits, min_overlap),
+        lambda g: tuple(_new(dev, 2 * g, dt) for dt in (torch.int32, torch.int32, torch.int64, torch.int64, torch.uint8)), (contained,),
+        (N + 1,),                                            # off: the group number of every head
+        lambda off, ws, need: _call("gnm_chain_count", N, _ptr(key), *off, _ptr(rec), ws, need, _stream()),
+        lambda off, out: _call("gnm_chain_pairs", N, _ptr(key), _ptr(diag), *off, out[0].numel() // 2, _ptr(length), R, band, min_hits,
+                               min_overlap, *map(_ptr, out), _ptr(contained), _ptr(rec), _stream()))
     return out + (contained,)
 
 
@@ -2833,7 +2813,7 @@ def gt_labels_host(src, dst, n: int, start, end, strand, twin, y, valid, backbon
     Unusable node values raise ValueError and write nothing but rec's `invalid` word."""
     lib = _lib.load()
     n, E = int(n), int(src.numel())
-    _overlap_host("gt_labels_host", src, dst, start, end, strand, twin, y, valid, backbone, component, top, rec)
+    _cpu_tensors("gt_labels_host", src, dst, start, end, strand, twin, y, valid, backbone, component, top, rec)
     _gt_args("gt_labels_host", n, E, start, end, strand, twin, y, valid, backbone, component, top, rec)
     _chk_args("gt_labels_host", ("src", src, torch.int32, E), ("dst", dst, torch.int32, E))
     rc = lib.gnm_gt_labels_host(n, E, _hp(src), _hp(dst), _hp(start), _hp(end), _hp(strand), _hp(twin), _hp(y), _hp(valid),

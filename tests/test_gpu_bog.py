@@ -147,6 +147,45 @@ def test_one_cycle_is_cut_at_its_smallest_node(lib, n):
     assert got["record"].tolist()[:4] == [1, n - 1, 1, 0] and got["walk_nodes"][0] == 0 and got["contig_ptr"].tolist() == [0, n]
 
 
+@pytest.mark.parametrize("n", [1023, 1024, 1025, 256 * 1024 + 1])   # the scan block B = 1024: B - 1, B, B + 1; 257 scan blocks
+def test_chains_of_three_nodes_at_the_scan_block_edges(lib, n):
+    """Nodes 3j -> 3j + 1 -> 3j + 2 in id order (the last chain may be shorter): the scanned head flags are 1, 0, 0, .. and the
+    scanned lengths 3, 0, 0, .., so every output has a closed form and a wrong block offset moves a contig.  gnm_bog_contigs on
+    hand-made tables; every output is the head of a longer buffer whose tail must keep its fill."""
+    from gnnome_assembly_amd import engine
+    v = np.arange(n)
+    linked = (v % 3 != 2) & (v + 1 < n)                      # v -> v + 1 by edge id[v]
+    src = v[linked]
+    E = src.size
+    eid = np.full(n, -1, np.int64)
+    eid[src] = np.arange(E)
+    pred = np.full(n, -1, np.int64)
+    pred[src + 1] = eid[src]
+    pl, rl = np.arange(E, dtype=np.int64) * 7 + 1, v.astype(np.int64) + 1000
+    C = (n + 2) // 3
+    ptr = np.minimum(3 * np.arange(C + 1), n)
+    lens = np.diff(ptr)
+    bases = np.zeros(C, np.int64)
+    np.add.at(bases, src // 3, pl)
+    bases += rl[ptr[1:] - 1]
+    want = {"contig_ptr": ptr, "walk_nodes": v, "walk_edges": pred, "contig_bases": bases, "contig_wrong": np.zeros(C, np.int64)}
+    record = [C, E, 0, 0, 0, int(lens[lens > 1].sum()), int((lens > 1).sum()), 1]
+    pad, fill = 64, -7
+    buf = {k: torch.full((m + pad,), fill, dtype=dt, device=DEV) for k, m, dt in
+           (("contig_ptr", n + 1, torch.int32), ("walk_nodes", n, torch.int32), ("walk_edges", n, torch.int32),
+            ("contig_bases", n, torch.int64), ("contig_wrong", n, torch.int32))}
+    rec = torch.zeros(B.WORDS, dtype=torch.int64, device=DEV)
+    engine.bog_contigs(_t(src, np.int32), _t(src + 1, np.int32), _t(eid, np.int32), _t(pred, np.int32), torch.ones(E, device=DEV),
+                       torch.ones(E, device=DEV), _t(pl, np.int64), _t(rl, np.int64), rec,
+                       **{k: b[:b.numel() - pad] for k, b in buf.items()})
+    torch.cuda.synchronize()
+    assert rec.tolist() == record
+    for k, b in buf.items():
+        got = b.cpu().numpy().astype(np.int64)
+        assert np.array_equal(got[:want[k].size], want[k]), (k, got[:12], want[k][:12])
+        assert (got[-pad:] == fill).all(), k
+
+
 # ---- 3. a mix of paths and cycles with distractors, ties and special scores ----------------------------------------------------------------
 @pytest.fixture(scope="module")
 def mix():

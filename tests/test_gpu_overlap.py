@@ -45,6 +45,23 @@ def test_chains_on_the_device(lib, name):
     same(got, run_chains(*CHAINS[name]), name + " (host entry)")
 
 
+@pytest.mark.parametrize("M", [0, 1, 255, 256, 257, 256 * 256 + 1])   # the scan block B = 256: B - 1, B, B + 1; 257 scan blocks
+def test_seed_hit_offsets_at_the_scan_block_edges(lib, M):
+    """Runs of two entries (2j, 2j + 1) of reads a < b on one strand, pos = (j, 0): the scanned counts are 0, 1, 0, 1, .. and hit j
+    has diag j, so a wrong offset moves a hit.  Closed form, and the host entry on the same arrays."""
+    i = np.arange(M)
+    a = 2 * ((i // 2) % 500)
+    arr = (i // 2, (a + i % 2).astype(np.int32), np.where(i % 2 == 0, i // 2, 0).astype(np.int32), np.zeros(M, np.uint8))
+    lengths = np.full(1000, 5000, np.int64)
+    got = run_pairs(arr, lengths, 15, 16, DEV)
+    N = M // 2
+    aj = 2 * (np.arange(N, dtype=np.int64) % 500)
+    rec = np.zeros(len(O.COUNTERS), np.int64)
+    rec[O.COUNTERS.index("runs")], rec[O.COUNTERS.index("hits")] = (M + 1) // 2, N
+    same(got, ((aj << 32) | ((aj + 1) << 1), np.arange(N, dtype=np.int32), rec), f"M = {M}")
+    same(got, run_pairs(arr, lengths, 15, 16), f"M = {M} (host entry)")
+
+
 def test_a_store_of_one_read(lib):
     seqs = [SKETCH["tile"][0][3]]
     got = run_sketch(seqs, 15, 25, DEV)

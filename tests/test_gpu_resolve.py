@@ -133,6 +133,35 @@ def test_empty_and_short_covers(lib):
     assert len(got) == 0 and got.stats.contigs == 11
 
 
+@pytest.mark.parametrize("C", [1, 1023, 1024, 1025, 256 * 1024 + 1])   # the scan block B = 1024: B - 1, B, B + 1; 257 scan blocks
+def test_contig_counts_at_the_scan_block_edges(lib, C):
+    """Contig c holds nodes 4c, 4c + 2 when c is even and node 4c alone when it is odd; bases rise with c, so the priority order is
+    the reverse of the input order.  At threshold 2 the scanned sequences are 2, 0, 2, 0, .. nodes and 1, 0, 1, 0, .. pieces in that
+    order: the even contigs come out whole, last first, and every output has a closed form."""
+    from gnnome_assembly_amd import decode
+    c = np.arange(C)
+    lens = np.where(c % 2 == 0, 2, 1)
+    ptr = np.concatenate([[0], np.cumsum(lens)])
+    nodes, edges = np.empty(ptr[-1], np.int64), np.full(ptr[-1], -1, np.int64)
+    nodes[ptr[:-1]] = 4 * c
+    even = c[c % 2 == 0]
+    nodes[ptr[even] + 1], edges[ptr[even] + 1] = 4 * even + 2, even // 2
+    pl, rl = np.arange(even.size, dtype=np.int64) * 5 + 1, np.arange(4 * C, dtype=np.int64) + 50
+    cover = dict(contig_ptr=ptr.astype(np.int32), walk_nodes=nodes.astype(np.int32), walk_edges=edges.astype(np.int32),
+                 bases=c.astype(np.int64) + 1, prefix_length=pl, read_length=rl, n=4 * C)
+    got = decode.resolve_strands_device(R.to_contigs(cover, DEV), 2)
+    torch.cuda.synchronize()
+    kept = even[::-1]
+    K = kept.size
+    h = got.host()
+    assert got.stats.words() == [C, K, K, 0, 2 * K, 0, 0, 1] and got.rounds == 1
+    assert np.array_equal(h["contig_ptr"], 2 * np.arange(K + 1))
+    assert np.array_equal(h["walk_nodes"], np.stack([4 * kept, 4 * kept + 2], 1).reshape(-1))
+    assert np.array_equal(h["walk_edges"], np.stack([np.full(K, -1), kept // 2], 1).reshape(-1))
+    assert np.array_equal(h["bases"], pl[kept // 2] + rl[4 * kept + 2]) and not h["wrong"].any()
+    assert len(got) == K and got.walk_nodes.numel() == 2 * K
+
+
 def test_invalid_input_raises_and_counts(lib):
     from gnnome_assembly_amd import decode
     from gnnome_assembly_amd._lib import GnmError
