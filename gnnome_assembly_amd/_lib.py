@@ -161,6 +161,11 @@ SIGNATURES = {
     "gnm_seed_pairs_count": (_i32, [_i64, _p, _p, _i32, _p, _p, _p, _sz, _p]),
     "gnm_seed_pairs_emit": (_i32, [_i64] + [_p] * 5 + [_i64, _i32, _i32, _p, _i64, _p, _p, _p]),
     "gnm_seed_pairs_host": (_i32, [_i64] + [_p] * 5 + [_i64, _i32, _i32, _i64] + [_p] * 4 + [_i32]),
+    "gnm_seed_pairs_lower_hits": (_i32, [_i64, _p, _p, _i32, _p, _i64, _p, _p, _sz, _p]),
+    "gnm_seed_pairs_lower_hits_host": (_i32, [_i64, _p, _p, _i32, _p, _i64, _p, _i32]),
+    "gnm_seed_pairs_count_range": (_i32, [_i64, _p, _p, _i32, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "gnm_seed_pairs_emit_range": (_i32, [_i64] + [_p] * 5 + [_i64, _i32, _i32, _i64, _i64, _p, _i64, _p, _p, _p]),
+    "gnm_seed_pairs_range_host": (_i32, [_i64] + [_p] * 5 + [_i64, _i32, _i32, _i64, _i64, _i64] + [_p] * 4 + [_i32]),
     "gnm_chain_count": (_i32, [_i64, _p, _p, _p, _p, _sz, _p]),
     "gnm_chain_pairs": (_i32, [_i64, _p, _p, _p, _i64, _p] + [_i64] * 4 + [_p] * 8),
     "gnm_chain_pairs_host": (_i32, [_i64, _p, _p, _p] + [_i64] * 5 + [_p] * 8 + [_i32]),

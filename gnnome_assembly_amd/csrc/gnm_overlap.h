@@ -163,6 +163,33 @@ GNM_SEQ_FN void ovl_hit_(const int32_t* read, const int32_t* pos, const uint8_t*
   diag = (int32_t)((int64_t)pos[ea] - q);
 }
 
+// Entry i's hits as the LOWER read: a hit's `a` is the smaller of its two read ids whichever entry comes later, so these are the
+// entries of i's run, before or behind it, whose read id is larger.  In a sketch sorted stably by hash a run is ordered by read and
+// the count is the run's end minus the end of i's read in it; it is counted entry by entry here (the run has at most max_occ entries
+// and ovl_run_ has walked it already), which needs no order inside the run.  back, skipped: as ovl_run_; same: the earlier entries
+// of i's own read (what the hit pass counts as same_read).
+GNM_SEQ_FN int64_t ovl_lower_(const int64_t* hash, const int32_t* read, int64_t M, int64_t i, int max_occ, int& back, bool& skipped,
+                              int64_t& same) {
+  ovl_run_(hash, M, i, max_occ, back, skipped);
+  same = 0;
+  if (skipped) return 0;
+  const int64_t h = hash[i];
+  const int32_t r = read[i];
+  int64_t m = 0;
+  for (int64_t j = i - back; j < i; ++j) {
+    m += read[j] > r ? 1 : 0;
+    same += read[j] == r ? 1 : 0;
+  }
+  for (int64_t j = i + 1; j < M && hash[j] == h; ++j) m += read[j] > r ? 1 : 0;   // not skipped: the run ends within max_occ entries
+  return m;
+}
+
+// Does the hit of two entries of reads rj, ri belong to the read range [a_lo, a_hi)?  Its `a` is the smaller id.
+GNM_SEQ_FN bool ovl_in_range_(int32_t rj, int32_t ri, int64_t a_lo, int64_t a_hi) {
+  const int64_t a = rj < ri ? rj : ri;
+  return a >= a_lo && a < a_hi;
+}
+
 // ---- stage 3: chains -----------------------------------------------------------------------------------------------------------
 enum { kChainFewHits = 0, kChainForward, kChainBackward, kChainContained, kChainShort };
 

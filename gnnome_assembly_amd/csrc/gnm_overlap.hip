@@ -12,9 +12,11 @@
 //   Emit: the workgroup's exclusive scan of the per-thread counts places the entries, ordered by read and position.
 //   LDS per workgroup: 3 word arrays + 638 hashes + 638 flags, about 6.3 KB.
 // gnm_seed_pairs_count / _emit: one lane per sorted entry; it walks back over the earlier entries of its run (at most max_occ).
+// gnm_seed_pairs_lower_hits, gnm_seed_pairs_count_range / _emit_range: the same lane per entry.  lower_hits: the entries of its run
+//   with a larger read id, one 64-bit atomic per entry into lower_hits[its read].  _range: pair_k with two more compares per pair.
 // gnm_chain_count / gnm_chain_pairs: head flags + scan = the group numbers; one lane per group head walks its group twice (its
 //   end, then the sliding window): the longest group bounds the launch's time.
-// Integer atomics on the record words only, one per counter and workgroup; no workgroup waits for another: outputs and record
+// Integer atomics on the record words, one per counter and workgroup, and on lower_hits (integer sums); no workgroup waits for another: outputs and record
 // depend on the inputs alone, not on the grid.
 #include <thread>
 #include <vector>
@@ -177,11 +179,14 @@ struct PairArgs {
   int64_t* off;                          // [M + 1]
   int64_t* key;
   int32_t* diag;
+  int64_t a_lo, a_hi;                    // RANGE: only the hits whose lower read id lies in [a_lo, a_hi)
+  int64_t* lower;                        // [R]: pair_lower_k's output
 };
 
-struct PairCounts { unsigned long long runs, skipped_runs, skipped_entries, same_read; };
+struct PairCounts { unsigned long long runs, skipped_runs, skipped_entries, same_read, hits; };
 
 // entry i: its hits counted (key == null) or written from slot `at` on; the counters of the count pass in c
+template <bool RANGE = false>
 GNM_SEQ_FN int64_t pair_entry_(const PairArgs& a, int64_t i, int64_t at, bool emit, PairCounts& c) {
   int back;
   bool skipped;
@@ -196,13 +201,15 @@ GNM_SEQ_FN int64_t pair_entry_(const PairArgs& a, int64_t i, int64_t at, bool em
       c.same_read += 1;
       continue;
     }
+    if (RANGE && !ovl_in_range_(a.read[j], a.read[i], a.a_lo, a.a_hi)) continue;
     if (emit && at + m >= 0 && at + m < a.N) ovl_hit_(a.read, a.pos, a.strand, a.length, a.R, a.k, j, i, a.key[at + m], a.diag[at + m]);
     ++m;
   }
   return m;
 }
 
-template <bool EMIT>
+// RANGE: the hits of a read range only (gnm_seed_pairs_count_range / _emit_range); its count pass adds nothing to the record.
+template <bool EMIT, bool RANGE = false>
 __global__ __launch_bounds__(kBlock) void pair_k(PairArgs a, unsigned long long* rec) {
   __shared__ unsigned long long lds[kWavesPerBlock];
   PairCounts c = {};
@@ -210,15 +217,49 @@ __global__ __launch_bounds__(kBlock) void pair_k(PairArgs a, unsigned long long*
   for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
     const int64_t i = b * kBlock + threadIdx.x;
     if (i >= a.M) continue;                                // no shuffle or barrier inside the loop
-    if (EMIT) pair_entry_(a, i, a.off[i], true, c);
-    else a.off[i] = pair_entry_(a, i, 0, false, c);
+    if (EMIT) pair_entry_<RANGE>(a, i, a.off[i], true, c);
+    else a.off[i] = pair_entry_<RANGE>(a, i, 0, false, c);
   }
-  if (!EMIT) {
+  if (!EMIT && !RANGE) {
     block_count_add(c.runs, lds, rec + kOvlRuns);
     block_count_add(c.skipped_runs, lds, rec + kOvlSkippedRuns);
     block_count_add(c.skipped_entries, lds, rec + kOvlSkippedEntries);
     block_count_add(c.same_read, lds, rec + kOvlSameRead);
   }
+}
+
+// entry i: its hits as the lower read (ovl_lower_) and what the count pass of the hits adds to the record for it
+GNM_SEQ_FN int64_t lower_entry_(const PairArgs& a, int64_t i, PairCounts& c) {
+  int back;
+  bool skipped;
+  int64_t same;
+  const int64_t m = ovl_lower_(a.hash, a.read, a.M, i, a.max_occ, back, skipped, same);
+  c.runs += back == 0 ? 1 : 0;
+  c.skipped_runs += back == 0 && skipped ? 1 : 0;
+  c.skipped_entries += skipped ? 1 : 0;
+  c.same_read += (unsigned long long)same;
+  c.hits += (unsigned long long)m;
+  return m;
+}
+
+// gnm_seed_pairs_lower_hits: one lane per sorted entry, one 64-bit integer atomic per entry that is some hit's lower read (sums of
+// integers: their order does not show).  An entry whose read id lies outside [0, R) adds to the record only.
+__global__ __launch_bounds__(kBlock) void pair_lower_k(PairArgs a, unsigned long long* rec) {
+  __shared__ unsigned long long lds[kWavesPerBlock];
+  PairCounts c = {};
+  const int64_t nb = (a.M + kBlock - 1) / kBlock;
+  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
+    const int64_t i = b * kBlock + threadIdx.x;
+    if (i >= a.M) continue;
+    const int64_t m = lower_entry_(a, i, c);
+    const int64_t r = a.read[i];
+    if (m > 0 && r >= 0 && r < a.R) atomicAdd((unsigned long long*)(a.lower + r), (unsigned long long)m);
+  }
+  block_count_add(c.runs, lds, rec + kOvlRuns);
+  block_count_add(c.skipped_runs, lds, rec + kOvlSkippedRuns);
+  block_count_add(c.skipped_entries, lds, rec + kOvlSkippedEntries);
+  block_count_add(c.same_read, lds, rec + kOvlSameRead);
+  block_count_add(c.hits, lds, rec + kOvlHits);
 }
 
 // ---- stage 3 -------------------------------------------------------------------------------------------------------------------
@@ -503,6 +544,127 @@ extern "C" int gnm_seed_pairs_host(int64_t M, const int64_t* hash, const int32_t
   }
   rec[kOvlHits] += run;
   return 0;
+}
+
+// ---- stage 2 in read-range chunks: the plan (hits per lower read) and the hits of one range of lower reads ----------------------
+static int lower_check(const char* what, const int64_t* lower_hits, int64_t R) {
+  GNM_CHECK_ARG(R >= 0 && R < INT32_MAX, "%s: R = %lld: expected 0 <= R < 2^31 - 1", what, (long long)R);
+  GNM_CHECK_ARG(R == 0 || (lower_hits && ((uintptr_t)lower_hits & 7) == 0), "%s: lower_hits must be non-null and 8-byte aligned when R > 0",
+                what);
+  return 0;
+}
+
+static int range_check(const char* what, int64_t a_lo, int64_t a_hi, int64_t R) {
+  GNM_CHECK_ARG(0 <= a_lo && a_lo <= a_hi && a_hi <= R, "%s: a_lo = %lld, a_hi = %lld: expected 0 <= a_lo <= a_hi <= R = %lld", what,
+                (long long)a_lo, (long long)a_hi, (long long)R);
+  return 0;
+}
+
+extern "C" int gnm_seed_pairs_lower_hits(int64_t M, const int64_t* hash, const int32_t* read, int max_occ, int64_t* lower_hits, int64_t R,
+                                         void* record, void* ws, size_t ws_bytes, void* stream) {
+  if (pairs_check("seed_pairs_lower_hits", M, hash, read, max_occ) || lower_check("seed_pairs_lower_hits", lower_hits, R)) return -1;
+  if (record_check("seed_pairs_lower_hits", record, "gnm_overlap_record")) return -1;
+  (void)ws;                                                // no scan: the counts are summed where they belong
+  (void)ws_bytes;
+  if (M == 0) return 0;
+  PairArgs a = {};
+  a.M = M; a.R = R; a.hash = hash; a.read = read; a.max_occ = max_occ; a.lower = lower_hits;
+  hipLaunchKernelGGL(pair_lower_k, dim3(persistent_grid((M + kBlock - 1) / kBlock, 1, 8)), dim3(kBlock), 0, (hipStream_t)stream, a,
+                     (unsigned long long*)record);
+  GNM_LAUNCH_CHECK("seed_pairs_lower_hits");
+  return 0;
+}
+
+extern "C" int gnm_seed_pairs_lower_hits_host(int64_t M, const int64_t* hash, const int32_t* read, int max_occ, int64_t* lower_hits,
+                                              int64_t R, void* record, int threads) {
+  if (pairs_check("seed_pairs_lower_hits_host", M, hash, read, max_occ) || lower_check("seed_pairs_lower_hits_host", lower_hits, R)) return -1;
+  if (record_check("seed_pairs_lower_hits_host", record, "gnm_overlap_record") || threads_check("seed_pairs_lower_hits_host", threads)) return -1;
+  PairArgs a = {};
+  a.M = M; a.R = R; a.hash = hash; a.read = read; a.max_occ = max_occ;
+  std::vector<int64_t> mine((size_t)M, 0);
+  std::vector<PairCounts> cs((size_t)threads, PairCounts{});
+  host_ranges_(M, threads, [&](int t, int64_t i0, int64_t i1) {
+    for (int64_t i = i0; i < i1; ++i) mine[(size_t)i] = lower_entry_(a, i, cs[(size_t)t]);
+  });
+  for (int64_t i = 0; i < M; ++i)
+    if (read[i] >= 0 && read[i] < R) lower_hits[read[i]] += mine[(size_t)i];
+  int64_t* rec = (int64_t*)record;
+  for (const PairCounts& c : cs) {
+    rec[kOvlRuns] += (int64_t)c.runs; rec[kOvlSkippedRuns] += (int64_t)c.skipped_runs;
+    rec[kOvlSkippedEntries] += (int64_t)c.skipped_entries; rec[kOvlSameRead] += (int64_t)c.same_read;
+    rec[kOvlHits] += (int64_t)c.hits;
+  }
+  return 0;
+}
+
+extern "C" int gnm_seed_pairs_count_range(int64_t M, const int64_t* hash, const int32_t* read, int max_occ, int64_t a_lo, int64_t a_hi,
+                                          int64_t R, int64_t* off, void* record, void* ws, size_t ws_bytes, void* stream) {
+  if (pairs_check("seed_pairs_count_range", M, hash, read, max_occ)) return -1;
+  GNM_CHECK_ARG(R >= 0 && R < INT32_MAX, "seed_pairs_count_range: R = %lld: expected 0 <= R < 2^31 - 1", (long long)R);
+  if (range_check("seed_pairs_count_range", a_lo, a_hi, R) || record_check("seed_pairs_count_range", record, "gnm_overlap_record")) return -1;
+  GNM_CHECK_ARG(off, "seed_pairs_count_range: off must not be null");
+  if (ws_check("seed_pairs_count_range", "gnm_overlap_scan_workspace_bytes", ws, ws_bytes, gnm_overlap_scan_workspace_bytes(M))) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  PairArgs a = {};
+  a.M = M; a.R = R; a.hash = hash; a.read = read; a.max_occ = max_occ; a.off = off; a.a_lo = a_lo; a.a_hi = a_hi;
+  if (M > 0)
+    hipLaunchKernelGGL((pair_k<false, true>), dim3(persistent_grid((M + kBlock - 1) / kBlock, 1, 8)), dim3(kBlock), 0, st, a,
+                       (unsigned long long*)nullptr);
+  ovl_scan(off, M, (int64_t*)ws, nullptr, st);             // the record stays as it is: the planning call added the totals
+  GNM_LAUNCH_CHECK("seed_pairs_count_range");
+  return 0;
+}
+
+extern "C" int gnm_seed_pairs_emit_range(int64_t M, const int64_t* hash, const int32_t* read, const int32_t* pos, const uint8_t* strand,
+                                         const int64_t* length, int64_t R, int k, int max_occ, int64_t a_lo, int64_t a_hi,
+                                         const int64_t* off, int64_t N, int64_t* key, int32_t* diag, void* stream) {
+  if (pairs_check("seed_pairs_emit_range", M, hash, read, max_occ) || pairs_emit_check("seed_pairs_emit_range", M, pos, strand, length, R, k))
+    return -1;
+  if (range_check("seed_pairs_emit_range", a_lo, a_hi, R)) return -1;
+  GNM_CHECK_ARG(N >= 0, "seed_pairs_emit_range: N = %lld: expected >= 0", (long long)N);
+  if (M == 0 || N == 0) return 0;
+  GNM_CHECK_ARG(off && key && diag, "seed_pairs_emit_range: off, key and diag must not be null when there are hits");
+  PairArgs a = {};
+  a.M = M; a.R = R; a.N = N; a.hash = hash; a.read = read; a.pos = pos; a.strand = strand; a.length = length; a.k = k;
+  a.max_occ = max_occ; a.off = const_cast<int64_t*>(off); a.key = key; a.diag = diag; a.a_lo = a_lo; a.a_hi = a_hi;
+  hipLaunchKernelGGL((pair_k<true, true>), dim3(persistent_grid((M + kBlock - 1) / kBlock, 1, 8)), dim3(kBlock), 0, (hipStream_t)stream, a,
+                     (unsigned long long*)nullptr);
+  GNM_LAUNCH_CHECK("seed_pairs_emit_range");
+  return 0;
+}
+
+extern "C" int gnm_seed_pairs_range_host(int64_t M, const int64_t* hash, const int32_t* read, const int32_t* pos, const uint8_t* strand,
+                                         const int64_t* length, int64_t R, int k, int max_occ, int64_t a_lo, int64_t a_hi,
+                                         int64_t capacity, int64_t* key, int32_t* diag, int64_t* total, void* record, int threads) {
+  if (pairs_check("seed_pairs_range_host", M, hash, read, max_occ) || pairs_emit_check("seed_pairs_range_host", M, pos, strand, length, R, k))
+    return -1;
+  if (range_check("seed_pairs_range_host", a_lo, a_hi, R)) return -1;
+  if (record_check("seed_pairs_range_host", record, "gnm_overlap_record") || threads_check("seed_pairs_range_host", threads)) return -1;
+  GNM_CHECK_ARG(total, "seed_pairs_range_host: total must not be null");
+  PairArgs a = {};
+  a.M = M; a.R = R; a.hash = hash; a.read = read; a.pos = pos; a.strand = strand; a.length = length; a.k = k; a.max_occ = max_occ;
+  a.a_lo = a_lo; a.a_hi = a_hi;
+  std::vector<int64_t> off((size_t)M + 1, 0);
+  host_ranges_(M, threads, [&](int, int64_t i0, int64_t i1) {
+    PairCounts unused = {};
+    for (int64_t i = i0; i < i1; ++i) off[(size_t)i] = pair_entry_<true>(a, i, 0, false, unused);
+  });
+  int64_t run = 0;
+  for (int64_t i = 0; i <= M; ++i) {
+    const int64_t v = off[(size_t)i];
+    off[(size_t)i] = run;
+    run += i < M ? v : 0;
+  }
+  *total = run;
+  if (capacity < 0) return 0;
+  GNM_CHECK_ARG(capacity >= run && (run == 0 || (key && diag)), "seed_pairs_range_host: %lld hits need room, capacity = %lld (or an output is null)",
+                (long long)run, (long long)capacity);
+  a.N = run; a.key = key; a.diag = diag;
+  host_ranges_(M, threads, [&](int, int64_t i0, int64_t i1) {
+    PairCounts unused = {};
+    for (int64_t i = i0; i < i1; ++i) pair_entry_<true>(a, i, off[(size_t)i], true, unused);
+  });
+  return 0;                                                // the record stays as it is, as after the device calls
 }
 
 static int chain_check(const char* what, int64_t N, const int64_t* key, const int32_t* diag, const int64_t* length, int64_t R, int64_t band,

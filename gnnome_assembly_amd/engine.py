@@ -2717,6 +2717,52 @@ def seed_pairs(hash_, read, pos, strand, length, k: int, max_occ: int, rec, thre
         lambda off, out: _call("gnm_seed_pairs_emit", *head(_ptr), *off, out[0].numel(), *map(_ptr, out), _stream()))
 
 
+def seed_pairs_lower_hits(hash_, read, R: int, max_occ: int, lower_hits, rec, threads: int = 1):
+    """The plan of the chunked route (stage 2 in read-range chunks): lower_hits int64 [R], zeroed by the caller, receives per read
+    the hits whose lower read id it is; rec is added to exactly as by seed_pairs' count pass.  hash_ int64, read int32 [M] sorted
+    stably by hash_.  Device tensors: gnm_seed_pairs_lower_hits, one launch, no read-back.  CPU tensors: the host twin."""
+    lib = _lib.load()
+    M = int(hash_.numel())
+    R, max_occ = _int_in("seed_pairs_lower_hits", "R", R, 0, 2 ** 31 - 2), _int_in("seed_pairs_lower_hits", "max_occ", max_occ, 1, OVERLAP_MAX_OCC)
+    _chk_record("seed_pairs_lower_hits", rec, OVERLAP_RECORD_WORDS, "rec")
+    _chk_args("seed_pairs_lower_hits", ("hash", hash_, torch.int64, M), ("read", read, torch.int32, M),
+              ("lower_hits", lower_hits, torch.int64, R))
+    dev = hash_.device
+    if dev.type == "cpu":
+        _cpu_tensors("seed_pairs_lower_hits", hash_, read, lower_hits, rec)
+        _lib.check(lib.gnm_seed_pairs_lower_hits_host(M, _hp(hash_), _hp(read), max_occ, _hp(lower_hits), R, _hp(rec), int(threads)),
+                   "gnm_seed_pairs_lower_hits_host")
+        return lower_hits
+    _chk_dev(hash_, read, lower_hits, rec)
+    if any(t.device != dev for t in (read, lower_hits, rec)):
+        raise ValueError("seed_pairs_lower_hits: every tensor must be on the device of hash")
+    with torch.cuda.device(dev):
+        _call("gnm_seed_pairs_lower_hits", M, _ptr(hash_), _ptr(read), max_occ, _ptr(lower_hits), R, _ptr(rec), None, 0, _stream())
+    return lower_hits
+
+
+def seed_pairs_range(hash_, read, pos, strand, length, k: int, max_occ: int, a_lo: int, a_hi: int, rec, threads: int = 1):
+    """seed_pairs restricted to the hits whose lower read id lies in [a_lo, a_hi), 0 <= a_lo <= a_hi <= R, in seed_pairs' order:
+    (key int64, diag int32).  rec is checked and left as it is (seed_pairs_lower_hits added the totals)."""
+    M, R = int(hash_.numel()), int(length.numel())
+    k, max_occ = _int_in("seed_pairs_range", "k", k, *SKETCH_K), _int_in("seed_pairs_range", "max_occ", max_occ, 1, OVERLAP_MAX_OCC)
+    a_lo, a_hi = _int_in("seed_pairs_range", "a_lo", a_lo, 0, R), _int_in("seed_pairs_range", "a_hi", a_hi, 0, R)
+    if a_lo > a_hi:
+        raise ValueError(f"seed_pairs_range: a_lo={a_lo} > a_hi={a_hi}: expected 0 <= a_lo <= a_hi <= {R}")
+    _chk_record("seed_pairs_range", rec, OVERLAP_RECORD_WORDS, "rec")
+    _chk_args("seed_pairs_range", ("hash", hash_, torch.int64, M), ("read", read, torch.int32, M), ("pos", pos, torch.int32, M),
+              ("strand", strand, torch.uint8, M), ("length", length, torch.int64, R))
+    dev = hash_.device
+    head = lambda p: (M, p(hash_), p(read), p(pos), p(strand), p(length), R, k, max_occ, a_lo, a_hi)  # noqa: E731
+    return _count_then_emit(
+        "seed_pairs_range", (hash_, read, pos, strand, length), rec, threads, head,
+        lambda m: (_new(dev, m, torch.int64), _new(dev, m, torch.int32)), (),
+        (M + 1,),                                            # off
+        lambda off, ws, need: _call("gnm_seed_pairs_count_range", M, _ptr(hash_), _ptr(read), max_occ, a_lo, a_hi, R, *off, _ptr(rec), ws,
+                                    need, _stream()),
+        lambda off, out: _call("gnm_seed_pairs_emit_range", *head(_ptr), *off, out[0].numel(), *map(_ptr, out), _stream()))
+
+
 def chain_pairs(key, diag, length, band: int, min_hits: int, min_overlap: int, rec, threads: int = 1):
     """The chains of the seed hits sorted by diag, then stably by key (stage 3): (src int32, dst int32, prefix_length int64,
     overlap_length int64, valid uint8) [2 G] -- group g owns slots 2g (the edge) and 2g + 1 (its twin) -- and contained uint8 [R]."""

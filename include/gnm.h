@@ -1048,6 +1048,17 @@ int gnm_resolve_layout(int64_t C, int64_t P, int64_t n, int64_t E, const int32_t
  *   key = a << 32 | b << 1 | rel (int64).  Order of the hits: by i, then by j ascending.
  *   gnm_seed_pairs_count: off int64 [M + 1]; record ADDS runs, skipped_runs, skipped_entries, same_read, hits.  The caller reads
  *   `hits` (N), calls gnm_seed_pairs_emit.
+ *   Stage 2 in read-range chunks (five more symbols, same rule: GNM_ABI_VERSION stays 7).  a(hit) is the lower read id of the hit's two
+ *   entries, the `a` of its key.  Every hit of a chain group carries the same a, and hits sorted by key are a-major; so the hits with
+ *   a_lo <= a(hit) < a_hi, sorted and chained on their own, give the slots of exactly the groups whose a lies in the range, and
+ *   consecutive ranges, concatenated, give the unchunked call's arrays.  Same input as gnm_seed_pairs_count.
+ *   gnm_seed_pairs_lower_hits: lower_hits int64 [R], which the caller zeroes: lower_hits[r] += #{hits : a(hit) == r}, the entries of
+ *   each entry's run that have a larger read id (counted directly: no order inside a run is assumed; 64-bit integer atomics, near one
+ *   per entry).  An entry whose read id is outside [0, R) counts in no lower_hits word (then sum(lower_hits) < hits); a sketch
+ *   of R reads has none.  record ADDS exactly what gnm_seed_pairs_count adds.  ws is not used (NULL, 0 are accepted).
+ *   gnm_seed_pairs_count_range / _emit_range: gnm_seed_pairs_count / _emit restricted to the hits with a_lo <= a(hit) < a_hi
+ *   (0 <= a_lo <= a_hi <= R), in the same order; the record stays as it is (gnm_seed_pairs_lower_hits added the totals); the
+ *   range's size is off[M].  With a_lo = 0, a_hi = R: the outputs of gnm_seed_pairs_count / _emit.
  * Stage 3, chains.  Input: the N hits sorted by diag, then stably by key: group (a, b, rel) holds its diagonals ascending, d_0 ..
  *   d_{g-1}.  c_i = #{j >= i : d_j <= d_i + band}; the window is the i of largest c_i, the lowest among equals; hits = c_i,
  *   D = d_{i + (c_i - 1) / 2}.  hits < min_hits: rejected (few_hits).  With la, lb the reads' lengths:
@@ -1066,7 +1077,7 @@ int gnm_resolve_layout(int64_t C, int64_t P, int64_t n, int64_t E, const int32_t
  * size to allocate) and the record stays as it is; otherwise capacity >= *total is required and the record is added to as by the
  * device calls of the stage.  One integer atomic per record word and workgroup; no workgroup waits for another: outputs and
  * record depend on the inputs alone, not on the grid or gnm_set_occupancy_cap.  k, w, max_occ, band, min_hits out of range,
- * counts negative or too large, a NULL or misaligned record / ws / packed, NULL arrays that the sizes need and (host) threads
+ * counts negative or too large, a_lo / a_hi out of order or range, a NULL or misaligned record / ws / packed / lower_hits, NULL arrays that the sizes need and (host) threads
  * outside [1, 1024] are errors, returned before anything runs.                                                                      */
 #define GNM_SKETCH_TILE 512
 typedef struct gnm_overlap_record {
@@ -1092,6 +1103,18 @@ int gnm_seed_pairs_emit(int64_t M, const int64_t* hash, const int32_t* read, con
 int gnm_seed_pairs_host(int64_t M, const int64_t* hash, const int32_t* read, const int32_t* pos, const uint8_t* strand,
                         const int64_t* length, int64_t R, int k, int max_occ, int64_t capacity, int64_t* key, int32_t* diag,
                         int64_t* total, void* record, int threads);
+int gnm_seed_pairs_lower_hits(int64_t M, const int64_t* hash, const int32_t* read, int max_occ, int64_t* lower_hits, int64_t R,
+                              void* record, void* ws, size_t ws_bytes, void* stream);
+int gnm_seed_pairs_lower_hits_host(int64_t M, const int64_t* hash, const int32_t* read, int max_occ, int64_t* lower_hits, int64_t R,
+                                   void* record, int threads);
+int gnm_seed_pairs_count_range(int64_t M, const int64_t* hash, const int32_t* read, int max_occ, int64_t a_lo, int64_t a_hi, int64_t R,
+                               int64_t* off, void* record, void* ws, size_t ws_bytes, void* stream);
+int gnm_seed_pairs_emit_range(int64_t M, const int64_t* hash, const int32_t* read, const int32_t* pos, const uint8_t* strand,
+                              const int64_t* length, int64_t R, int k, int max_occ, int64_t a_lo, int64_t a_hi, const int64_t* off,
+                              int64_t N, int64_t* key, int32_t* diag, void* stream);
+int gnm_seed_pairs_range_host(int64_t M, const int64_t* hash, const int32_t* read, const int32_t* pos, const uint8_t* strand,
+                              const int64_t* length, int64_t R, int k, int max_occ, int64_t a_lo, int64_t a_hi, int64_t capacity,
+                              int64_t* key, int32_t* diag, int64_t* total, void* record, int threads);
 int gnm_chain_count(int64_t N, const int64_t* key, int64_t* off, void* record, void* ws, size_t ws_bytes, void* stream);
 int gnm_chain_pairs(int64_t N, const int64_t* key, const int32_t* diag, const int64_t* off, int64_t G, const int64_t* length, int64_t R,
                     int64_t band, int64_t min_hits, int64_t min_overlap, int32_t* src, int32_t* dst, int64_t* prefix_length,

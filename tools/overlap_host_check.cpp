@@ -1,6 +1,6 @@
 // Stand-alone host check of csrc/gnm_overlap.h (no GPU, no Python): random reads -- with N's, of every length around k, w and the
 // tile size, the last one ending the store exactly -- through the tile routines against a brute-force sketch, and random runs and
-// groups through the seed-hit and chain routines, meant to be built with a host sanitizer:
+// groups through the seed-hit (with the hits per lower read and the read-range test of the chunked route) and chain routines, meant to be built with a host sanitizer:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I gnnome_assembly_amd/csrc \
 //       tools/overlap_host_check.cpp -o overlap_host_check && ./overlap_host_check
 // Exit status 0 and "ok" when every case agrees.
@@ -158,6 +158,30 @@ int main() {
           diag.push_back(0);
           ovl_hit_(read.data(), pos.data(), strand.data(), length.data(), R, 15, j, i, key.back(), diag.back());
         }
+    }
+    // the chunked route: every entry's hits as the lower read (the reads of a run are in no order here) and the range test
+    int64_t lower_sum = 0, in_ranges = 0;
+    const int64_t cut = (int64_t)(rng() % (R + 1));
+    for (int64_t i = 0; i < M; ++i) {
+      int back;
+      bool skipped;
+      int64_t same_read, want = 0, lo = i, hi = i;
+      const int64_t got = ovl_lower_(hash.data(), read.data(), M, i, occ, back, skipped, same_read);
+      while (lo > 0 && hash[(size_t)lo - 1] == hash[(size_t)i]) --lo;
+      while (hi + 1 < M && hash[(size_t)hi + 1] == hash[(size_t)i]) ++hi;
+      for (int64_t j = lo; j <= hi && hi - lo + 1 <= occ; ++j) want += read[(size_t)j] > read[(size_t)i];
+      if (got != want) {
+        printf("lower hits differ: round %d entry %lld\n", round, (long long)i);
+        ++bad;
+      }
+      lower_sum += got;
+      for (int64_t j = i - back; !skipped && j < i; ++j)
+        if (read[(size_t)j] != read[(size_t)i])
+          in_ranges += (ovl_in_range_(read[(size_t)j], read[(size_t)i], 0, cut) ? 1 : 0) + (ovl_in_range_(read[(size_t)j], read[(size_t)i], cut, R) ? 1 : 0);
+    }
+    if (lower_sum != (int64_t)key.size() || in_ranges != (int64_t)key.size()) {
+      printf("lower hits or ranges do not add up: round %d\n", round);
+      ++bad;
     }
     std::vector<size_t> o(key.size());
     for (size_t i = 0; i < o.size(); ++i) o[i] = i;
