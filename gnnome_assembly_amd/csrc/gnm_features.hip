@@ -304,7 +304,8 @@ extern "C" size_t gnm_pagerank_pe_workspace_bytes(int64_t N) { return (size_t)3 
 extern "C" int gnm_pagerank_pe(int64_t N, int64_t E, const int32_t* isrc, const int32_t* in_ptr,
                                const int32_t* out_ptr, int pe_dim, double alpha, float* pe, void* ws,
                                size_t ws_bytes, void* stream) {
-  GNM_CHECK_ARG(N > 0 && E >= 0 && isrc && in_ptr && out_ptr && pe_dim >= 0 && pe, "pagerank_pe: bad argument");
+  // isrc may be null when E == 0 (an empty tensor has no storage): in_ptr is all zeros then and no kernel reads isrc
+  GNM_CHECK_ARG(N > 0 && E >= 0 && (E == 0 || isrc) && in_ptr && out_ptr && pe_dim >= 0 && pe, "pagerank_pe: bad argument");
   GNM_CHECK_ARG(ws && ws_bytes >= gnm_pagerank_pe_workspace_bytes(N), "pagerank_pe: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   double* x = (double*)ws;

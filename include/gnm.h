@@ -583,6 +583,7 @@ int gnm_seg_sum_rows(int64_t N, int W, const float* X, const int32_t* ptr, const
 /* ---- input feature preparation ("next" row: utils.py:67-74, 97-138; train.py:245-251) -------------
  * pagerank_pe: pe[N, 2+pe_dim] = in_deg | out_deg | pe_dim PageRank steps (alpha = 0.95 in the
  *              reference), fp64 iterate, from the graph index.  ws: gnm_pagerank_pe_workspace_bytes(N).
+ *              N > 0; E = 0 is a graph (degrees 0, every step (1-alpha)/N) and isrc may then be null.
  * edge_feats_zscore: e[E,2] = z-scored (overlap_length, overlap_similarity), unbiased std, in the
  *              caller's edge-id order.  ws: 4 * gnm_max_partial_blocks() doubles.                    */
 size_t gnm_pagerank_pe_workspace_bytes(int64_t N);

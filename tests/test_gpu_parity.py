@@ -768,21 +768,32 @@ def test_no_grad_forward_keeps_no_activations():
 @pytest.mark.mode_independent
 def test_feature_preparation_matches_reference(golden_dir):
     """utils.add_positional_encoding output of the reference (golden pe_pagerank.npz) and
-    utils.preprocess_graph's z-score, computed on the GPU from the graph index."""
+    utils.preprocess_graph's z-score, computed on the GPU from the graph index: every element within the per-element bars of
+    tests/features_reference.py of the fp64 statements there, and within one fp32 ulp of the golden file (which holds the
+    reference's fp32-rounded output)."""
     import gnnome_assembly_amd as G
+    from gnnome_assembly_amd import _lib
+    import features_reference as fr
     dev = _dev()
     z = np.load(os.path.join(golden_dir, "pe_pagerank.npz"))
-    g = G.AssemblyGraph(z["src"], z["dst"], int(z["n"])).to(dev)
+    n = int(z["n"])
+    g = G.AssemblyGraph(z["src"], z["dst"], n).to(dev)
     pe18 = G.features.positional_encoding(g, 16).cpu().numpy()
     assert np.array_equal(pe18[:, 0], z["in_deg"]) and np.array_equal(pe18[:, 1], z["out_deg"])
-    assert np.abs(pe18[:, 2:] - z["pe"]).max() <= 2e-7 * np.abs(z["pe"]).max()
+    assert np.all(np.abs(pe18[:, 2:] - z["pe"]) <= np.spacing(np.abs(z["pe"])))
+    want = fr.pagerank_pe64(z["src"], z["dst"], n, 16, 0.95)
+    r, i = fr.worst_ratio(pe18, want, fr.pagerank_bound(want, fr.max_in_degree(z["dst"], n), 16))
+    assert r <= 1.0, (r, np.unravel_index(i, want.shape), pe18.flat[i], want.flat[i])
     rng = np.random.default_rng(3)
     ln = rng.integers(500, 30000, size=z["src"].size).astype(np.float32)
     sim = rng.random(z["src"].size).astype(np.float32)
-    e = G.features.edge_features(torch.from_numpy(ln).to(dev), torch.from_numpy(sim).to(dev)).cpu()
-    tl, ts = torch.from_numpy(ln), torch.from_numpy(sim)
-    ref = torch.stack(((tl - tl.mean()) / tl.std(), (ts - ts.mean()) / ts.std()), 1)     # utils.py:72-74
-    assert float((e - ref).abs().max()) < 5e-6
+    e = G.features.edge_features(torch.from_numpy(ln).to(dev), torch.from_numpy(sim).to(dev)).cpu().numpy()
+    nb = fr.zs_blocks(ln.size, _lib.load().gnm_num_cus())
+    want = fr.zscore64(ln, sim)
+    for j, x in enumerate((ln, sim)):
+        assert fr.zscore_margin(x, nb) >= fr.MARGIN
+        r, i = fr.worst_ratio(e[:, j], want[:, j], fr.zscore_bound(want[:, j], x, nb))
+        assert r <= 1.0, (j, r, i, e[i, j], want[i, j])
 
 
 def test_training_harness_counterpart(tmp_path):
