@@ -68,6 +68,16 @@ inline int ws_check(const char* what, const char* sizer, const void* ws, size_t 
   return 0;
 }
 
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// Grid for the elementwise (grid-stride) kernels: one workgroup per `block` items, at most 8 per CU, at least 1
+inline int ew_grid(int64_t items, int block = kBlock) {
+  int64_t g = cdiv(items, block);
+  const int64_t cap = (int64_t)num_cus() * 8;
+  if (g > cap) g = cap;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
 // Grid for the persistent row/segment kernels: a multiple of 8 (one slice per XCD),
 // at most kMaxPartialBlocks, at least enough to give every block `min_items` items.
 // `call_cap` > 0: the caller's per-call cap on workgroups per CU (entry points that take max_blocks_per_cu);

@@ -290,14 +290,6 @@ __global__ __launch_bounds__(kBlock) void dec_pick_k(int64_t E, int64_t N, const
 
 using namespace gnm;
 
-static inline int fgrid(int64_t n) {
-  int64_t g = (n + 255) / 256;
-  const int64_t cap = (int64_t)num_cus() * 8;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // ws: 3*N doubles
 extern "C" size_t gnm_pagerank_pe_workspace_bytes(int64_t N) { return (size_t)3 * (size_t)N * sizeof(double); }
 
@@ -311,7 +303,7 @@ extern "C" int gnm_pagerank_pe(int64_t N, int64_t E, const int32_t* isrc, const 
   double* x = (double*)ws;
   double* xn = x + N;
   double* w = x + 2 * N;
-  const int ld = pe_dim + 2, g = fgrid(N);
+  const int ld = pe_dim + 2, g = ew_grid(N, 256);
   hipLaunchKernelGGL(pr_init_k, dim3(g), dim3(256), 0, st, N, in_ptr, out_ptr, x, pe, ld);
   for (int s = 0; s < pe_dim; ++s) {
     hipLaunchKernelGGL(pr_scale_k, dim3(g), dim3(256), 0, st, N, (const double*)x, out_ptr, w);
@@ -327,12 +319,12 @@ extern "C" int gnm_pagerank_pe(int64_t N, int64_t E, const int32_t* isrc, const 
 extern "C" int gnm_edge_feats_zscore(int64_t E, const float* overlap_length, const float* overlap_similarity,
                                      float* e, void* ws, size_t ws_bytes, void* stream) {
   GNM_CHECK_ARG(E > 1 && overlap_length && overlap_similarity && e, "edge_feats_zscore: bad argument");
-  int nb = fgrid(E);
+  int nb = ew_grid(E, 256);
   if (nb > kMaxPartialBlocks) nb = kMaxPartialBlocks;
   GNM_CHECK_ARG(ws && ws_bytes >= (size_t)nb * 4 * sizeof(double), "edge_feats_zscore: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(zs_stats_k, dim3(nb), dim3(kBlock), 0, st, E, overlap_length, overlap_similarity, (double*)ws);
-  hipLaunchKernelGGL(zs_apply_k, dim3(fgrid(E)), dim3(256), 0, st, E, overlap_length, overlap_similarity,
+  hipLaunchKernelGGL(zs_apply_k, dim3(ew_grid(E, 256)), dim3(256), 0, st, E, overlap_length, overlap_similarity,
                      (const double*)ws, nb, e);
   GNM_LAUNCH_CHECK("edge_feats_zscore");
   return 0;

@@ -1815,7 +1815,6 @@ __global__ __launch_bounds__(256) void slab_reduce_ld_k(const float* __restrict_
 
 using namespace gnm;
 
-static inline int64_t cdiv_(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // kernel-generation switches for same-process A/B runs (gnm_debug_set_variant, GNM_VARIANTS).  Round 5 removed the generations
 // that had lost their A/B (the round-1 split-mode edge backward / weight gradient / VALU encoders, the unpipelined t kernels,
@@ -1853,18 +1852,18 @@ static int edge_t_fused_impl(int64_t E, const float* e_in, const float* W3, cons
   launch_pack<MM>(W3, FH, FH / 32, 0, ws, st);
   GNM_LAUNCH_CHECK("pack_w (NT)");
   if constexpr (MM::kSplit) {
-    const int64_t ntiles = cdiv_(E, ER3);
+    const int64_t ntiles = cdiv(E, ER3);
     const int grid = persistent_grid(ntiles, 8, occ_blocks<edge_t32_b3p_k<MM>>());
     hipLaunchKernelGGL(edge_t32_b3p_k<MM>, dim3(grid), dim3(kBlock), 0, st, E, e_in, (const void*)ws, b3, t, P, isrc, idst,
-                       partials, cdiv_(ntiles, grid));
+                       partials, cdiv(ntiles, grid));
     GNM_LAUNCH_CHECK("edge_t_fused_fwd");
     *nblk_out = grid;
     return 0;
   }
-  const int64_t ntiles = cdiv_(E, FTR);
+  const int64_t ntiles = cdiv(E, FTR);
   const int grid = persistent_grid(ntiles, 4, occ_blocks<rowtile_nt_k<MM, true, 1>>());
   hipLaunchKernelGGL((rowtile_nt_k<MM, true, 1>), dim3(grid), dim3(kBlock), 0, st, E, e_in, (const void*)ws, b3, t,
-                     (int64_t)FH, P, isrc, idst, partials, cdiv_(ntiles, grid), 1);
+                     (int64_t)FH, P, isrc, idst, partials, cdiv(ntiles, grid), 1);
   GNM_LAUNCH_CHECK("edge_t_fused_fwd");
   *nblk_out = grid;
   return 0;
@@ -1882,14 +1881,14 @@ extern "C" int gnm_edge_t_fused_fwd(int64_t E, int H, const float* e_in, const f
     if (h2) launch_pack_w2_gen(W3, (int64_t)WH, 2, 2, 0, ws, st);
     else hipLaunchKernelGGL(pack_w3_gen_k, dim3(64), dim3(256), 0, st, W3, (int64_t)WH, 2, 2, 0, (bf16x8*)ws);
     GNM_LAUNCH_CHECK("pack_w3_gen (NT 256)");
-    const int64_t ntiles = cdiv_(E, ER3);
+    const int64_t ntiles = cdiv(E, ER3);
     int nchunk = num_cus() / 2 / kXcds * kXcds;            // one 8-wave workgroup per CU, two classes per chunk
     if (nchunk < kXcds) nchunk = kXcds;
     if (nchunk > kMaxPartialBlocks) nchunk = kMaxPartialBlocks / kXcds * kXcds;
     if (h2) hipLaunchKernelGGL(edge_t32_h256p_k<MmH2>, dim3(nchunk * 2), dim3(kBlockW), 0, st, E, e_in, (const void*)ws, b3, t, P, isrc, idst,
-                               partials, nchunk, cdiv_(ntiles, nchunk));
+                               partials, nchunk, cdiv(ntiles, nchunk));
     else hipLaunchKernelGGL(edge_t32_h256p_k<MmB3>, dim3(nchunk * 2), dim3(kBlockW), 0, st, E, e_in, (const void*)ws, b3, t, P, isrc, idst,
-                            partials, nchunk, cdiv_(ntiles, nchunk));
+                            partials, nchunk, cdiv(ntiles, nchunk));
     GNM_LAUNCH_CHECK("edge_t_fused_fwd (256)");
     *nblk_out = nchunk;
     return 0;
@@ -1913,13 +1912,13 @@ extern "C" int gnm_edge_bwd_gt_nn(int64_t E, int H, const float* ge, const float
   if (h2) launch_pack_w2_gen(W3, (int64_t)WH, 2, 2, 1, ws, st);
   else hipLaunchKernelGGL(pack_w3_gen_k, dim3(64), dim3(256), 0, st, W3, (int64_t)WH, 2, 2, 1, (bf16x8*)ws);
   GNM_LAUNCH_CHECK("pack_w3_gen (NN 256)");
-  const int64_t ntiles = cdiv_(E, ER3);
+  const int64_t ntiles = cdiv(E, ER3);
   int nchunk = num_cus() / 2 / kXcds * kXcds;
   if (nchunk < kXcds) nchunk = kXcds;
   if (h2) hipLaunchKernelGGL(edge_gt_nn_h256_k<MmH2>, dim3(nchunk * 2), dim3(kBlockW), 0, st, E, ge, t, stat_e, bstat_e, gamma_e, (const void*)ws,
-                             gt, ge_out, nchunk, cdiv_(ntiles, nchunk));
+                             gt, ge_out, nchunk, cdiv(ntiles, nchunk));
   else hipLaunchKernelGGL(edge_gt_nn_h256_k<MmB3>, dim3(nchunk * 2), dim3(kBlockW), 0, st, E, ge, t, stat_e, bstat_e, gamma_e, (const void*)ws,
-                          gt, ge_out, nchunk, cdiv_(ntiles, nchunk));
+                          gt, ge_out, nchunk, cdiv(ntiles, nchunk));
   GNM_LAUNCH_CHECK("edge_bwd_gt_nn");
   return 0;
 }
@@ -1930,7 +1929,7 @@ static int node_proj_fwd_impl(int64_t N, int ncols, const float* h, const float*
   hipStream_t st = (hipStream_t)stream;
   launch_pack<MM>(W, FH, ncols / 32, 0, ws, st);
   GNM_LAUNCH_CHECK("pack_w (NT, node)");
-  const int64_t ntiles = cdiv_(N, FTR);
+  const int64_t ntiles = cdiv(N, FTR);
   if constexpr (MM::kSplit) {
     // HBM-bound in split mode: column groups over workgroups, weights stationary (no reload per tile)
     const int ncg = ncols / FH;
@@ -1939,12 +1938,12 @@ static int node_proj_fwd_impl(int64_t N, int ncols, const float* h, const float*
     if (nslot < kXcds) nslot = kXcds;
     hipLaunchKernelGGL((rowtile_nt_k<MM, false, 1>), dim3(nslot * ncg), dim3(kBlock), 0, st, N, h, (const void*)ws, b,
                        Pout, (int64_t)ncols, (const float*)nullptr, (const int32_t*)nullptr,
-                       (const int32_t*)nullptr, (double*)nullptr, cdiv_(ntiles, nslot), ncg);
+                       (const int32_t*)nullptr, (double*)nullptr, cdiv(ntiles, nslot), ncg);
   } else {
     const int grid = persistent_grid(ntiles, 2, occ_blocks<rowtile_nt_k<MM, false, 5>>());
     hipLaunchKernelGGL((rowtile_nt_k<MM, false, 5>), dim3(grid), dim3(kBlock), 0, st, N, h, (const void*)ws, b, Pout,
                        (int64_t)ncols, (const float*)nullptr, (const int32_t*)nullptr,
-                       (const int32_t*)nullptr, (double*)nullptr, cdiv_(ntiles, grid), 1);
+                       (const int32_t*)nullptr, (double*)nullptr, cdiv(ntiles, grid), 1);
   }
   GNM_LAUNCH_CHECK("node_proj_fwd");
   return 0;
@@ -2144,10 +2143,10 @@ static int edge_bwd_fused_impl(int64_t E, const float* ge, float* ge_out, const 
   } else {
     launch_pack<MM>(W3, FH, FH / 32, 1, ws, st);
     GNM_LAUNCH_CHECK("pack_w (NN)");
-    const int64_t ntiles = cdiv_(E, FTR2);
+    const int64_t ntiles = cdiv(E, FTR2);
     grid = persistent_grid(ntiles, 8, occ_blocks<edge_bwd_fused32_k>());
     hipLaunchKernelGGL(edge_bwd_fused32_k, dim3(grid), dim3(kBlock), 0, st, E, ge, ge_out, t, e_in, stat_e, bstat_e,
-                       gamma_e, (const void*)ws, w3_slabs(ws), partials, cdiv_(ntiles, grid));
+                       gamma_e, (const void*)ws, w3_slabs(ws), partials, cdiv(ntiles, grid));
     GNM_LAUNCH_CHECK("edge_bwd_fused");
   }
   return w3_grad_reduce("edge_bwd_fused slab reduce", ws, partials, grid, gW3, gb3, stream);
@@ -2189,7 +2188,7 @@ static int tn_colgroups(int64_t N, const float* A, int64_t lda, int ncg, const f
   hipStream_t st = (hipStream_t)stream;
   // split mode: tn_tr_k (transpose reads); fp32-MFMA mode, and fewer rows than one tile of tn_tr_k in any mode: tn_colgroup_k
   const bool tr = cv || (g_matmul_mode && N >= tn_tr_rows_per_tile());
-  const int64_t ntiles = cdiv_(N, tr ? tn_tr_rows_per_tile() : FTR);
+  const int64_t ntiles = cdiv(N, tr ? tn_tr_rows_per_tile() : FTR);
   const bool h2 = g_matmul_mode == 2;                    // f16x2 (tn_tr_k<., ., true>)
   int occ = tr ? tn_tr_occupancy(cv != nullptr, h2) : occ_blocks<tn_colgroup_k<MmF32>>();
   if (max_blocks_per_cu > 0 && occ > max_blocks_per_cu) occ = max_blocks_per_cu;    // the caller shares the CUs with another stream
@@ -2199,10 +2198,10 @@ static int tn_colgroups(int64_t N, const float* A, int64_t lda, int ncg, const f
   nslot = nslot / kXcds * kXcds;             // whole slots per XCD (see tn_colgroup_k)
   if (nslot < kXcds) nslot = kXcds;          // empty slots write zero slabs
   if (tr)
-    tn_tr_launch(N, A, lda, ncg, B, FH, 1, slab, partials, nslot, cdiv_(ntiles, nslot), st, cv, h2);
+    tn_tr_launch(N, A, lda, ncg, B, FH, 1, slab, partials, nslot, cdiv(ntiles, nslot), st, cv, h2);
   else
     hipLaunchKernelGGL(tn_colgroup_k<MmF32>, dim3(nslot * ncg), dim3(kBlock), 0, st, N, A, lda, ncg, B, slab, partials,
-                       nslot, cdiv_(ntiles, nslot));
+                       nslot, cdiv(ntiles, nslot));
   GNM_LAUNCH_CHECK("tn_colgroup");
   // one launch each for all column groups (same per-element summation order as one launch per group)
   hipLaunchKernelGGL(slab_reduce_k, dim3(FH * FH / 128, ncg), dim3(256), 0, st, (const float*)slab, nslot, FH * FH, gW);
@@ -2222,7 +2221,7 @@ static bool gemm_b3_shape_ok(int mode, int64_t M, int64_t N, int64_t K) {
   return M >= 2048 && N > 0 && K > 0 && N % FH == 0 && K % FH == 0 && (N / FH) * (K / FH) <= 256;
 }
 static int gemm_b3_tn_slots(int64_t rows, int ncls) {
-  const int64_t ntiles = cdiv_(rows, tn_tr_rows_per_tile());
+  const int64_t ntiles = cdiv(rows, tn_tr_rows_per_tile());
   int nslot = (num_cus() * tn_tr_occupancy(false, g_matmul_mode == 2)) / ncls;
   if (nslot > kMaxPartialBlocks / ncls) nslot = kMaxPartialBlocks / ncls;
   if ((int64_t)nslot > ntiles) nslot = (int)ntiles;
@@ -2249,10 +2248,10 @@ int gnm::gemm_b3_try(int mode, int64_t M, int64_t N, int64_t K, const float* A, 
     if (bias || resid || relu || !al(B, ldb) || !al(C, ldc)) return 0;   // slab_reduce_ld_k stores float4 rows of C
     const int ncga = (int)(M / FH), ncgb = (int)(N / FH), ncls = ncga * ncgb;
     const int nslot = gemm_b3_tn_slots(K, ncls);
-    const int64_t ntiles = cdiv_(K, tn_tr_rows_per_tile());
+    const int64_t ntiles = cdiv(K, tn_tr_rows_per_tile());
     float* slab = (float*)ws;
     double* partials = (double*)((char*)ws + (size_t)ncls * nslot * FH * FH * sizeof(float));
-    tn_tr_launch(K, A, lda, ncga, B, ldb, ncgb, slab, partials, nslot, cdiv_(ntiles, nslot), st, nullptr, g_matmul_mode == 2);
+    tn_tr_launch(K, A, lda, ncga, B, ldb, ncgb, slab, partials, nslot, cdiv(ntiles, nslot), st, nullptr, g_matmul_mode == 2);
     hipLaunchKernelGGL(slab_reduce_ld_k, dim3(FH, ncls), dim3(256), 0, st, (const float*)slab, nslot, ncgb, C, ldc);   // one launch for all blocks
     return hipGetLastError() == hipSuccess ? 1 : -2;
   }
@@ -2263,15 +2262,15 @@ int gnm::gemm_b3_try(int mode, int64_t M, int64_t N, int64_t K, const float* A, 
   else hipLaunchKernelGGL(pack_w3_gen_k, dim3(4 * ncls * ncg), dim3(256), 0, st, B, ldb, ncls, ncg, mode == GNM_GEMM_NN ? 1 : 0,
                           (bf16x8*)ws);
   constexpr int T = 4;
-  const int64_t ngroups = cdiv_(M, NR3 * T);
+  const int64_t ngroups = cdiv(M, NR3 * T);
   int nchunk = (num_cus() * (h2 ? occ_blocks<gemm_rows_b3_k<MmH2, T>>() : occ_blocks<gemm_rows_b3_k<MmB3, T>>())) / ncls;
   if ((int64_t)nchunk > ngroups) nchunk = (int)ngroups;
   nchunk = nchunk / kXcds * kXcds;
   if (nchunk < kXcds) nchunk = kXcds;
   if (h2) hipLaunchKernelGGL((gemm_rows_b3_k<MmH2, T>), dim3(nchunk * ncls), dim3(kBlock), 0, st, M, A, lda, ncg, ncls, (const void*)ws,
-                             bias, resid, ldr, relu, C, ldc, nchunk, cdiv_(ngroups, nchunk));
+                             bias, resid, ldr, relu, C, ldc, nchunk, cdiv(ngroups, nchunk));
   else hipLaunchKernelGGL((gemm_rows_b3_k<MmB3, T>), dim3(nchunk * ncls), dim3(kBlock), 0, st, M, A, lda, ncg, ncls, (const void*)ws,
-                          bias, resid, ldr, relu, C, ldc, nchunk, cdiv_(ngroups, nchunk));
+                          bias, resid, ldr, relu, C, ldc, nchunk, cdiv(ngroups, nchunk));
   return hipGetLastError() == hipSuccess ? 1 : -2;
 }
 // the same TN product plus the column sums of A (a Linear's bias gradient beside its weight gradient): tn_tr_k keeps them
@@ -2306,9 +2305,9 @@ static int node_proj_bwd_nn_split(int64_t N, int ncols, const float* gP, const f
   if constexpr (MM::kScaled) launch_pack_w2_gen(W, (int64_t)FH, 1, ncg, 1, ws, st);
   else hipLaunchKernelGGL(pack_w3_gen_k, dim3(4 * ncg), dim3(256), 0, st, W, (int64_t)FH, 1, ncg, 1, (bf16x8*)ws);
   GNM_LAUNCH_CHECK("pack_w (NN, node)");
-  const int64_t ngroups = cdiv_(N, NR3 * T);
+  const int64_t ngroups = cdiv(N, NR3 * T);
   const int grid = persistent_grid(ngroups, 1, partials ? occ_blocks<rowtile_nn2_k<MM, T>>() : occ_blocks<rowtile_nn_group32_b3_k<MM, T>>());
-  const Nn2Args a{N, gP, (int64_t)ncols, ncg, (const void*)ws, gh_out, gh_in, cdiv_(ngroups, grid), z_lo, stat_h_lo, partials};
+  const Nn2Args a{N, gP, (int64_t)ncols, ncg, (const void*)ws, gh_out, gh_in, cdiv(ngroups, grid), z_lo, stat_h_lo, partials};
   if (partials) {
     hipLaunchKernelGGL((rowtile_nn2_k<MM, T>), dim3(grid), dim3(kBlock), 0, st, a);
     *nblk_out = grid;
@@ -2330,10 +2329,10 @@ static int node_proj_bwd_nn(int64_t N, int ncols, const float* gP, const float* 
     for (int cg = 0; cg < ncg; ++cg)
       launch_pack<MM>(W + (size_t)cg * FH * FH, FH, FH / 32, 1, (char*)ws + (size_t)cg * 4 * MM::kPackBytes, st);
     GNM_LAUNCH_CHECK("pack_w (NN, node)");
-    const int64_t ntiles = cdiv_(N, FTR);
+    const int64_t ntiles = cdiv(N, FTR);
     const int grid = persistent_grid(ntiles, 2, occ_blocks<rowtile_nn_acc_k<MM>>());
     hipLaunchKernelGGL(rowtile_nn_acc_k<MM>, dim3(grid), dim3(kBlock), 0, st, N, gP, (int64_t)ncols, ncg,
-                       (const void*)ws, gh_out, gh_in, cdiv_(ntiles, grid));
+                       (const void*)ws, gh_out, gh_in, cdiv(ntiles, grid));
     GNM_LAUNCH_CHECK("node_proj_bwd (NN)");
     return 0;
   }

@@ -516,22 +516,13 @@ using namespace gnm;
     default: ::gnm::set_error("H=%d unsupported (32, 64, 128, 256)", (int)(H)); return -1; \
   }
 
-static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int ew_grid(int64_t items) {
-  int64_t g = ceil_div64(items, kBlock);
-  const int64_t cap = (int64_t)num_cus() * 8;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 extern "C" int gnm_edge_t_stats_fwd(int64_t E, int H, float* t, const float* P, const int32_t* isrc,
                                     const int32_t* idst, double* partials, int* nblk_out,
                                     void* stream) {
   GNM_CHECK_ARG(E >= 0 && t && P && isrc && idst && partials && nblk_out, "edge_t_stats_fwd: null/neg argument");
   GNM_DISPATCH_H(H, {
     const int grid = persistent_grid(E, 256, occ_blocks<edge_t_stats_fwd_k<HH>>());
-    const int64_t rpb = ceil_div64(E, grid);
+    const int64_t rpb = cdiv(E, grid);
     hipLaunchKernelGGL(edge_t_stats_fwd_k<HH>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, E, t, P, isrc, idst, partials, rpb);
     *nblk_out = grid;
   });
@@ -547,7 +538,7 @@ extern "C" int gnm_edge_gate_fwd(int64_t N, int64_t E, int H, const float* t, co
                 "edge_gate_fwd: null/neg argument");      // e_in == NULL: no residual (residual=False / in != out)
   GNM_DISPATCH_H(H, {
     const int grid = persistent_grid(N, 64, occ_blocks<edge_gate_fwd_k<HH>>());
-    const int64_t npb = ceil_div64(N, grid);
+    const int64_t npb = cdiv(N, grid);
     if (e_in)
       hipLaunchKernelGGL((edge_gate_fwd_k<HH, true>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, t, e_in, stat_e, P, isrc, in_ptr, e_out, hf, inv_f, npb);
     else
@@ -565,7 +556,7 @@ extern "C" int gnm_node_agg_src_fwd(int64_t N, int64_t E, int H, const float* e_
                     partials && nblk_out, "node_agg_src_fwd: null/neg argument");
   GNM_DISPATCH_H(H, {
     const int grid = persistent_grid(N, 64, occ_blocks<node_agg_src_fwd_k<HH>>());
-    const int64_t npb = ceil_div64(N, grid);
+    const int64_t npb = cdiv(N, grid);
     hipLaunchKernelGGL(node_agg_src_fwd_k<HH>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, e_out, P, out_ptr, out_pos, out_dst, hf, hb, inv_b, z, partials, npb);
     *nblk_out = grid;
   });
@@ -591,7 +582,7 @@ extern "C" int gnm_node_bwd_stats(int64_t N, int H, const float* z, const float*
   GNM_CHECK_ARG(N >= 0 && z && stat_h && gh_out && partials && nblk_out, "node_bwd_stats: null/neg argument");
   GNM_DISPATCH_H(H, {
     const int grid = persistent_grid(N, 256, occ_blocks<node_bwd_stats_k<HH>>());
-    const int64_t rpb = ceil_div64(N, grid);
+    const int64_t rpb = cdiv(N, grid);
     hipLaunchKernelGGL(node_bwd_stats_k<HH>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, z, stat_h, gh_out, partials, rpb);
     *nblk_out = grid;
   });
@@ -620,7 +611,7 @@ extern "C" int gnm_edge_bwd_dst(int64_t N, int64_t E, int H, const float* e_out,
                     partials && nblk_out, "edge_bwd_dst: null/neg argument");
   GNM_DISPATCH_H(H, {
     const int grid = persistent_grid(N, 64, occ_blocks<edge_bwd_dst_k<HH>>());
-    const int64_t npb = ceil_div64(N, grid);
+    const int64_t npb = cdiv(N, grid);
     hipLaunchKernelGGL(edge_bwd_dst_k<HH>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, e_out, t, stat_e, ge, P, Q, hf, hb, isrc, in_ptr, gP, Ud, Td, partials, npb);
     *nblk_out = grid;
   });
@@ -637,7 +628,7 @@ extern "C" int gnm_edge_bwd_src(int64_t N, int64_t E, int H, const float* e_out,
                     out_pos && out_dst && Ud && Td && gP && max_blocks_per_cu >= 0, "edge_bwd_src: null/neg argument");
   GNM_DISPATCH_H(H, {
     const int grid = persistent_grid(N, 64, occ_blocks<edge_bwd_src_k<HH>>(), max_blocks_per_cu);
-    const int64_t npb = ceil_div64(N, grid);
+    const int64_t npb = cdiv(N, grid);
     hipLaunchKernelGGL(edge_bwd_src_k<HH>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, e_out, t, stat_e, bstat_e, gamma_e, ge, Q, in_ptr, out_ptr, out_pos, out_dst, Ud, Td, gP, npb);
   });
   GNM_LAUNCH_CHECK("edge_bwd_src");
@@ -652,7 +643,7 @@ extern "C" int gnm_edge_bwd_src_fix(int64_t nfix, const int32_t* fix_nodes, int6
                     out_pos && out_dst && gP && UT, "edge_bwd_src_fix: null/neg argument");
   if (nfix == 0) return 0;
   GNM_DISPATCH_H(H, {
-    int64_t grid = ceil_div64(nfix, kWavesPerBlock);
+    int64_t grid = cdiv(nfix, kWavesPerBlock);
     const int64_t cap = (int64_t)num_cus() * occ_blocks<edge_bwd_src_fix_k<HH>>();
     if (grid > cap) grid = cap;
     hipLaunchKernelGGL(edge_bwd_src_fix_k<HH>, dim3((int)grid), dim3(kBlock), 0, (hipStream_t)stream, nfix, fix_nodes,

@@ -524,15 +524,6 @@ using namespace gnm;
     default: ::gnm::set_error("H=%d unsupported (32, 64, 128, 256)", (int)(H)); return -1; \
   }
 
-static inline int64_t cdivl(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int ewgrid(int64_t items) {
-  int64_t g = cdivl(items, kBlock);
-  const int64_t cap = (int64_t)num_cus() * 8;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 extern "C" int gnm_ln_edge_gate_fwd(int64_t N, int64_t E, int H, const float* t, const float* e_in,
                                     const float* gamma, const float* beta, const float* P,
                                     const int32_t* isrc, const int32_t* in_ptr, float* e_out, float* hf,
@@ -544,10 +535,10 @@ extern "C" int gnm_ln_edge_gate_fwd(int64_t N, int64_t E, int H, const float* t,
     const int grid = persistent_grid(N, 64, occ_blocks<ln_edge_gate_fwd_k<HH>>());
     if (e_in)
       hipLaunchKernelGGL((ln_edge_gate_fwd_k<HH, true>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, t, e_in, gamma,
-                         beta, P, isrc, in_ptr, e_out, hf, inv_f, cdivl(N, grid), width);
+                         beta, P, isrc, in_ptr, e_out, hf, inv_f, cdiv(N, grid), width);
     else
       hipLaunchKernelGGL((ln_edge_gate_fwd_k<HH, false>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, t, e_in, gamma,
-                         beta, P, isrc, in_ptr, e_out, hf, inv_f, cdivl(N, grid), width);
+                         beta, P, isrc, in_ptr, e_out, hf, inv_f, cdiv(N, grid), width);
   });
   GNM_LAUNCH_CHECK("ln_edge_gate_fwd");
   return 0;
@@ -558,9 +549,9 @@ extern "C" int gnm_ln_node_update_fwd(int64_t N, int H, const float* z, const fl
   GNM_CHECK_ARG(N >= 0 && z && gamma && beta && h_out && width >= 1 && width <= H, "ln_node_update_fwd: null/neg argument or width outside [1, H]");   // h_in == NULL: no residual
   GNM_DISPATCH_H(H, {
     if (h_in)
-      hipLaunchKernelGGL((ln_node_update_fwd_k<HH, true>), dim3(ewgrid(N * (HH / 4))), dim3(kBlock), 0, (hipStream_t)stream, N, z, gamma, beta, h_in, h_out, width);
+      hipLaunchKernelGGL((ln_node_update_fwd_k<HH, true>), dim3(ew_grid(N * (HH / 4))), dim3(kBlock), 0, (hipStream_t)stream, N, z, gamma, beta, h_in, h_out, width);
     else
-      hipLaunchKernelGGL((ln_node_update_fwd_k<HH, false>), dim3(ewgrid(N * (HH / 4))), dim3(kBlock), 0, (hipStream_t)stream, N, z, gamma, beta, h_in, h_out, width);
+      hipLaunchKernelGGL((ln_node_update_fwd_k<HH, false>), dim3(ew_grid(N * (HH / 4))), dim3(kBlock), 0, (hipStream_t)stream, N, z, gamma, beta, h_in, h_out, width);
   });
   GNM_LAUNCH_CHECK("ln_node_update_fwd");
   return 0;
@@ -576,7 +567,7 @@ extern "C" int gnm_ln_node_bwd(int64_t N, int H, const float* z, const float* ga
   GNM_DISPATCH_H(H, {
     const int grid = persistent_grid(N, 256, occ_blocks<ln_node_bwd_k<HH>>());
     hipLaunchKernelGGL(ln_node_bwd_k<HH>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, z, gamma, beta,
-                       gh_out, hf, inv_f, hb, inv_b, gP, Q, partials, cdivl(N, grid), width);
+                       gh_out, hf, inv_f, hb, inv_b, gP, Q, partials, cdiv(N, grid), width);
     *nblk_out = grid;
   });
   GNM_LAUNCH_CHECK("ln_node_bwd");
@@ -593,7 +584,7 @@ extern "C" int gnm_ln_edge_bwd_dst(int64_t N, int64_t E, int H, const float* e_o
   GNM_DISPATCH_H(H, {
     const int grid = persistent_grid(N, 64, occ_blocks<ln_edge_bwd_dst_k<HH>>());
     hipLaunchKernelGGL(ln_edge_bwd_dst_k<HH>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, e_out, t, gamma,
-                       beta, ge, P, Q, isrc, in_ptr, gP, gt, partials, cdivl(N, grid), width);
+                       beta, ge, P, Q, isrc, in_ptr, gP, gt, partials, cdiv(N, grid), width);
     *nblk_out = grid;
   });
   GNM_LAUNCH_CHECK("ln_edge_bwd_dst");
@@ -608,7 +599,7 @@ extern "C" int gnm_ln_edge_bwd_src(int64_t N, int64_t E, int H, const float* e_o
   GNM_DISPATCH_H(H, {
     const int grid = persistent_grid(N, 64, occ_blocks<ln_edge_bwd_src_k<HH>>());
     hipLaunchKernelGGL(ln_edge_bwd_src_k<HH>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, e_out, gt, Q,
-                       out_ptr, out_pos, out_dst, gP, cdivl(N, grid));
+                       out_ptr, out_pos, out_dst, gP, cdiv(N, grid));
   });
   GNM_LAUNCH_CHECK("ln_edge_bwd_src");
   return 0;
@@ -621,10 +612,7 @@ extern "C" int gnm_ln_edge_bwd_src_fix(int64_t nfix, const int32_t* fix_nodes, i
                 "ln_edge_bwd_src_fix: null/neg argument");
   if (nfix == 0) return 0;
   GNM_DISPATCH_H(H, {
-    int64_t grid = cdivl(nfix, kWavesPerBlock);
-    const int64_t cap = (int64_t)num_cus() * 8;
-    if (grid > cap) grid = cap;
-    hipLaunchKernelGGL(ln_edge_bwd_src_fix_k<HH>, dim3((int)grid), dim3(kBlock), 0, (hipStream_t)stream, nfix, fix_nodes, e_out, gt, Q,
+    hipLaunchKernelGGL(ln_edge_bwd_src_fix_k<HH>, dim3(ew_grid(nfix, kWavesPerBlock)), dim3(kBlock), 0, (hipStream_t)stream, nfix, fix_nodes, e_out, gt, Q,
                        out_ptr, out_pos, out_dst, gP);
   });
   GNM_LAUNCH_CHECK("ln_edge_bwd_src_fix");
@@ -641,7 +629,7 @@ extern "C" int gnm_ln_wide_row_stats(int64_t R, int C, const float* x, int64_t c
   GNM_CHECK_ARG(width >= 1 && width <= C * kWideH, "ln_wide_row_stats: width must be in [1, 256 C]");
   const int grid = persistent_grid(R, 64, occ_blocks<ln_wide_row_stats_k>());
   hipLaunchKernelGGL(ln_wide_row_stats_k, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, R, C, x, chunk_stride, width, stat,
-                     cdivl(R, grid));
+                     cdiv(R, grid));
   GNM_LAUNCH_CHECK("ln_wide_row_stats");
   return 0;
 }
@@ -656,10 +644,10 @@ extern "C" int gnm_ln_wide_edge_gate_fwd(int64_t N, int64_t E, const float* t, c
   const int grid = persistent_grid(N, 64, occ_blocks<ln_wide_edge_gate_fwd_k<true>>());
   if (e_in)
     hipLaunchKernelGGL((ln_wide_edge_gate_fwd_k<true>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, t, e_in, gamma, beta, stat,
-                       P, isrc, in_ptr, e_out, hf, inv_f, cdivl(N, grid), c0, width);
+                       P, isrc, in_ptr, e_out, hf, inv_f, cdiv(N, grid), c0, width);
   else
     hipLaunchKernelGGL((ln_wide_edge_gate_fwd_k<false>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, t, e_in, gamma, beta, stat,
-                       P, isrc, in_ptr, e_out, hf, inv_f, cdivl(N, grid), c0, width);
+                       P, isrc, in_ptr, e_out, hf, inv_f, cdiv(N, grid), c0, width);
   GNM_LAUNCH_CHECK("ln_wide_edge_gate_fwd");
   return 0;
 }
@@ -669,10 +657,10 @@ extern "C" int gnm_ln_wide_node_update_fwd(int64_t N, const float* z, const floa
   GNM_CHECK_WIDE("ln_wide_node_update_fwd", c0, width);
   GNM_CHECK_ARG(N >= 0 && z && stat && gamma && beta && h_out, "ln_wide_node_update_fwd: null/neg argument");   // h_in == NULL: no residual
   if (h_in)
-    hipLaunchKernelGGL((ln_wide_node_update_fwd_k<true>), dim3(ewgrid(N * (kWideH / 4))), dim3(kBlock), 0, (hipStream_t)stream, N, z, stat,
+    hipLaunchKernelGGL((ln_wide_node_update_fwd_k<true>), dim3(ew_grid(N * (kWideH / 4))), dim3(kBlock), 0, (hipStream_t)stream, N, z, stat,
                        gamma, beta, h_in, h_out, c0, width);
   else
-    hipLaunchKernelGGL((ln_wide_node_update_fwd_k<false>), dim3(ewgrid(N * (kWideH / 4))), dim3(kBlock), 0, (hipStream_t)stream, N, z, stat,
+    hipLaunchKernelGGL((ln_wide_node_update_fwd_k<false>), dim3(ew_grid(N * (kWideH / 4))), dim3(kBlock), 0, (hipStream_t)stream, N, z, stat,
                        gamma, beta, h_in, h_out, c0, width);
   GNM_LAUNCH_CHECK("ln_wide_node_update_fwd");
   return 0;
@@ -685,7 +673,7 @@ extern "C" int gnm_ln_wide_node_bwd_sums(int64_t N, const float* z, const float*
   GNM_CHECK_ARG(N >= 0 && z && stat && gamma && beta && gh_out && rowsum && partials && nblk_out, "ln_wide_node_bwd_sums: null/neg argument");
   const int grid = persistent_grid(N, 256, occ_blocks<ln_wide_node_bwd_sums_k>());
   hipLaunchKernelGGL(ln_wide_node_bwd_sums_k, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, z, stat, gamma, beta, gh_out, rowsum,
-                     partials, cdivl(N, grid), c0, width);
+                     partials, cdiv(N, grid), c0, width);
   *nblk_out = grid;
   GNM_LAUNCH_CHECK("ln_wide_node_bwd_sums");
   return 0;
@@ -699,7 +687,7 @@ extern "C" int gnm_ln_wide_node_bwd_apply(int64_t N, const float* z, const float
                 "ln_wide_node_bwd_apply: null/neg argument");
   const int grid = persistent_grid(N, 256, occ_blocks<ln_wide_node_bwd_apply_k>());
   hipLaunchKernelGGL(ln_wide_node_bwd_apply_k, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, z, stat, gamma, beta, gh_out, rowsum,
-                     hf, inv_f, hb, inv_b, gP, Q, cdivl(N, grid), c0, width);
+                     hf, inv_f, hb, inv_b, gP, Q, cdiv(N, grid), c0, width);
   GNM_LAUNCH_CHECK("ln_wide_node_bwd_apply");
   return 0;
 }
@@ -713,7 +701,7 @@ extern "C" int gnm_ln_wide_edge_bwd_sums(int64_t N, int64_t E, const float* e_ou
                     nblk_out, "ln_wide_edge_bwd_sums: null/neg argument");
   const int grid = persistent_grid(N, 64, occ_blocks<ln_wide_edge_bwd_sums_k>());
   hipLaunchKernelGGL(ln_wide_edge_bwd_sums_k, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, e_out, t, stat, gamma, beta, ge, P, Q,
-                     isrc, in_ptr, gP, rowsum, partials, cdivl(N, grid), c0, width);
+                     isrc, in_ptr, gP, rowsum, partials, cdiv(N, grid), c0, width);
   *nblk_out = grid;
   GNM_LAUNCH_CHECK("ln_wide_edge_bwd_sums");
   return 0;
@@ -727,7 +715,7 @@ extern "C" int gnm_ln_wide_edge_bwd_apply(int64_t N, int64_t E, const float* t, 
                 "ln_wide_edge_bwd_apply: null/neg argument");
   const int grid = persistent_grid(N, 64, occ_blocks<ln_wide_edge_bwd_apply_k>());
   hipLaunchKernelGGL(ln_wide_edge_bwd_apply_k, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, N, t, stat, gamma, beta, ge, rowsum,
-                     in_ptr, gt, gP, cdivl(N, grid), c0, width);
+                     in_ptr, gt, gP, cdiv(N, grid), c0, width);
   GNM_LAUNCH_CHECK("ln_wide_edge_bwd_apply");
   return 0;
 }

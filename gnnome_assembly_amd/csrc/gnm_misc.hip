@@ -1,13 +1,10 @@
-// Predictor epilogue, loss, and the small reductions / gathers around the layer stack (gfx950).
+// Predictor epilogue and the small reductions / gathers around the layer stack (gfx950).
 //
 //   predictor_score_*   score_predictor.py:12-25 in the split-W1 form
 //                       relu(Ps[src] + Pd[dst] + e W1e^T + b1) . W2 + b2   (no [E,3H] concat)
-//   bce_fwd_bwd         train.py:210-211,253-255 BCEWithLogitsLoss(pos_weight), mean, + dloss/dlogit
-//   bce_stats_fwd_bwd   the same, + TP/TN/FP/FN (utils.py:217-223) and the epoch sums, from the same pass
 //   colsum / seg_sum_rows / gather_rows / relu_mask: bias gradients, segmented sums of the
 //                       predictor's [E,64] gradient rows, edge-id -> internal-order gather.
 #include "gnm_common.h"
-#include "gnm_bce.h"
 
 namespace gnm {
 
@@ -163,111 +160,10 @@ __global__ void relu_mask_k(int64_t n, float* __restrict__ x, const float* __res
     x[i] = ref[i] > 0.f ? x[i] : 0.f;
 }
 
-// softplusf_, bce_term_, bce_grad_, bce_block_sum_ and the rounding threshold live in gnm_bce.h (gnm_symloss.hip shares them).
-// The threshold's literal is spelled here as well -- tests/loss_counts_common.py reads it from this file -- and must be the header's:
-namespace misc_literal {
-constexpr float kSigmoidRoundsUp = 0x1.800002p-24f;
-}
-static_assert(misc_literal::kSigmoidRoundsUp == kSigmoidRoundsUp, "gnm_bce.h and gnm_misc.hip disagree on kSigmoidRoundsUp");
-
-// STATS: also TP TN FP FN of p = round(sigmoid(x)) against y as four int32 per block behind the kMaxPartialBlocks loss partials
-// (a NaN logit and a label that is neither 0 nor 1 fail every comparison and are counted nowhere), and gscore may be NULL (no
-// per-edge store).  Elements, their order per thread and the loss arithmetic are the same for both instantiations: the loss
-// partials are bit-identical.
-template <bool STATS>
-__global__ __launch_bounds__(kBlock) void bce_fwd_bwd_k(int64_t E, const float* __restrict__ x,
-                                                        const float* __restrict__ y, float pw,
-                                                        float inv_e, float* __restrict__ gscore,
-                                                        double* __restrict__ ws) {
-  __shared__ double red[kBlock];
-  __shared__ int cred[kWavesPerBlock][4];
-  double acc = 0.0;
-  int tp = 0, tn = 0, fp = 0, fn = 0;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < E; i += (int64_t)gridDim.x * kBlock) {
-    const float xi = x[i], yi = y[i];
-    float p, q;
-    acc += (double)bce_term_(xi, yi, pw, p, q);
-    if (!STATS || gscore) gscore[i] = bce_grad_(yi, pw, p, q, inv_e);
-    if (STATS) {
-      const bool p1 = xi >= kSigmoidRoundsUp, p0 = xi < kSigmoidRoundsUp, y1 = yi == 1.f, y0 = yi == 0.f;
-      tp += p1 && y1; tn += p0 && y0; fp += p1 && y0; fn += p0 && y1;
-    }
-  }
-  bce_block_sum_(acc, red);
-  if (threadIdx.x == 0) ws[blockIdx.x] = red[0];
-  if (STATS) {
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      tp += __shfl_xor(tp, off, kWave); tn += __shfl_xor(tn, off, kWave);
-      fp += __shfl_xor(fp, off, kWave); fn += __shfl_xor(fn, off, kWave);
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-      int* c = cred[threadIdx.x / kWave];
-      c[0] = tp; c[1] = tn; c[2] = fp; c[3] = fn;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-      int s = 0;
-#pragma unroll
-      for (int w = 0; w < kWavesPerBlock; ++w) s += cred[w][threadIdx.x];
-      reinterpret_cast<int*>(ws + kMaxPartialBlocks)[blockIdx.x * 4 + threadIdx.x] = s;
-    }
-  }
-}
-
-template <bool STATS>
-__global__ void bce_finalize_k(const double* __restrict__ ws, int nblk, double inv_e,
-                               float* __restrict__ loss_out, int64_t* __restrict__ counts_out,
-                               BceEpochAcc* __restrict__ epoch_acc) {
-  __shared__ double red[256];
-  double acc = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 256) acc += ws[b];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const float loss = (float)(red[0] * inv_e);
-  if (threadIdx.x == 0) loss_out[0] = loss;
-  if (STATS) {
-    if (threadIdx.x < kWave) {                  // the first wave: lane l takes blocks l, l + 64, ...; integers, any order
-      const int4* bc = reinterpret_cast<const int4*>(ws + kMaxPartialBlocks);
-      long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-      for (int b = threadIdx.x; b < nblk; b += kWave) {
-        const int4 v = bc[b];
-        c0 += v.x; c1 += v.y; c2 += v.z; c3 += v.w;
-      }
-#pragma unroll
-      for (int off = 1; off < kWave; off <<= 1) {
-        c0 += __shfl_xor(c0, off, kWave); c1 += __shfl_xor(c1, off, kWave);
-        c2 += __shfl_xor(c2, off, kWave); c3 += __shfl_xor(c3, off, kWave);
-      }
-      if (threadIdx.x == 0) {
-        counts_out[0] = c0; counts_out[1] = c1; counts_out[2] = c2; counts_out[3] = c3;
-        if (epoch_acc) {
-          epoch_acc->loss_sum += (double)loss;
-          epoch_acc->steps += 1;
-          epoch_acc->counts[0] += c0; epoch_acc->counts[1] += c1;
-          epoch_acc->counts[2] += c2; epoch_acc->counts[3] += c3;
-        }
-      }
-    }
-  }
-}
 
 }  // namespace gnm
 
 using namespace gnm;
-
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int ew_grid2(int64_t items, int block) {
-  int64_t g = cdiv(items, block);
-  const int64_t cap = (int64_t)num_cus() * 8;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
 
 #define GNM_DISPATCH_W(W, ...)                                     \
   switch (W) {                                                     \
@@ -283,7 +179,7 @@ extern "C" int gnm_predictor_score_fwd(int64_t E, int HS, float* hid, const floa
                                        const float* b2, const int32_t* perm, float* scores,
                                        void* stream) {
   GNM_CHECK_ARG(E >= 0 && hid && Pn && isrc && idst && W2 && b2 && perm && scores, "predictor_score_fwd: null/neg argument");
-  GNM_DISPATCH_W(HS, hipLaunchKernelGGL(predictor_score_fwd_k<WW>, dim3(ew_grid2(E * (WW / 4), kBlock)),
+  GNM_DISPATCH_W(HS, hipLaunchKernelGGL(predictor_score_fwd_k<WW>, dim3(ew_grid(E * (WW / 4))),
                                         dim3(kBlock), 0, (hipStream_t)stream, E, hid, Pn, isrc, idst,
                                         W2, b2, perm, scores));
   GNM_LAUNCH_CHECK("predictor_score_fwd");
@@ -386,7 +282,7 @@ extern "C" int gnm_colsum_f32(int64_t M, int64_t W, const float* X, int64_t ld, 
 extern "C" int gnm_gather_rows_f32(int64_t M, int64_t W, const float* X, const int32_t* idx,
                                    float* out, void* stream) {
   GNM_CHECK_ARG(M >= 0 && W > 0 && X && idx && out, "gather_rows_f32: bad argument");
-  hipLaunchKernelGGL(gather_rows_k, dim3(ew_grid2(M * W, 256)), dim3(256), 0, (hipStream_t)stream, M,
+  hipLaunchKernelGGL(gather_rows_k, dim3(ew_grid(M * W, 256)), dim3(256), 0, (hipStream_t)stream, M,
                      W, X, idx, out);
   GNM_LAUNCH_CHECK("gather_rows_f32");
   return 0;
@@ -394,45 +290,7 @@ extern "C" int gnm_gather_rows_f32(int64_t M, int64_t W, const float* X, const i
 
 extern "C" int gnm_relu_mask_f32(int64_t n, float* x, const float* ref, void* stream) {
   GNM_CHECK_ARG(n >= 0 && x && ref, "relu_mask_f32: bad argument");
-  hipLaunchKernelGGL(relu_mask_k, dim3(ew_grid2(n, 256)), dim3(256), 0, (hipStream_t)stream, n, x, ref);
+  hipLaunchKernelGGL(relu_mask_k, dim3(ew_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, n, x, ref);
   GNM_LAUNCH_CHECK("relu_mask_f32");
-  return 0;
-}
-
-extern "C" int gnm_bce_fwd_bwd(int64_t E, const float* scores, const float* y, float pos_weight,
-                               float* loss_out, float* gscore, void* ws, size_t ws_bytes,
-                               void* stream) {
-  GNM_CHECK_ARG(E > 0 && scores && y && loss_out && gscore, "bce_fwd_bwd: bad argument");
-  const int grid = bce_grid(E);
-  GNM_CHECK_ARG(ws && ws_bytes >= (size_t)grid * sizeof(double), "bce_fwd_bwd: workspace too small");
-  hipLaunchKernelGGL(bce_fwd_bwd_k<false>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, E, scores, y,
-                     pos_weight, (float)(1.0 / (double)E), gscore, (double*)ws);
-  GNM_LAUNCH_CHECK("bce_fwd_bwd");
-  hipLaunchKernelGGL(bce_finalize_k<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
-                     grid, 1.0 / (double)E, loss_out, (int64_t*)nullptr, (BceEpochAcc*)nullptr);
-  GNM_LAUNCH_CHECK("bce finalize");
-  return 0;
-}
-
-// ws: double[kMaxPartialBlocks] loss partials, then int32[kMaxPartialBlocks][4] block counts
-extern "C" size_t gnm_bce_stats_workspace_bytes(void) {
-  return (size_t)kMaxPartialBlocks * (sizeof(double) + 4 * sizeof(int32_t));
-}
-
-extern "C" int gnm_bce_stats_fwd_bwd(int64_t E, const float* scores, const float* y, float pos_weight,
-                                     float* loss_out, float* gscore, int64_t* counts_out, void* epoch_acc,
-                                     void* ws, size_t ws_bytes, void* stream) {
-  static_assert(sizeof(BceEpochAcc) == 48, "gnm.h: epoch_acc is 48 bytes");
-  GNM_CHECK_ARG(E > 0 && scores && y && loss_out && counts_out, "bce_stats_fwd_bwd: bad argument");
-  GNM_CHECK_ARG(ws && ws_bytes >= gnm_bce_stats_workspace_bytes(), "bce_stats_fwd_bwd: workspace too small");
-  GNM_CHECK_ARG((uintptr_t)ws % 16 == 0 && (!epoch_acc || (uintptr_t)epoch_acc % 8 == 0) && (uintptr_t)counts_out % 8 == 0,
-                "bce_stats_fwd_bwd: ws must be 16-byte, counts_out and epoch_acc 8-byte aligned");
-  const int grid = bce_grid(E);
-  hipLaunchKernelGGL(bce_fwd_bwd_k<true>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, E, scores, y,
-                     pos_weight, (float)(1.0 / (double)E), gscore, (double*)ws);
-  GNM_LAUNCH_CHECK("bce_stats_fwd_bwd");
-  hipLaunchKernelGGL(bce_finalize_k<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
-                     grid, 1.0 / (double)E, loss_out, counts_out, (BceEpochAcc*)epoch_acc);
-  GNM_LAUNCH_CHECK("bce stats finalize");
   return 0;
 }

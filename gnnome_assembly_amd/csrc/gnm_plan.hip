@@ -209,18 +209,14 @@ extern "C" int gnm_graph_build_sweep_plan_device(const int32_t* isrc, const int3
   if (hipMemsetAsync(first, 0x7f, sizeof(int32_t) * (size_t)N, st) != hipSuccess) return -2;     // 0x7f7f7f7f > any row
   if (hipMemsetAsync(last, 0xff, sizeof(int32_t) * (size_t)N, st) != hipSuccess) return -2;      // -1
   if (peak && hipMemsetAsync(peak, 0, sizeof(int32_t), st) != hipSuccess) return -2;
-  int g = (int)((E + 255) / 256);
-  if (g > num_cus() * 8) g = num_cus() * 8;
-  hipLaunchKernelGGL(plan_first_last_k, dim3(g), dim3(256), 0, st, E, isrc, first, last);
+  hipLaunchKernelGGL(plan_first_last_k, dim3(ew_grid(E, 256)), dim3(256), 0, st, E, isrc, first, last);
   GNM_LAUNCH_CHECK("plan_first_last");
   const int64_t nblk = (N + nodes_per_block - 1) / nodes_per_block;
   hipLaunchKernelGGL(plan_build_k, dim3((unsigned)((nblk + PW - 1) / PW)), dim3(64 * PW), 0, st, N, isrc, idst, in_ptr,
                      (const int32_t*)first, (const int32_t*)last, nodes_per_block, nslots, margin, nblk, sinfo, dinfo, served, peak);
   GNM_LAUNCH_CHECK("plan_build");
   if (fix_nodes) {
-    int gf = (int)((N + 255) / 256);
-    if (gf > num_cus() * 8) gf = num_cus() * 8;
-    hipLaunchKernelGGL(plan_fix_list_k, dim3(gf), dim3(256), 0, st, N, (const uint8_t*)served, fix_nodes);
+    hipLaunchKernelGGL(plan_fix_list_k, dim3(ew_grid(N, 256)), dim3(256), 0, st, N, (const uint8_t*)served, fix_nodes);
     GNM_LAUNCH_CHECK("plan_fix_list");
   }
   return 0;

@@ -340,7 +340,6 @@ __global__ __launch_bounds__(256) void pred_slab_reduce_k(const float* __restric
 
 using namespace gnm;
 
-static inline int64_t cdivp(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static size_t pack_f_bytes(int H) { return (size_t)2 * (H / 8) * 64 * 16; }     // W1e NT pack: 2 column blocks x H / 8 k-quads
 static size_t pack_b_bytes(int H) { return (size_t)(H / 32) * (PS / 8) * 64 * 16; }   // W1e NN pack: H / 32 column blocks x 8 k-quads
 
@@ -355,14 +354,14 @@ static int predictor_fused_fwd_impl(int64_t E, const float* e, const float* W1e,
                                     const float* b2, float* hid, float* scores, void* ws, hipStream_t st) {
   hipLaunchKernelGGL(pack_wk_k, dim3(8), dim3(256), 0, st, W1e, ldw, 2, PHT / 8, 0, (float*)ws);
   GNM_LAUNCH_CHECK("predictor pack (NT)");
-  const int64_t ntiles = cdivp(E, PT);
+  const int64_t ntiles = cdiv(E, PT);
   const int grid = persistent_grid(ntiles, 4, occ_blocks<pred_fwd_k<true, PHT>>());
   if (hid)
     hipLaunchKernelGGL((pred_fwd_k<true, PHT>), dim3(grid), dim3(kBlock), 0, st, E, e, (const float*)ws, b1, Pn, isrc, idst,
-                       perm, W2, b2, hid, scores, cdivp(ntiles, grid));
+                       perm, W2, b2, hid, scores, cdiv(ntiles, grid));
   else
     hipLaunchKernelGGL((pred_fwd_k<false, PHT>), dim3(grid), dim3(kBlock), 0, st, E, e, (const float*)ws, b1, Pn, isrc, idst,
-                       perm, W2, b2, hid, scores, cdivp(ntiles, grid));
+                       perm, W2, b2, hid, scores, cdiv(ntiles, grid));
   GNM_LAUNCH_CHECK("predictor_fused_fwd");
   return 0;
 }
@@ -389,10 +388,10 @@ static int predictor_fused_bwd_impl(int64_t E, float* hid, const float* gscore, 
   float* slab = (float*)((char*)ws + pack_f_bytes(PHT) + pack_b_bytes(PHT));
   hipLaunchKernelGGL(pack_wk_k, dim3(8), dim3(256), 0, st, W1e, ldw, PHT / 32, PS / 8, 1, wp);
   GNM_LAUNCH_CHECK("predictor pack (NN)");
-  const int64_t ntiles = cdivp(E, PT);
+  const int64_t ntiles = cdiv(E, PT);
   const int grid = persistent_grid(ntiles, 4, occ_blocks<pred_bwd_k<PHT>>());
   hipLaunchKernelGGL(pred_bwd_k<PHT>, dim3(grid), dim3(kBlock), 0, st, E, hid, gscore, perm, W2, e, (const float*)wp, ge,
-                     slab, partials, cdivp(ntiles, grid));
+                     slab, partials, cdiv(ntiles, grid));
   GNM_LAUNCH_CHECK("predictor_fused_bwd");
   static_assert((PS * PHT) % 128 == 0, "slab_reduce_128 covers 128 elements per workgroup");
   hipLaunchKernelGGL(pred_slab_reduce_k, dim3(PS * PHT / 128), dim3(256), 0, st, (const float*)slab, grid, PS * PHT, gW1e);

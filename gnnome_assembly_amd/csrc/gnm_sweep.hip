@@ -367,10 +367,7 @@ static int edge_gate2_fwd_impl(int64_t N, int64_t E, int H, const float* t, cons
     }
     GNM_LAUNCH_CHECK("edge_gate2_fwd");
     if (nfix > 0) {
-      int64_t g2 = (nfix + kWavesPerBlock - 1) / kWavesPerBlock;
-      const int64_t cap = (int64_t)num_cus() * 8;
-      if (g2 > cap) g2 = cap;
-      hipLaunchKernelGGL(node_agg_src_fix_k<HF>, dim3((int)g2), dim3(kBlock), 0, st, nfix, fix_nodes, b.e_out, b.P, out_ptr, out_pos,
+      hipLaunchKernelGGL(node_agg_src_fix_k<HF>, dim3(ew_grid(nfix, kWavesPerBlock)), dim3(kBlock), 0, st, nfix, fix_nodes, b.e_out, b.P, out_ptr, out_pos,
                          out_dst, b.hb, b.inv_b);
       GNM_LAUNCH_CHECK("edge_gate2_fwd fix");
     }

@@ -10,8 +10,8 @@ per-element bars and the case matrix their tests run.  numpy and math only; noth
     zs_blocks(E, cus) / pr_grid(n, cus)            the launch arithmetic of the two entry points, restated
     pagerank_cases(cus) / zscore_cases(cus)        the matrices of tests/test_gpu_features.py and test_features_reference_cpu.py
 
-Launch arithmetic (read in gnm_features.hip): fgrid(n) = min(cdiv(n, 256), CUS * 8), at least 1, workgroups of 256 threads in
-grid-stride loops; the z-score's statistics kernel runs nb = min(fgrid(E), 2048) workgroups and writes 4 doubles each."""
+Launch arithmetic (read in gnm_features.hip, gnm_common.h): ew_grid(n, 256) = min(cdiv(n, 256), CUS * 8), at least 1, workgroups of 256
+threads in grid-stride loops; the z-score's statistics kernel runs nb = min(ew_grid(E, 256), 2048) workgroups and writes 4 doubles each."""
 import functools
 import math
 

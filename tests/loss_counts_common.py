@@ -15,9 +15,9 @@ WINDOW = 4096               # fp32 steps checked on either side of X_STAR and of
 
 def source_constant():
     """kSigmoidRoundsUp as the kernel's source spells it (a hex float)."""
-    src = open(os.path.join(REPO, "gnnome_assembly_amd", "csrc", "gnm_misc.hip")).read()
+    src = open(os.path.join(REPO, "gnnome_assembly_amd", "csrc", "gnm_bce.h")).read()
     m = re.search(r"constexpr\s+float\s+kSigmoidRoundsUp\s*=\s*(-?0x[0-9a-fA-F.]+p[-+]?\d+)f\s*;", src)
-    assert m, "kSigmoidRoundsUp must be a hex float literal in gnm_misc.hip"
+    assert m, "kSigmoidRoundsUp must be a hex float literal in gnm_bce.h"
     return float.fromhex(m.group(1))
 
 
